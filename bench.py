@@ -11,10 +11,13 @@ sequentially dependent) and the K(t) feedback trajectories
 communicator (RCCL over xGMI, dre_comm_allgather on the library stream).  `--mode strong`: ONE solve, the same device-resident time loop on
 every rank, the independent shifted solves of every fan group farmed over the ranks inside the library, one all-gather per group (meant for --n 5177 / 20209).
 
-Legs after the timed region (rank 0): `roofline` (one profiled solve, HIP events per kernel class on the library's streams), `parity` (K(t)
-of the timed solve against the oracle's committed full-length fixture; the run FAILS on a mismatch), and at N = 1, n = 371 one leg per remaining
-BASELINE config, each with its own roofline, parity and set-up times: `general_path` (SteelProfile(5177), 12 steps — the leg of rounds 2-3),
-`general_path_45` (configs[3] at its stated 45 steps), `general_path_20209` (configs[4]: save_state, 12 steps), `ros2_1357_projection`
+A plain run sets up, warms up, times --steps solves and prints the headline record; `--dump-outputs DIR` writes what the last timed solve
+returned (K(t) and the ADI iteration count of every Lyapunov solve) as DIR/<name>.npy.
+
+With `--full`, legs after the timed region (rank 0): `roofline` (one profiled solve, HIP events per kernel class on the library's streams),
+`parity` (K(t) of the timed solve against the oracle's committed full-length fixture; the run FAILS on a mismatch), and at N = 1, n = 371 one leg
+per remaining BASELINE config, each with its own roofline, parity and set-up times: `general_path` (SteelProfile(5177), 12 steps — the leg of
+rounds 2-3), `general_path_45` (configs[3] at its stated 45 steps), `general_path_20209` (configs[4]: save_state, 12 steps), `ros2_1357_projection`
 (configs[2]: Ros2 with the default Projection(2) shifts, complex pairs); `cpu_baseline` (the NumPy/SciPy oracle, N = 1; configs[0]'s dense
 Rosenbrock solver is timed there too).
 
@@ -65,7 +68,36 @@ def parse():
                     help="replicas mode, N > 1: gather K(t) with the library's own communicator (dre_comm_allgather, default) or torch.distributed")
     ap.add_argument("--save-state", action="store_true", help="save_state=true (BASELINE configs[4]): every X(t) is kept, X stays factored")
     ap.add_argument("--cpu-steps", type=int, default=8, help="Rosenbrock time steps of the bounded CPU-baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline record: roofline (one profiled solve), parity against the oracle's fixture, the other BASELINE configs "
+                         "(rank 0 at N = 1, n = 371) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write K(t) and the ADI iteration counts of the last timed solve as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BUDGET = 60 << 20          # bytes, all arrays of --dump-outputs together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, K, its):
+    """K: (..., nt, m, n) float64 trajectories as a caller receives them (K(t_i) is m x n); its: ADI iterations per Lyapunov solve.  A K larger
+    than the budget is cut to a fixed, seeded sample of its n columns (indices in K_columns.npy)."""
+    os.makedirs(path, exist_ok=True)
+    if os.path.abspath(path).startswith(ROOT + os.sep) and not os.path.exists(os.path.join(path, ".gitignore")):
+        with open(os.path.join(path, ".gitignore"), "w") as f:          # benchmark outputs written inside the checkout stay out of git
+            f.write("*\n")
+    its = np.asarray(its, dtype=np.float64)
+    n = K.shape[-1]
+    col_bytes = K.nbytes // n
+    room = (DUMP_BUDGET - its.nbytes) // (col_bytes + 8)
+    if room < n:
+        cols = np.sort(np.random.default_rng(0).choice(n, size=room, replace=False))
+        K = K[..., cols]
+        np.save(os.path.join(path, "K_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(path, "K.npy"), np.ascontiguousarray(K, dtype=np.float64))
+    np.save(os.path.join(path, "adi_iterations.npy"), its)
 
 
 def roofline_record(stats, n, m, pencil, its_solve, kw, wall):
@@ -495,88 +527,92 @@ def main():
     out = None
     parity_failure = None
     its_last = list(width["its"])
-    if strong and world > 1 and rank != 0:
+    if rank == 0 and args.dump_outputs:
+        # what the last timed solve returned: K(t_i) as m x n matrices (block i of Kdev is m x n column-major), per replica when gathered
+        dump_outputs(args.dump_outputs, (Kall if Kall is not None else Kdev).transpose(-1, -2).cpu().numpy(), its_last)
+    if args.full and strong and world > 1 and rank != 0:
         one_solve(gather=False)      # strong mode: every ADI group enqueues a collective, so the profiled extra solve of rank 0 needs its partners
     if rank == 0:
-        # ---- roofline leg: one extra identical solve with per-kernel HIP-event timing on the library stream
-        ctx.prof_reset()
-        ctx.prof_enable(True)
-        one_solve(gather=False)      # replicas: the profiled solve does not gather (collectives stay matched); strong: all ranks run it (above)
-        stats = ctx.prof_stats()
-        ctx.prof_enable(False)
-        if os.environ.get("DRE_BENCH_CLASSES"):        # builder's view: every kernel class of the profiled solve (stderr; the JSON line is unchanged)
-            for k_, v_ in sorted(stats.items(), key=lambda kv: -kv[1]["ms"]):
-                print(f"[class] {k_:24s} launches {v_['launches']:6d}  ms {v_['ms']:9.3f}  avg_us {v_['ms'] * 1e3 / max(v_['launches'], 1):8.2f}", file=sys.stderr)
-        roof = roofline_record(stats, n, m, pencil, total_iters / (args.steps * (1 if strong else world)), width["kw"], elapsed / args.steps)
-        # ---- parity leg (after the timed region): the K(t) trajectory of the last timed solve of rank 0 against the committed oracle fixture
-        try:
-            parity = parity_check(n, args.nsteps, Kdev.cpu().numpy(), its_last)
-        except SystemExit as e:      # reported AFTER the final barrier: a parity failure must not strand the other ranks in it
-            parity, parity_failure = None, e
-        # ---- general path leg: the sparse multifrontal path north_star names, in the driver-timed record
-        general = general45 = general20k = general20k45 = ros2leg = ros2gen = None
-        if world == 1 and n == 371 and not strong and not args.no_general_path:
-            general = general_path(D, ctx, args, config="BASELINE configs[3], first 12 of its 45 steps (the leg of rounds 2-3)")
-            general45 = general_path(D, ctx, args, nsteps=45, steps=2, warmup=1, config="BASELINE configs[3] at its stated length (one GPU)")
-            general20k = general_path(D, ctx, args, n=20209, nsteps=12, steps=2, warmup=1, save_state=True, config="BASELINE configs[4] (one GPU), 12 of 45 steps")
-            general20k45 = general_path(D, ctx, args, n=20209, nsteps=45, steps=1, warmup=1, save_state=True,
-                                        config="BASELINE configs[4] at its stated length (one GPU): 45 steps, save_state; no oracle fixture of this length "
-                                               "(the 12-step one took the oracle 26 minutes) - tests/test_gpu_r05.py checks it through size-independent properties")
-            ros2leg = ros2_projection_leg(D, ctx)
-            ros2gen = ros2_general_leg(D, ctx)
-        # ---- CPU baseline leg: the oracle (a NumPy/SciPy port with the reference's algorithmic choices) on a bounded sample.
-        # The BLAS thread count matters a lot at this size (128 OpenBLAS threads are 13x SLOWER than one on 371-row panels),
-        # so a two-step probe picks the fastest of a few thread counts and the sample runs with that one.
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:       # rank 0 at N = 1 only
-            sys.path.insert(0, os.path.join(ROOT, "oracle"))
-            import warnings
-            import dre_oracle as o
-            from threadpoolctl import threadpool_limits
-            warnings.simplefilter("ignore")
+        if args.full:
+            # ---- roofline leg: one extra identical solve with per-kernel HIP-event timing on the library stream
+            ctx.prof_reset()
+            ctx.prof_enable(True)
+            one_solve(gather=False)      # replicas: the profiled solve does not gather (collectives stay matched); strong: all ranks run it (above)
+            stats = ctx.prof_stats()
+            ctx.prof_enable(False)
+            if os.environ.get("DRE_BENCH_CLASSES"):        # builder's view: every kernel class of the profiled solve (stderr; the JSON line is unchanged)
+                for k_, v_ in sorted(stats.items(), key=lambda kv: -kv[1]["ms"]):
+                    print(f"[class] {k_:24s} launches {v_['launches']:6d}  ms {v_['ms']:9.3f}  avg_us {v_['ms'] * 1e3 / max(v_['launches'], 1):8.2f}", file=sys.stderr)
+            roof = roofline_record(stats, n, m, pencil, total_iters / (args.steps * (1 if strong else world)), width["kw"], elapsed / args.steps)
+            # ---- parity leg (after the timed region): the K(t) trajectory of the last timed solve of rank 0 against the committed oracle fixture
+            try:
+                parity = parity_check(n, args.nsteps, Kdev.cpu().numpy(), its_last)
+            except SystemExit as e:      # reported AFTER the final barrier: a parity failure must not strand the other ranks in it
+                parity, parity_failure = None, e
+            # ---- general path leg: the sparse multifrontal path north_star names, in the driver-timed record
+            general = general45 = general20k = general20k45 = ros2leg = ros2gen = None
+            if world == 1 and n == 371 and not strong and not args.no_general_path:
+                general = general_path(D, ctx, args, config="BASELINE configs[3], first 12 of its 45 steps (the leg of rounds 2-3)")
+                general45 = general_path(D, ctx, args, nsteps=45, steps=2, warmup=1, config="BASELINE configs[3] at its stated length (one GPU)")
+                general20k = general_path(D, ctx, args, n=20209, nsteps=12, steps=2, warmup=1, save_state=True, config="BASELINE configs[4] (one GPU), 12 of 45 steps")
+                general20k45 = general_path(D, ctx, args, n=20209, nsteps=45, steps=1, warmup=1, save_state=True,
+                                            config="BASELINE configs[4] at its stated length (one GPU): 45 steps, save_state; no oracle fixture of this length "
+                                                   "(the 12-step one took the oracle 26 minutes) - tests/test_gpu_r05.py checks it through size-independent properties")
+                ros2leg = ros2_projection_leg(D, ctx)
+                ros2gen = ros2_general_leg(D, ctx)
+            # ---- CPU baseline leg: the oracle (a NumPy/SciPy port with the reference's algorithmic choices) on a bounded sample.
+            # The BLAS thread count matters a lot at this size (128 OpenBLAS threads are 13x SLOWER than one on 371-row panels),
+            # so a two-step probe picks the fastest of a few thread counts and the sample runs with that one.
+            cpu = None
+            if not args.no_cpu_baseline and world == 1:       # rank 0 at N = 1 only
+                sys.path.insert(0, os.path.join(ROOT, "oracle"))
+                import warnings
+                import dre_oracle as o
+                from threadpoolctl import threadpool_limits
+                warnings.simplefilter("ignore")
 
-            def cpu_run(nsteps_cpu, threads, reuse=False):
-                st = []
-                with threadpool_limits(limits=threads):
-                    tc = time.perf_counter()
-                    o.solve(o.GDREProblem(d.E, d.A, d.B, d.C, o.lowrank(L, Dm), (t0, t0 + dt * nsteps_cpu)),
-                            o.Ros1(o.ADI(shifts=o.Cyclic(list(shifts)), factor_cache=o.FactorCache(reuse=reuse))), dt=dt, stats=st)
-                    tc = time.perf_counter() - tc
-                return sum(x["iters"] for x in st), tc
+                def cpu_run(nsteps_cpu, threads, reuse=False):
+                    st = []
+                    with threadpool_limits(limits=threads):
+                        tc = time.perf_counter()
+                        o.solve(o.GDREProblem(d.E, d.A, d.B, d.C, o.lowrank(L, Dm), (t0, t0 + dt * nsteps_cpu)),
+                                o.Ros1(o.ADI(shifts=o.Cyclic(list(shifts)), factor_cache=o.FactorCache(reuse=reuse))), dt=dt, stats=st)
+                        tc = time.perf_counter() - tc
+                    return sum(x["iters"] for x in st), tc
 
-            ncpu = os.cpu_count() or 1
-            probe = {}
-            big = n > 1500            # one Rosenbrock step of the oracle takes tens of seconds there: the probe IS the sample
-            for th in (sorted({1, 4, min(16, ncpu)}) if not big else [min(16, ncpu)]):
-                print(f"[bench] cpu baseline: probing {th} BLAS thread(s)", file=sys.stderr, flush=True)
-                it_p, t_p = cpu_run(min(args.nsteps, 2), th)
-                probe[th] = it_p / t_p
-                if big: cpu_it, tc, nsteps_cpu = it_p, t_p, min(args.nsteps, 2)
-            best = max(probe, key=probe.get)
-            fair = None
-            if not big:
-                # bounded sample: the full 45-step workload if the probe says it fits ~30 s, else args.cpu_steps steps
-                est_full = 746.0 / probe[best] * (n / 371.0) ** 2
-                nsteps_cpu = args.nsteps if est_full < 30.0 else args.cpu_steps
-                print(f"[bench] cpu baseline: {nsteps_cpu} steps with {best} thread(s)", file=sys.stderr, flush=True)
-                cpu_it, tc = cpu_run(nsteps_cpu, best)
-                it2, tc2 = cpu_run(nsteps_cpu, best, reuse=True)
-                fair = dict(value=it2 / tc2, unit="ADI iterations/s",
-                            note="same sample and threads, sparse LU factors reused per shift like the engine (the reference refactorises every ADI step)")
-            # BASELINE configs[0]: the DENSE Rosenbrock-1 solver on the CPU (reference plumbing, src/riccati/dense_ros1.jl:30-49), a bounded sample
-            dense0 = None
-            if n <= 400:
-                with threadpool_limits(limits=best):
-                    td = time.perf_counter()
-                    o.solve(o.GDREProblem(d.E, d.A, d.B, d.C, o.lowrank(L, Dm).dense(), (t0, t0 + dt * 5)), o.Ros1(), dt=dt)
-                    td = time.perf_counter() - td
-                dense0 = dict(config="BASELINE configs[0]", workload=f"SteelProfile({n}) dense Ros1 on the CPU (oracle), 5 of 45 time steps", s_per_time_step=td / 5.0,
-                              threads=best)
-            cpu = dict(value=cpu_it / tc, unit="ADI iterations/s", cores=best, kind="port", factor_caching_variant=fair, dense_ros1_config0=dense0,
-                       thread_probe_it_per_s={str(k): round(v, 1) for k, v in probe.items()},
-                       sample=f"{nsteps_cpu} of {args.nsteps} Rosenbrock steps of the same workload ({cpu_it} ADI iterations, {tc:.1f} s), "
-                              f"NumPy/SciPy oracle with {best} BLAS thread(s) ({'fastest of the probed counts' if not big else 'single probe at this size'}; {ncpu} host CPUs), "
-                              f"SuperLU refactorised every ADI step like the reference")
+                ncpu = os.cpu_count() or 1
+                probe = {}
+                big = n > 1500            # one Rosenbrock step of the oracle takes tens of seconds there: the probe IS the sample
+                for th in (sorted({1, 4, min(16, ncpu)}) if not big else [min(16, ncpu)]):
+                    print(f"[bench] cpu baseline: probing {th} BLAS thread(s)", file=sys.stderr, flush=True)
+                    it_p, t_p = cpu_run(min(args.nsteps, 2), th)
+                    probe[th] = it_p / t_p
+                    if big: cpu_it, tc, nsteps_cpu = it_p, t_p, min(args.nsteps, 2)
+                best = max(probe, key=probe.get)
+                fair = None
+                if not big:
+                    # bounded sample: the full 45-step workload if the probe says it fits ~30 s, else args.cpu_steps steps
+                    est_full = 746.0 / probe[best] * (n / 371.0) ** 2
+                    nsteps_cpu = args.nsteps if est_full < 30.0 else args.cpu_steps
+                    print(f"[bench] cpu baseline: {nsteps_cpu} steps with {best} thread(s)", file=sys.stderr, flush=True)
+                    cpu_it, tc = cpu_run(nsteps_cpu, best)
+                    it2, tc2 = cpu_run(nsteps_cpu, best, reuse=True)
+                    fair = dict(value=it2 / tc2, unit="ADI iterations/s",
+                                note="same sample and threads, sparse LU factors reused per shift like the engine (the reference refactorises every ADI step)")
+                # BASELINE configs[0]: the DENSE Rosenbrock-1 solver on the CPU (reference plumbing, src/riccati/dense_ros1.jl:30-49), a bounded sample
+                dense0 = None
+                if n <= 400:
+                    with threadpool_limits(limits=best):
+                        td = time.perf_counter()
+                        o.solve(o.GDREProblem(d.E, d.A, d.B, d.C, o.lowrank(L, Dm).dense(), (t0, t0 + dt * 5)), o.Ros1(), dt=dt)
+                        td = time.perf_counter() - td
+                    dense0 = dict(config="BASELINE configs[0]", workload=f"SteelProfile({n}) dense Ros1 on the CPU (oracle), 5 of 45 time steps", s_per_time_step=td / 5.0,
+                                  threads=best)
+                cpu = dict(value=cpu_it / tc, unit="ADI iterations/s", cores=best, kind="port", factor_caching_variant=fair, dense_ros1_config0=dense0,
+                           thread_probe_it_per_s={str(k): round(v, 1) for k, v in probe.items()},
+                           sample=f"{nsteps_cpu} of {args.nsteps} Rosenbrock steps of the same workload ({cpu_it} ADI iterations, {tc:.1f} s), "
+                                  f"NumPy/SciPy oracle with {best} BLAS thread(s) ({'fastest of the probed counts' if not big else 'single probe at this size'}; {ncpu} host CPUs), "
+                                  f"SuperLU refactorised every ADI step like the reference")
         out = {
             "metric": "ADI iterations/sec (GDRE Ros1 LRSIF, SteelProfile surrogate)",
             "value": total_iters / elapsed,
@@ -596,21 +632,16 @@ def main():
                        "adi_iterations_per_solve": total_iters / (args.steps * (1 if strong else world)),
                        "lyapunov_solves_converged": f"{nconv}/{ngale}",
                        "sparse_factorizations_per_solve": nfac,
-                       "parity": parity,
                        "save_state": bool(args.save_state),
                        "parallelism": (f"ONE solve, fan groups shift-sharded x{world} inside the library (one RCCL all-gather per group of up to 8 ADI iterations)" if strong else
                                        f"replicas x{world}" + ((" + K(t) gathered by " + ("dre_comm_allgather (RCCL inside the library)" if use_lib_comm
                                                                                           else "torch.distributed all_gather")) if world > 1 else "")),
                        "comm": ctx.comm_info() if use_lib_comm else comm_note},
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "general_path": general,
-            "general_path_45": general45,
-            "general_path_20209": general20k,
-            "general_path_20209_45": general20k45,
-            "ros2_1357_projection": ros2leg,
-            "ros2_general_5177": ros2gen,
         }
+        if args.full:
+            out["config"]["parity"] = parity
+            out.update(roofline=roof, cpu_baseline=cpu, general_path=general, general_path_45=general45, general_path_20209=general20k,
+                       general_path_20209_45=general20k45, ros2_1357_projection=ros2leg, ros2_general_5177=ros2gen)
         out["setup_ms"] = setup_ms
         out["first_solve_ms"] = first_solve_ms
     if world > 1:

@@ -55,7 +55,7 @@ for k, v in bf.items():
                    fabric_bytes_per_launch=fb + wb, avg_us=au,
                    fabric_GBps=(fb + wb) / (au * 1e-6) / 1e9 if au else None)
 run = None
-try:          # the counter passes ran `bench.py --steps 1 --warmup 1` (+ the profiled extra solve): 3 solves of adi_iterations_per_solve each
+try:          # the counter passes ran `bench.py --full --steps 1 --warmup 1` (+ the profiled extra solve): 3 solves of adi_iterations_per_solve each
     bj = json.loads(open(os.path.join(out_dir, f"bench_under_rocprof_{tag}.json")).read().strip().splitlines()[-1])
     run = dict(solves=3, adi_iterations_per_solve=bj["config"]["adi_iterations_per_solve"],
                note="counter passes: warm-up + 1 timed + 1 profiled solve; one shifted solve per ADI iteration")
