@@ -647,6 +647,29 @@ class Ros2:
     inner_alg: Optional[ADI] = None
 
 
+@dataclass
+class MatrixSign:
+    """Dense GALE algorithm tag (in the place of the reference's `BartelsStewart`, lyapunov/bartels-stewart.jl): the generalized
+    matrix-sign-function iteration on the device.  It requires a c-stable pencil; otherwise DREError(-7, DRE_ERR_NOT_STABLE).
+    tol None: 10 n eps (stop when ||Z + E||_F <= tol ||E||_F); max_refine: refinement steps by replay while the relative residual
+    exceeds 100 n eps."""
+    maxiters: int = 50
+    tol: Optional[float] = None
+    max_refine: int = 2
+
+
+@dataclass
+class Ros3:
+    """DifferentialRiccatiEquations.jl:61 (dense only: X0 must be a matrix, inner_alg MatrixSign())"""
+    inner_alg: Optional[MatrixSign] = None
+
+
+@dataclass
+class Ros4:
+    """DifferentialRiccatiEquations.jl:62 (dense only: X0 must be a matrix, inner_alg MatrixSign())"""
+    inner_alg: Optional[MatrixSign] = None
+
+
 class Callbacks:
     """Observer hooks (src/Callbacks.jl:97-187).  The loop is device resident, so the per-iteration hooks are
     replayed in order after each Lyapunov solve with the recorded norms / shifts; `X` and `residual` are None
@@ -1000,12 +1023,19 @@ def residual(prob, X: LDLt, ctx=None) -> LDLt:
 def solve_gdre(prob: GDREProblem, alg, dt, save_state=False, observer=None, ctx=None, return_stats=False):
     """solve(::GDREProblem{<:LDLᵀ}, ::Ros1/Ros2; dt, save_state, observer)
     (DifferentialRiccatiEquations.jl:78-94, riccati/lowrank_ros1.jl, lowrank_ros2.jl)"""
+    dense_order = {Ros1: 1, Ros2: 2, Ros3: 3, Ros4: 4}.get(type(alg))
     if not isinstance(prob.X0, LDLt):
-        raise TypeError("this engine implements the low-rank path only: X0 must be an LDLᵀ object (lowrank(L, D)); "
-                        "the dense Rosenbrock methods of the reference are outside the accelerated path")
+        if dense_order is None or not isinstance(alg.inner_alg, MatrixSign):
+            raise TypeError("a dense X0 selects the dense Rosenbrock methods, which run on the device only with the matrix-sign-function solver "
+                            "named explicitly, e.g. Ros1(MatrixSign()): it needs a c-stable pencil, unlike the reference's Bartels-Stewart default")
+        return _solve_gdre_dense(prob, alg, dense_order, dt, save_state, observer, ctx, return_stats)
+    if isinstance(alg, (Ros3, Ros4)):
+        raise TypeError("Ros3 and Ros4 have no low-rank formulation: X0 must be a dense matrix")
     order = 1 if isinstance(alg, Ros1) else 2 if isinstance(alg, Ros2) else None
     if order is None:
         raise TypeError("only Ros1 and Ros2 have a low-rank formulation")
+    if isinstance(alg.inner_alg, MatrixSign):
+        raise TypeError("MatrixSign() is a dense solver: it needs a dense X0 (an ndarray), not an LDLᵀ object")
     ctx = ctx or dev.default_context()
     inner = alg.inner_alg if alg.inner_alg is not None else ADI()
     if _needs_state(observer):
@@ -1073,6 +1103,79 @@ def solve_gdre(prob: GDREProblem, alg, dt, save_state=False, observer=None, ctx=
     if return_stats:
         return sol, dict(adi_iters=iters, factorizations=nfac, gales=gales,
                          host_ms=dict(upload=(_t1 - _t0) * 1e3, solve=(_t2 - _t1) * 1e3, results=(_t3 - _t2) * 1e3, hooks=(time.perf_counter() - _t3) * 1e3))
+    return sol
+
+
+# ------------------------------------------------------------------------------------------------
+# Dense path                                 src/riccati/dense_ros{1,2,3,4}.jl, src/lyapunov/bartels-stewart.jl
+# ------------------------------------------------------------------------------------------------
+def _dense_f64(M):
+    M = M.toarray() if sp.issparse(M) else np.asarray(M, dtype=float)       # collect(E) (dense_ros1.jl:16)
+    return np.asfortranarray(M, dtype=float)
+
+
+def _sign_params(alg: MatrixSign):
+    return int(alg.maxiters), float(alg.tol) if alg.tol is not None else 0.0, int(alg.max_refine)
+
+
+def solve_gale_dense(prob: GALEProblem, alg: MatrixSign, ctx=None, return_info=False):
+    """solve(::GALEProblem, ::MatrixSign): A'XE + E'XA = -C with dense X (bartels-stewart.jl:3-12, lyapc replaced by the sign iteration).
+    C may be an ndarray or an LDLᵀ object (densified as bartels-stewart.jl:6-8 does)."""
+    Cm = prob.C.dense() if isinstance(prob.C, LDLt) else prob.C
+    E, A, Cm = _dense_f64(prob.E), _dense_f64(prob.A), _dense_f64(Cm)
+    ctx = ctx or dev.default_context()
+    Ed, Ad, Cd = ctx.upload(E), ctx.upload(A), ctx.upload(Cm)
+    xp = C.c_void_p()
+    ii, dd = (C.c_int64 * 2)(), (C.c_double * 2)()
+    maxiters, tol, max_refine = _sign_params(alg)
+    ctx.chk(ctx.lib.dre_dense_gale_solve(ctx.ptr, Ed.ptr, Ad.ptr, Cd.ptr, maxiters, tol, max_refine, C.byref(xp), ii, dd))
+    X = dev.DenseMatrix(ctx, xp).numpy()
+    if return_info:
+        return X, dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1]))
+    return X
+
+
+def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_stats):
+    """solve(::GDREProblem{<:Matrix}, ::Ros<order>(MatrixSign()); dt, save_state, observer)  (dense_ros{1,2,3,4}.jl), device resident;
+    the observer hooks are replayed afterwards in dense_ros1.jl's order."""
+    ctx = ctx or dev.default_context()
+    E, A, X0 = _dense_f64(prob.E), _dense_f64(prob.A), _dense_f64(prob.X0)
+    Bm, Cm = _dense_f64(prob.B), _dense_f64(prob.C)
+    ups = [ctx.upload(M) for M in (E, A, Bm, Cm, X0)]
+    maxiters, tol, max_refine = _sign_params(alg.inner_alg)
+    r = C.c_void_p()
+    lib = ctx.lib
+    ctx.chk(lib.dre_dense_gdre_solve(ctx.ptr, *[u.ptr for u in ups], float(prob.tspan[0]), float(prob.tspan[1]), float(dt), int(order),
+                                     int(bool(save_state)), maxiters, tol, max_refine, C.byref(r)))
+    try:
+        ii = (C.c_int64 * 7)()
+        lib.dre_gdre_result_info(r, ii)
+        nt, nx, _, _, nsolve, m, n = list(ii)
+        t = np.zeros(nt)
+        lib.dre_gdre_result_times(r, t.ctypes.data_as(C.POINTER(C.c_double)))
+        Kall = np.zeros((nt, n, m))
+        ctx.chk(lib.dre_gdre_result_K_all(ctx.ptr, r, Kall.ctypes.data_as(C.POINTER(C.c_double))))
+        Ks = [Kall[i].T for i in range(nt)]
+        Xs = [prob.X0]                    # first(sol.X) === prob.X0  (test/rail.jl:40)
+        for i in range(1, nx):
+            xp = C.c_void_p()
+            ctx.chk(lib.dre_gdre_result_X_dense(ctx.ptr, r, i, C.byref(xp)))
+            Xs.append(dev.DenseMatrix(ctx, xp).numpy())
+        its, refs = np.zeros(max(nsolve, 1), dtype=np.int64), np.zeros(max(nsolve, 1), dtype=np.int64)
+        res = np.zeros(2 * max(nsolve, 1))
+        lib.dre_gdre_result_dense_stats(r, its.ctypes.data_as(C.POINTER(C.c_int64)), refs.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        res.ctypes.data_as(C.POINTER(C.c_double)))
+    finally:
+        lib.dre_gdre_result_free(r)
+    _call(observer, "observe_gdre_start", prob, alg)
+    for i in range(nt):
+        Xi = Xs[i] if (save_state or i == 0) else (Xs[-1] if i == nt - 1 else None)
+        _call(observer, "observe_gdre_step", t[i], Xi, Ks[i])
+    _call(observer, "observe_gdre_done")
+    sol = DRESolution(Xs, Ks, t)
+    if return_stats:
+        solves = [dict(iters=int(its[j]), refinements=int(refs[j]), res0=float(res[2 * j]), res=float(res[2 * j + 1])) for j in range(nsolve)]
+        return sol, dict(lyapunov_solves=nsolve, solves=solves)
     return sol
 
 
@@ -1448,6 +1551,8 @@ def solve(prob, alg, **kw):
     if isinstance(prob, GDREProblem):
         return solve_gdre(prob, alg, **kw)
     if isinstance(prob, GALEProblem):
+        if isinstance(alg, MatrixSign):
+            return solve_gale_dense(prob, alg, **kw)
         return solve_gmres(prob, alg, **kw) if isinstance(alg, GMRES) else solve_gale(prob, alg, **kw)
     if isinstance(prob, GAREProblem):
         return solve_gare(prob, alg, **kw)

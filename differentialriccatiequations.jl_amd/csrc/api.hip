@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "comm.hpp"
+#include "dense_sign.hpp"
 #include "engine.hpp"
 #include "hostla.hpp"
 #include "profiling.hpp"
@@ -37,6 +38,11 @@ struct dre_gdre_result {
     GdreResult r;
     const dre_pencil* pen = nullptr;
     int m = 0;
+    // dense path (dre_dense_gdre_solve): pen is null, K(t) lives in r.Kt, the states and per-solve statistics here
+    bool dense = false;
+    int n = 0;
+    std::vector<Mat> Xd;
+    std::vector<SignStats> solves;
 };
 
 static thread_local std::string g_noctx_error;
@@ -60,7 +66,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 100; }
+int dre_version(void) { return 101; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -922,6 +928,11 @@ int dre_gdre_solve(dre_ctx* ctx, const dre_pencil* p, const dre_dense* B, const 
     });
 }
 int dre_gdre_result_info(const dre_gdre_result* r, int64_t* info) {
+    if (r->dense) {
+        info[0] = (int64_t)r->r.t.size(); info[1] = (int64_t)r->Xd.size(); info[2] = 0; info[3] = 0;
+        info[4] = (int64_t)r->solves.size(); info[5] = r->m; info[6] = r->n;
+        return DRE_OK;
+    }
     info[0] = (int64_t)r->r.t.size(); info[1] = (int64_t)r->r.X.size(); info[2] = r->r.adi_iters; info[3] = r->r.nfactor;
     info[4] = (int64_t)r->r.gale.size(); info[5] = r->m; info[6] = r->pen->p->n;
     return DRE_OK;
@@ -989,11 +1000,12 @@ int dre_gdre_result_K_all(dre_ctx* ctx, const dre_gdre_result* r, double* K_host
     });
 }
 int dre_gdre_result_X(const dre_gdre_result* r, int i, dre_ldlt** X) {
-    if (i < 0 || i >= (int)r->r.X.size()) return DRE_ERR_INVALID;
+    if (r->dense || i < 0 || i >= (int)r->r.X.size()) return DRE_ERR_INVALID;
     auto* h = new dre_ldlt(); h->x = r->r.X[i]; h->pen = r->pen; *X = h;
     return DRE_OK;
 }
 int dre_gdre_result_gale(const dre_gdre_result* r, int j, int64_t* iinfo, double* dinfo) {
+    if (r->dense) return DRE_ERR_INVALID;
     if (j < 0 || j >= (int)r->r.gale.size()) return DRE_ERR_INVALID;
     const AdiResult& a = r->r.gale[j];
     iinfo[0] = a.iters; iinfo[1] = a.converged; iinfo[2] = a.warnings; iinfo[3] = a.rhs_cols;
@@ -1001,6 +1013,7 @@ int dre_gdre_result_gale(const dre_gdre_result* r, int j, int64_t* iinfo, double
     return DRE_OK;
 }
 int dre_gdre_result_gale_history(const dre_gdre_result* r, int j, int64_t* counts, double* norms, int32_t* norm_iters, double* sre, double* sim) {
+    if (r->dense) return DRE_ERR_INVALID;
     if (j < 0 || j >= (int)r->r.gale.size()) return DRE_ERR_INVALID;
     const AdiResult& g = r->r.gale[j];
     if (counts) { counts[0] = (int64_t)g.norms.size(); counts[1] = (int64_t)g.shifts.size(); }
@@ -1009,6 +1022,7 @@ int dre_gdre_result_gale_history(const dre_gdre_result* r, int j, int64_t* count
     return DRE_OK;
 }
 int dre_gdre_result_gales_all(const dre_gdre_result* r, int64_t* iinfo, double* dinfo, double* norms, int32_t* norm_iters, double* sre, double* sim) {
+    if (r->dense) return DRE_ERR_INVALID;
     size_t on = 0, os = 0;
     for (size_t j = 0; j < r->r.gale.size(); ++j) {
         const AdiResult& g = r->r.gale[j];
@@ -1024,6 +1038,62 @@ int dre_gdre_result_gales_all(const dre_gdre_result* r, int64_t* iinfo, double* 
     return DRE_OK;
 }
 int dre_gdre_result_free(dre_gdre_result* r) { delete r; return DRE_OK; }
+
+// ---- dense path (dense_sign.hip) ---------------------------------------------------------------------------------------------------
+int dre_dense_gale_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, const dre_dense* R, int maxiters, double tol, int max_refine,
+                         dre_dense** X, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && F && R && X, "dre_dense_gale_solve: null argument");
+        const int n = E->m.rows;
+        DRE_REQUIRE(F->m.rows == n && F->m.cols == n && R->m.rows == n && R->m.cols == n, "dre_dense_gale_solve: E, F, R must be n x n");
+        SignLyap lyap(c, E->m, maxiters, tol, max_refine);
+        lyap.factor(F->m);
+        auto* out = new dre_dense();
+        out->m = Mat(c, n, n);
+        SignStats s;
+        try { s = lyap.solve(R->m, out->m); c->sync(); } catch (...) { delete out; throw; }
+        if (iinfo) { iinfo[0] = s.iters; iinfo[1] = s.refinements; }
+        if (dinfo) { dinfo[0] = s.res0; dinfo[1] = s.res; }
+        *X = out;
+    });
+}
+int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
+                         double t0, double tf, double dt, int order, int save_state, int maxiters, double tol, int max_refine,
+                         dre_gdre_result** out) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && A && B && C && X0 && out, "dre_dense_gdre_solve: null argument");
+        DenseGdreResult d = dense_gdre_solve(c, E->m, A->m, B->m, C->m, X0->m, t0, tf, dt, order, save_state != 0, maxiters, tol, max_refine);
+        auto* r = new dre_gdre_result();
+        r->dense = true; r->n = E->m.rows; r->m = B->m.cols;
+        r->r.t = std::move(d.t); r->r.Kt = std::move(d.Kt);
+        r->Xd = std::move(d.X); r->solves = std::move(d.solves);
+        *out = r;
+    });
+}
+int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(r && r->dense, "dre_gdre_result_X_dense: not a dense result");
+        DRE_REQUIRE(i >= 0 && i < (int)r->Xd.size(), "state index out of range");
+        Ctx* c = &ctx->c;
+        auto* h = new dre_dense();
+        h->m = Mat(c, r->n, r->n);
+        copy_mat(c, r->Xd[(size_t)i], h->m);
+        c->sync();
+        *X = h;
+    });
+}
+int dre_gdre_result_dense_stats(const dre_gdre_result* r, int64_t* iters, int64_t* refinements, double* residuals) {
+    if (!r || !r->dense) return DRE_ERR_INVALID;
+    for (size_t j = 0; j < r->solves.size(); ++j) {
+        const SignStats& s = r->solves[j];
+        if (iters) iters[j] = s.iters;
+        if (refinements) refinements[j] = s.refinements;
+        if (residuals) { residuals[2 * j] = s.res0; residuals[2 * j + 1] = s.res; }
+    }
+    return DRE_OK;
+}
 
 // ---- host helpers ------------------------------------------------------------------------------
 int dre_host_eigvals(int n, const double* A, double* wr, double* wi) {

@@ -89,6 +89,12 @@ class DevicePool {
     }
     void trim() { std::lock_guard<std::mutex> lk(mu_); trim_locked(); }
     size_t total_bytes() const { return total_; }
+    size_t cached_bytes() {                          // bytes held in released buffers (reusable without a new hipMalloc)
+        std::lock_guard<std::mutex> lk(mu_);
+        size_t b = 0;
+        for (auto& kv : free_) b += kv.first;
+        return b;
+    }
     long misses() const { return misses_; }          // allocations that went to hipMalloc
 
   private:

@@ -1,0 +1,62 @@
+// Dense path (GDREProblem{<:Matrix}): in-place Gauss-Jordan inversion with partial pivoting, the generalized matrix-sign-function
+// Lyapunov solver built on it, and the dense Rosenbrock drivers Ros1..Ros4 (dense_sign.hip).  See DESIGN.md, "Dense path".
+#pragma once
+#include "common.hpp"
+
+namespace dre {
+
+enum : int { ERR_NOT_STABLE = -7 };    // = DRE_ERR_NOT_STABLE of include/dre_hip.h
+
+#define DENSE_MAX_N 4096               // the pivoting panel keeps ceil(n / 512) rows per thread in registers
+
+// Device-side control words of the inversion and of one sign iteration (read back once per step by the host).
+struct SignCtl {
+    double logdet;      // log |det| of the last inverted matrix (sum of log |pivot|)
+    int singular;       // the inversion met an exactly zero (or non-finite) pivot column
+    int done;           // sign iteration: 0 running, 1 converged, 2 stagnated away from -E (not c-stable), 3 non-finite
+    double dist;        // ||Z_{k+1} + E||_F / ||E||_F
+    double step;        // ||Z_{k+1} - Z_k||_F / ||Z_{k+1}||_F
+    double res;         // relative residual ||R + F'XE + E'XF||_F / ||R||_F of the last residual evaluation
+    double pad[3];
+};
+
+// A <- inv(A) in place (n x n, n <= DENSE_MAX_N); ctl->logdet = log|det A|, ctl->singular set on a zero pivot.  No synchronisation.
+void gj_invert(Ctx* ctx, Mat& A, int* piv_dev, SignCtl* ctl_dev);
+
+struct SignStats { long iters = 0, refinements = 0; double res0 = 0.0, res = 0.0; };
+
+// One pencil E (fixed) with a stage matrix F: the sign iteration keeps its (P_k, c_k) sequence so that further right-hand sides
+// on the same pencil cost only the W recursion (replay).
+class SignLyap {
+  public:
+    SignLyap(Ctx* ctx, const Mat& E, int maxiters, double tol, int max_refine, size_t extra_n2 = 0);
+    // sign iteration on (F, E): throws Error(ERR_NOT_STABLE) / Error(ERR_SINGULAR)
+    void factor(const Mat& F);
+    // F'XE + E'XF = -R (R symmetric) with the kept sequence, refined by replay; X is n x n
+    SignStats solve(const Mat& R, Mat& X);
+    int iters() const { return iters_; }
+
+  private:
+    void replay(const Mat& R, Mat& X);
+    double residual(const Mat& R, const Mat& X);
+    void read_ctl(SignCtl* h);
+    Ctx* c_;
+    int n_, maxiters_, max_refine_, iters_ = 0;
+    double tol_, logdetE_ = 0.0;
+    Mat E_, Einv_, F_, Z_, Zi_, Y_, W_, T_, Res_, Pstore_;
+    std::vector<double> cs_;
+    DevArr<int> piv_;
+    DevArr<SignCtl> ctl_;
+    DevArr<double> part_, nrm_;
+};
+
+struct DenseGdreResult {
+    std::vector<double> t;
+    std::vector<Mat> Kt;         // K(t_i)' as n x m
+    std::vector<Mat> X;          // X(t_i): first and last, or all under save_state
+    std::vector<SignStats> solves;
+};
+DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X0, double t0, double tf, double dt,
+                                 int order, bool save_state, int maxiters, double tol, int max_refine);
+
+}  // namespace dre

@@ -275,7 +275,7 @@ struct LowRankUpdate
 end
 lr_update(A, α, U, V) = LowRankUpdate(A, Float64(α), Matrix{Float64}(U), Matrix{Float64}(V))
 struct GALEProblem
-    E; A; C::LDLᵀ
+    E; A; C            # LDLᵀ (ADI, GMRES) or a dense matrix (MatrixSign)
 end
 split_operator(A::LowRankUpdate) = (A.A, A.α, A.U, permutedims(A.V))
 split_operator(A) = (A, 1.0, nothing, nothing)
@@ -509,7 +509,72 @@ function CommonSolve.solve(prob::GDREProblem{LDLᵀ}, alg::Union{Ros1,Ros2}; dt:
     DRESolution(Xs, Ks, t)
 end
 
+# ---- dense path: solve(::GDREProblem{<:Matrix}, Ros1..Ros4(MatrixSign())), solve(::GALEProblem, MatrixSign()) ----------------------
+"Dense GALE algorithm tag: the generalized matrix-sign-function iteration (needs a c-stable pencil; DREError(-7) otherwise).  tol = 0: 10 n eps."
+Base.@kwdef struct MatrixSign; maxiters::Int = 50; tol::Float64 = 0.0; max_refine::Int = 2; end
+Base.@kwdef struct Ros3; inner_alg = nothing; end
+Base.@kwdef struct Ros4; inner_alg = nothing; end
+
+function download(ctx::Context, d::Ptr{Cvoid})
+    r, c = Ref{Cint}(0), Ref{Cint}(0)
+    ccall((:dre_dense_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), d, r, c)
+    M = zeros(r[], c[])
+    chk(ctx, ccall((:dre_dense_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cint), ctx.ptr, d, M, max(r[], 1)))
+    ccall((:dre_dense_free, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.ptr, d)
+    M
+end
+
+"solve(GALEProblem(E, A, C), MatrixSign()): A'XE + E'XA = -C with dense X (bartels-stewart.jl:3-12, lyapc replaced); an LDLᵀ C is densified"
+function CommonSolve.solve(prob::GALEProblem, alg::MatrixSign; ctx::Context=default_context())
+    C = prob.C isa LDLᵀ ? sum(a * L * D * L' for (a, L, D) in zip(prob.C.alphas, prob.C.Ls, prob.C.Ds)) : prob.C
+    E, A, R = upload(ctx, Matrix(prob.E)), upload(ctx, Matrix(prob.A)), upload(ctx, Matrix(C))
+    X = Ref{Ptr{Cvoid}}(C_NULL)
+    ii, dd = zeros(Int64, 2), zeros(2)
+    chk(ctx, ccall((:dre_dense_gale_solve, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Float64}),
+                   ctx.ptr, E.ptr, A.ptr, R.ptr, alg.maxiters, alg.tol, alg.max_refine, X, ii, dd))
+    download(ctx, X[])
+end
+
+"solve(::GDREProblem{<:Matrix}, Ros1..Ros4(MatrixSign()); dt, save_state, observer)  — src/riccati/dense_ros{1,2,3,4}.jl"
+function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,Ros2,Ros3,Ros4}; dt::Real, save_state::Bool=false, observer=nothing,
+                           ctx::Context=default_context())
+    alg.inner_alg isa MatrixSign || throw(ArgumentError("a dense X0 runs on the device only with the inner algorithm named: Ros1(inner_alg = MatrixSign())"))
+    sa = alg.inner_alg
+    order = alg isa Ros1 ? 1 : alg isa Ros2 ? 2 : alg isa Ros3 ? 3 : 4
+    ops = [upload(ctx, Matrix(M)) for M in (prob.E, prob.A, prob.B, prob.C, prob.X0)]
+    res = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ctx, ccall((:dre_dense_gdre_solve, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}),
+                   ctx.ptr, ops[1].ptr, ops[2].ptr, ops[3].ptr, ops[4].ptr, ops[5].ptr, prob.tspan[1], prob.tspan[2], dt, order, save_state,
+                   sa.maxiters, sa.tol, sa.max_refine, res))
+    info = zeros(Int64, 7)
+    ccall((:dre_gdre_result_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), res[], info)
+    nt, nx, m, n = info[1], info[2], info[6], info[7]
+    t = zeros(nt)
+    ccall((:dre_gdre_result_times, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), res[], t)
+    Kall = zeros(m, n, nt)
+    chk(ctx, ccall((:dre_gdre_result_K_all, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), ctx.ptr, res[], Kall))
+    Ks = [Kall[:, :, i] for i in 1:nt]
+    Xs = Any[prob.X0]                                  # first(sol.X) === prob.X0 (test/rail.jl:40)
+    for i in 1:nx-1
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        chk(ctx, ccall((:dre_gdre_result_X_dense, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), ctx.ptr, res[], i, h))
+        push!(Xs, download(ctx, h[]))
+    end
+    ccall((:dre_gdre_result_free, LIB), Cint, (Ptr{Cvoid},), res[])
+    if observer !== nothing                            # dense_ros1.jl's order, replayed after the device run
+        Callbacks.observe_gdre_start!(observer, prob, alg)
+        for i in 1:nt
+            Xi = (save_state || i == 1) ? Xs[i] : (i == nt ? Xs[end] : nothing)
+            Callbacks.observe_gdre_step!(observer, t[i], Xi, Ks[i])
+        end
+        Callbacks.observe_gdre_done!(observer)
+    end
+    DRESolution(Xs, Ks, t)
+end
+
 export Context, Pencil, LDLᵀ, lowrank, compress!, compress_fast!, concatenate!, residual, lyapunov_apply, ADI, Shifts, Callbacks, GALEProblem, GDREProblem, DRESolution, Ros1, Ros2,
-       LowRankUpdate, lr_update, ADISolver, isdone, solve
+       Ros3, Ros4, MatrixSign, LowRankUpdate, lr_update, ADISolver, isdone, solve
 
 end # module

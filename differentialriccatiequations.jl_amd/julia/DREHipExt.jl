@@ -15,14 +15,21 @@ import CommonSolve
 import DifferentialRiccatiEquations as DRE
 import DREHip
 
-export HipRos1, HipRos2, HipADI
+export HipRos1, HipRos2, HipRos3, HipRos4, HipADI, HipMatrixSign
 
 "Algorithm tags: the reference's inner `ADI` options object is reused unchanged"
 struct HipRos1; inner_alg; end
 struct HipRos2; inner_alg; end
 struct HipADI; alg; end
+struct HipRos3; inner_alg; end
+struct HipRos4; inner_alg; end
+"Dense GALE tag (in the place of the reference's BartelsStewart()): the device's matrix-sign-function solver, c-stable pencils only"
+Base.@kwdef struct HipMatrixSign; maxiters::Int = 50; tol::Float64 = 0.0; max_refine::Int = 2; end
 HipRos1() = HipRos1(nothing)
 HipRos2() = HipRos2(nothing)
+HipRos3() = HipRos3(nothing)
+HipRos4() = HipRos4(nothing)
+to_hip(s::HipMatrixSign) = DREHip.MatrixSign(s.maxiters, s.tol, s.max_refine)
 
 # ---- conversions ------------------------------------------------------------------------------------------------------------------
 function to_hip(X::DRE.LDLᵀ)
@@ -76,5 +83,20 @@ function CommonSolve.solve(prob::DRE.GALEProblem{<:DRE.LDLᵀ}, alg::HipADI; ini
 end
 hip_residual(prob::DRE.GALEProblem{<:DRE.LDLᵀ}, X::DRE.LDLᵀ) =
     from_hip(DREHip.residual(DREHip.GALEProblem(prob.E, to_hip(prob.A), to_hip(prob.C)), to_hip(X)))
+
+# ---- dense path: solve(::GDREProblem{<:Matrix}, ::HipRos1..4(HipMatrixSign()); dt, save_state, observer) (dense_ros{1,2,3,4}.jl) -----
+function CommonSolve.solve(prob::DRE.GDREProblem{<:Matrix}, alg::Union{HipRos1,HipRos2,HipRos3,HipRos4}; dt::Real, save_state::Bool=false, observer=nothing)
+    alg.inner_alg isa HipMatrixSign || throw(ArgumentError("a dense X0 runs on the device only with HipMatrixSign() named as the inner algorithm"))
+    hp = DREHip.GDREProblem(collect(prob.E), collect(prob.A), Matrix{Float64}(prob.B), Matrix{Float64}(prob.C), Matrix{Float64}(prob.X0), prob.tspan)
+    T = alg isa HipRos1 ? DREHip.Ros1 : alg isa HipRos2 ? DREHip.Ros2 : alg isa HipRos3 ? DREHip.Ros3 : DREHip.Ros4
+    sol = DREHip.solve(hp, T(to_hip(alg.inner_alg)); dt, save_state, observer)
+    Xs = Any[prob.X0]                                     # first(sol.X) === prob.X0 (test/rail.jl:40)
+    append!(Xs, sol.X[2:end])
+    DRE.DRESolution(Xs, sol.K, sol.t)
+end
+
+# solve(::GALEProblem, ::HipMatrixSign) in the place of solve(::GALEProblem, ::BartelsStewart) (bartels-stewart.jl:3-12)
+CommonSolve.solve(prob::DRE.GALEProblem, alg::HipMatrixSign) =
+    DREHip.solve(DREHip.GALEProblem(collect(prob.E), collect(prob.A), prob.C isa DRE.LDLᵀ ? Matrix(prob.C) : Matrix{Float64}(prob.C)), to_hip(alg))
 
 end # module

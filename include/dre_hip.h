@@ -33,6 +33,7 @@ extern "C" {
 #define DRE_ERR_SINGULAR (-4)
 #define DRE_ERR_INTERNAL (-5)
 #define DRE_ERR_NODEVICE (-6)
+#define DRE_ERR_NOT_STABLE (-7)   /* dense path: (F, E) is not c-stable, the sign iteration did not reach -E */
 
 /* hard limits of the engine */
 #define DRE_ADI_MAX_ITERS 100000      /* largest dre_adi_options.maxiters (the device keeps the norm history as a ring that the host empties per chunk) */
@@ -359,6 +360,28 @@ int dre_gdre_result_gale_history(const dre_gdre_result* r, int j, int64_t* count
 int dre_gdre_result_gales_all(const dre_gdre_result* r, int64_t* iinfo, double* dinfo, double* norms, int32_t* norm_iters, double* shifts_re,
                               double* shifts_im);
 int dre_gdre_result_free(dre_gdre_result* r);
+
+/* ---- dense path (GDREProblem{<:Matrix}: src/riccati/dense_ros{1,2,3,4}.jl, src/lyapunov/bartels-stewart.jl) ------------------------
+ * Every dense operand is n x n (B n x m, C q x n), n <= 4096.  The Lyapunov solver is the generalized matrix-sign-function iteration
+ * (Benner & Quintana-Orti 1999) on the device in place of the reference's Bartels-Stewart: it requires a c-stable pencil (F, E) and fails
+ * with DRE_ERR_NOT_STABLE otherwise; a singular E or F is DRE_ERR_SINGULAR.  maxiters: sign iterations per pencil; tol <= 0 selects
+ * 10 n eps (stop when ||Z + E||_F <= tol ||E||_F); max_refine: refinement steps by replay while the relative residual exceeds 100 n eps.
+ * Device memory of about (maxiters + 26) n^2 doubles (+ n^2 per saved state) is checked up front (DRE_ERR_ALLOC). */
+/* solve(GALEProblem(E, F, R), MatrixSign()):  F'XE + E'XF = -R   (bartels-stewart.jl:3-12, lyapc replaced)
+   iinfo: [0] sign iterations [1] refinement steps;  dinfo: [0] relative residual before refinement [1] after */
+int dre_dense_gale_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, const dre_dense* R, int maxiters, double tol, int max_refine,
+                         dre_dense** X, int64_t* iinfo, double* dinfo);
+/* solve(GDREProblem{<:Matrix}, Ros<order>(MatrixSign()); dt, save_state), order 1..4 (dense_ros{1,2,3,4}.jl).  The result is a
+ * dre_gdre_result: _info ([2], [3] = 0; [4] = Lyapunov solves), _times, _K, _K_all, _K_device and _free work as for the low-rank path;
+ * dre_gdre_result_X and the _gale* accessors return DRE_ERR_INVALID on it. */
+int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
+                         double t0, double tf, double dt, int order, int save_state, int maxiters, double tol, int max_refine,
+                         dre_gdre_result** out);
+/* stored state i of a dense result as a new n x n matrix (sol.X[i]; index 0 is X0) */
+int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X);
+/* per Lyapunov solve j (info[4] of them): iters[j] sign iterations, refinements[j], residuals[2j], residuals[2j+1] relative residual before /
+   after refinement; any array may be NULL */
+int dre_gdre_result_dense_stats(const dre_gdre_result* r, int64_t* iters, int64_t* refinements, double* residuals /* 2 per solve */);
 
 /* ---- host helpers exposed for CPU tests of the Projection shift pipeline ---------------------- */
 int dre_host_eigvals(int n, const double* A, double* wr, double* wi);
