@@ -651,6 +651,8 @@ class Ros2:
 class MatrixSign:
     """Dense GALE algorithm tag (in the place of the reference's `BartelsStewart`, lyapunov/bartels-stewart.jl): the generalized
     matrix-sign-function iteration on the device.  It requires a c-stable pencil; otherwise DREError(-7, DRE_ERR_NOT_STABLE).
+    Any n up to 46340 (the device's index limit) whose (maxiters + 26) n^2 doubles fit in device memory: the inversions use the register
+    pivoting panel for n <= 4096 and the tournament panel above (context option dense_gj_panel).
     tol None: 10 n eps (stop when ||Z + E||_F <= tol ||E||_F); max_refine: refinement steps by replay while the relative residual
     exceeds 100 n eps."""
     maxiters: int = 50
@@ -1133,6 +1135,20 @@ def solve_gale_dense(prob: GALEProblem, alg: MatrixSign, ctx=None, return_info=F
     if return_info:
         return X, dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1]))
     return X
+
+
+def dense_invert(A, ctx=None):
+    """inv(A) by the device's in-place Gauss-Jordan inversion (dre_dense_invert) with the context's pivoting panel (option dense_gj_panel):
+    (Ainv, piv, logabsdet).  piv holds the row interchanges, LAPACK style with 0-based indices (row j was swapped with row piv[j] >= j);
+    logabsdet = log |det A|.  A singular A raises DREError(-4)."""
+    A = _dense_f64(A)
+    ctx = ctx or dev.default_context()
+    Ad = ctx.upload(A)
+    n = A.shape[0]
+    piv = np.zeros(n, dtype=np.int32)
+    ld = C.c_double()
+    ctx.chk(ctx.lib.dre_dense_invert(ctx.ptr, Ad.ptr, piv.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ld)))
+    return Ad.numpy(), piv, float(ld.value)
 
 
 def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_stats):

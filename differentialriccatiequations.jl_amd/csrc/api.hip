@@ -66,7 +66,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 101; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve)
+int dre_version(void) { return 102; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -198,6 +198,7 @@ static OptionRef option_ref(Ctx& c, const std::string& key) {
     DRE_OPT_I("side_after_panels", side_after_panels)
     DRE_OPT_I("setup_batched", setup_batched)
     DRE_OPT_I("dense_warm", dense_warm)
+    DRE_OPT_I("dense_gj_panel", dense_gj_panel)
     DRE_OPT_I("side_prefetch", side_prefetch)
     DRE_OPT_I("side_gate", side_gate)
     DRE_OPT_I("recurrence_wide", recurrence_wide)
@@ -231,6 +232,8 @@ int dre_ctx_set_option(dre_ctx* ctx, const char* name, double value) {
             ctx->c.comm->emulate = (int)value;
             return;
         }
+        if (key == "dense_gj_panel" && !(value == 0.0 || value == 1.0 || value == 2.0))
+            throw Error(ERR_INVALID, "dre_ctx_set_option: dense_gj_panel must be 0 (auto), 1 (register) or 2 (tournament)");
         const OptionRef r = option_ref(ctx->c, key);
         if (r.i) *r.i = (int)value;
         else if (r.d) *r.d = value;
@@ -1070,6 +1073,24 @@ int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, c
         r->r.t = std::move(d.t); r->r.Kt = std::move(d.Kt);
         r->Xd = std::move(d.X); r->solves = std::move(d.solves);
         *out = r;
+    });
+}
+int dre_dense_invert(dre_ctx* ctx, dre_dense* A, int32_t* piv, double* logabsdet) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(A, "dre_dense_invert: null argument");
+        const int n = A->m.rows;
+        DRE_REQUIRE(A->m.cols == n && n >= 1 && n <= DENSE_MAX_N, "dre_dense_invert: square matrix of order 1 .. " + std::to_string(DENSE_MAX_N) + " expected");
+        DevArr<int> pv(c, n);
+        DevArr<SignCtl> ctl(c, 1);
+        DRE_HIP(hipMemsetAsync(ctl.p, 0, sizeof(SignCtl), c->stream));
+        gj_invert(c, A->m, pv.p, ctl.p);
+        SignCtl h;
+        DRE_HIP(hipMemcpyAsync(&h, ctl.p, sizeof(SignCtl), hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        if (h.singular) throw Error(ERR_SINGULAR, "dre_dense_invert: singular matrix (exactly zero or non-finite pivot)");
+        if (piv) { DRE_HIP(hipMemcpyAsync(piv, pv.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream)); c->sync(); }
+        if (logabsdet) *logabsdet = h.logdet;
     });
 }
 int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X) {

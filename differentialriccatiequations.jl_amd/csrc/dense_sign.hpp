@@ -7,7 +7,14 @@ namespace dre {
 
 enum : int { ERR_NOT_STABLE = -7 };    // = DRE_ERR_NOT_STABLE of include/dre_hip.h
 
-#define DENSE_MAX_N 4096               // the pivoting panel keeps ceil(n / 512) rows per thread in registers
+// Order limits of the dense path.  DENSE_MAX_N is the index limit: every device kernel the dense path launches (dense_sign.hip, the element-wise
+// copies and norms of dense.hip, the GEMM family of gemm.hip) forms element offsets inside an n x n operand either in size_t or as an int
+// row / column index below n, and every int product it forms (row + col * ld of the n x n, n x nb and nb x n operands, the
+// k * n column offset of a stored P_k) stays below 2^31 - 1 while n <= 46340 = floor(sqrt(2^31 - 1)).  Below that limit the device memory
+// decides (require_memory).  GJ_REGISTER_MAX_N is the limit of the register panel, which keeps ceil(n / 512) rows per thread in registers
+// (dense_gj_panel = 1 refuses larger n; the default 0 switches to the tournament panel above it).
+#define DENSE_MAX_N 46340
+#define GJ_REGISTER_MAX_N 4096
 
 // Device-side control words of the inversion and of one sign iteration (read back once per step by the host).
 struct SignCtl {
@@ -20,7 +27,9 @@ struct SignCtl {
     double pad[3];
 };
 
-// A <- inv(A) in place (n x n, n <= DENSE_MAX_N); ctl->logdet = log|det A|, ctl->singular set on a zero pivot.  No synchronisation.
+// A <- inv(A) in place (n x n, n <= DENSE_MAX_N); ctl->logdet = log|det A|, ctl->singular set on a zero pivot; piv[0..n) the row interchanges
+// (LAPACK style: row j was swapped with row piv[j] >= j).  The panel follows ctx->dense_gj_panel (0 auto, 1 register, 2 tournament) and
+// (the tournament panel's width is 32).  No synchronisation.
 void gj_invert(Ctx* ctx, Mat& A, int* piv_dev, SignCtl* ctl_dev);
 
 struct SignStats { long iters = 0, refinements = 0; double res0 = 0.0, res = 0.0; };

@@ -510,7 +510,7 @@ function CommonSolve.solve(prob::GDREProblem{LDLᵀ}, alg::Union{Ros1,Ros2}; dt:
 end
 
 # ---- dense path: solve(::GDREProblem{<:Matrix}, Ros1..Ros4(MatrixSign())), solve(::GALEProblem, MatrixSign()) ----------------------
-"Dense GALE algorithm tag: the generalized matrix-sign-function iteration (needs a c-stable pencil; DREError(-7) otherwise).  tol = 0: 10 n eps."
+"Dense GALE algorithm tag: the generalized matrix-sign-function iteration (needs a c-stable pencil; DREError(-7) otherwise).  tol = 0: 10 n eps.  Any n <= 46340 whose (maxiters + 26) n^2 doubles fit in device memory (register pivoting panel for n <= 4096, tournament panel above: option dense_gj_panel)."
 Base.@kwdef struct MatrixSign; maxiters::Int = 50; tol::Float64 = 0.0; max_refine::Int = 2; end
 Base.@kwdef struct Ros3; inner_alg = nothing; end
 Base.@kwdef struct Ros4; inner_alg = nothing; end

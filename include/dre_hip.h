@@ -93,7 +93,10 @@ int dre_ctx_info(dre_ctx* ctx, int64_t* info /* [0]=CUs [1]=pool bytes */);
  *   "x_side_stream"             Ros1, n <= 1536, no save_state: X is carried as "compressed warm start + ADI increments" and its
  *                               compression (adi.jl:78-80) runs on a second stream beside the next time step (default 1; env
  *                               DRE_X_SIDE_STREAM);  "x_compress_every" = s (default 1) with x_side_stream = 0: single stream,
- *                               X compressed every s-th step only */
+ *                               X compressed every s-th step only
+ *   "dense_gj_panel"            dense path: the pivoting panel of the Gauss-Jordan inversions.  0 (default) auto: the register panel for
+ *                               n <= 4096, the tournament panel above; 1 the register panel only (n > 4096 is DRE_ERR_INVALID); 2 the
+ *                               tournament panel at every n.  Other values are DRE_ERR_INVALID */
 int dre_ctx_set_option(dre_ctx* ctx, const char* name, double value);
 /* the current value of an option of dre_ctx_set_option (tests snapshot and restore what they change; no reference counterpart: the reference's
  * tunables are keyword arguments) */
@@ -362,7 +365,9 @@ int dre_gdre_result_gales_all(const dre_gdre_result* r, int64_t* iinfo, double* 
 int dre_gdre_result_free(dre_gdre_result* r);
 
 /* ---- dense path (GDREProblem{<:Matrix}: src/riccati/dense_ros{1,2,3,4}.jl, src/lyapunov/bartels-stewart.jl) ------------------------
- * Every dense operand is n x n (B n x m, C q x n), n <= 4096.  The Lyapunov solver is the generalized matrix-sign-function iteration
+ * Every dense operand is n x n (B n x m, C q x n), n <= 46340: the index limit of the device kernels (every int element index inside an
+ * n x n operand stays below 2^31); below it the device memory decides.  The Gauss-Jordan inversions use the register pivoting panel for
+ * n <= 4096 and the multi-workgroup tournament panel above (option "dense_gj_panel").  The Lyapunov solver is the generalized matrix-sign-function iteration
  * (Benner & Quintana-Orti 1999) on the device in place of the reference's Bartels-Stewart: it requires a c-stable pencil (F, E) and fails
  * with DRE_ERR_NOT_STABLE otherwise; a singular E or F is DRE_ERR_SINGULAR.  maxiters: sign iterations per pencil; tol <= 0 selects
  * 10 n eps (stop when ||Z + E||_F <= tol ||E||_F); max_refine: refinement steps by replay while the relative residual exceeds 100 n eps.
@@ -377,6 +382,10 @@ int dre_dense_gale_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, c
 int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
                          double t0, double tf, double dt, int order, int save_state, int maxiters, double tol, int max_refine,
                          dre_gdre_result** out);
+/* A <- inv(A) in place with the configured pivoting panel (n x n, n <= 46340); piv (n entries, or NULL): the row interchanges, LAPACK
+ * style with 0-based indices (row j was swapped with row piv[j] >= j); logabsdet (or NULL): log |det A|.  A singular A (an exactly zero or
+ * non-finite pivot) is DRE_ERR_SINGULAR and leaves A undefined. */
+int dre_dense_invert(dre_ctx* ctx, dre_dense* A, int32_t* piv, double* logabsdet);
 /* stored state i of a dense result as a new n x n matrix (sol.X[i]; index 0 is X0) */
 int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X);
 /* per Lyapunov solve j (info[4] of them): iters[j] sign iterations, refinements[j], residuals[2j], residuals[2j+1] relative residual before /
