@@ -649,12 +649,14 @@ class Ros2:
 
 @dataclass
 class MatrixSign:
-    """Dense GALE algorithm tag (in the place of the reference's `BartelsStewart`, lyapunov/bartels-stewart.jl): the generalized
+    """Dense GALE and GARE algorithm tag (in the place of the reference's `BartelsStewart`, lyapunov/bartels-stewart.jl): the generalized
     matrix-sign-function iteration on the device.  It requires a c-stable pencil; otherwise DREError(-7, DRE_ERR_NOT_STABLE).
     Any n up to 46340 (the device's index limit) whose (maxiters + 26) n^2 doubles fit in device memory: the inversions use the register
     pivoting panel for n <= 4096 and the tournament panel above (context option dense_gj_panel).
     tol None: 10 n eps (stop when ||Z + E||_F <= tol ||E||_F); max_refine: refinement steps by replay while the relative residual
-    exceeds 100 n eps."""
+    exceeds 100 n eps.
+    For a GAREProblem (solve_gare_dense): the sign iteration of the 2n x 2n Hamiltonian pencil (n <= 23170; tol None: 10 (2n) eps on the
+    relative step) and max_refine Newton-Kleinman steps."""
     maxiters: int = 50
     tol: Optional[float] = None
     max_refine: int = 2
@@ -1003,9 +1005,14 @@ def solve_(solver: ADISolver) -> LDLt:
 
 
 def residual(prob, X: LDLt, ctx=None) -> LDLt:
-    """residual(::GALEProblem{<:LDLᵀ}, ::LDLᵀ)  (lyapunov/residual.jl:3-31);  residual(::GAREProblem, ::LDLᵀ)  (riccati/residual.jl:5-52)"""
+    """residual(::GALEProblem{<:LDLᵀ}, ::LDLᵀ)  (lyapunov/residual.jl:3-31);  residual(::GAREProblem, ::LDLᵀ)  (riccati/residual.jl:5-52);
+    residual(::GAREProblem, ::ndarray): the dense residual as an ndarray (riccati/residual.jl:54-66, gare_residual_dense)"""
     if isinstance(prob, GAREProblem):
-        return gare_residual(prob, X, ctx)
+        if isinstance(X, LDLt):
+            return gare_residual(prob, X, ctx)
+        if isinstance(X, np.ndarray):
+            return gare_residual_dense(prob, X, ctx)
+        raise TypeError(f"residual(GAREProblem, X): X must be an LDLᵀ object or a dense ndarray, not {type(X).__name__}")
     ctx = ctx or dev.default_context()
     A0, lr = _split_operator(prob.E, prob.A)
     pencil = _pencil_for(prob.E, A0, ctx)
@@ -1562,6 +1569,56 @@ def solve_gare(prob: GAREProblem, alg: Newton, observer=None, ctx=None, return_i
     return X
 
 
+def _gare_dense_operands(prob: GAREProblem, ctx):
+    """E, A densified (as _dense_f64 does for the other dense solvers); G = beta B Rinv B' and Q = gamma C' S C stay factored: B, Ct and the
+    inner matrices with the scalars folded in (None for an identity inner matrix with scalar 1)."""
+    beta, B, Rinv = prob.G
+    gamma, Ct, S = prob.Q
+    B, Ct = _dense_f64(B), _dense_f64(Ct)
+    Rinv, S = np.asarray(Rinv, dtype=float), np.asarray(S, dtype=float)
+    Rs = None if beta == 1 and np.array_equal(Rinv, np.eye(B.shape[1])) else _dense_f64(beta * Rinv)
+    Ss = None if gamma == 1 and np.array_equal(S, np.eye(Ct.shape[1])) else _dense_f64(gamma * S)
+    ups = [ctx.upload(M) for M in (_dense_f64(prob.E), _dense_f64(prob.A), B, Ct)]
+    ups += [ctx.upload(M) if M is not None else None for M in (Rs, Ss)]
+    E, A, Bd, Ctd, Rd, Sd = ups
+    ptr = lambda u: u.ptr if u is not None else None                          # noqa: E731
+    return ups, (ptr(E), ptr(A), ptr(Bd), ptr(Rd), ptr(Ctd), ptr(Sd))
+
+
+def solve_gare_dense(prob: GAREProblem, alg: MatrixSign, ctx=None, return_info=False):
+    """solve(::GAREProblem, ::MatrixSign): the dense stabilizing solution X of Q + A'XE + E'XA − E'XGXE = 0 with G = β B R⁻¹ Bᵀ and
+    Q = γ Cᵀ S C (any scalars and inner matrices), on the device: the sign function of the Hamiltonian pencil, extraction by Householder QR
+    and up to alg.max_refine Newton-Kleinman steps (dre_dense_gare_solve).  Open-loop unstable plants are fine as long as (A, B, E) is
+    stabilizable and (A, C, E) detectable; Hamiltonian eigenvalues on or near the imaginary axis raise DREError(-7).
+    return_info: (X, dict(iters, refinements, res0, res, K)) with the scaled residuals ||R||_F / (||Q||_F + 2 ||A'XE||_F + ||E'XGXE||_F)
+    after extraction and at the end, and the feedback K = R⁻¹BᵀXE (β folded in: K = β R⁻¹ Bᵀ X E)."""
+    ctx = ctx or dev.default_context()
+    keep, ptrs = _gare_dense_operands(prob, ctx)
+    xp = C.c_void_p()
+    ii, dd = (C.c_int64 * 2)(), (C.c_double * 2)()
+    maxiters, tol, max_refine = _sign_params(alg)
+    ctx.chk(ctx.lib.dre_dense_gare_solve(ctx.ptr, *ptrs, maxiters, tol, max_refine, C.byref(xp), ii, dd))
+    X = dev.DenseMatrix(ctx, xp).numpy()
+    del keep
+    if return_info:
+        beta, B, Rinv = prob.G
+        E = prob.E.toarray() if sp.issparse(prob.E) else np.asarray(prob.E, dtype=float)
+        K = (beta * np.asarray(Rinv, dtype=float)) @ (np.asarray(B, dtype=float).T @ X @ E)
+        return X, dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1]), K=K)
+    return X
+
+
+def gare_residual_dense(prob: GAREProblem, X, ctx=None):
+    """residual(::GAREProblem, X::Matrix)  (riccati/residual.jl:54-66) on the device: Q + A'XE + E'XA − E'XGXE (symmetrised) as an ndarray."""
+    ctx = ctx or dev.default_context()
+    keep, ptrs = _gare_dense_operands(prob, ctx)
+    Xd = ctx.upload(_dense_f64(X))
+    rp, nrm = C.c_void_p(), C.c_double()
+    ctx.chk(ctx.lib.dre_dense_gare_residual(ctx.ptr, *ptrs, Xd.ptr, C.byref(rp), C.byref(nrm)))
+    del keep
+    return dev.DenseMatrix(ctx, rp).numpy()
+
+
 def solve(prob, alg, **kw):
     """CommonSolve.solve for the problems of this path."""
     if isinstance(prob, GDREProblem):
@@ -1571,5 +1628,7 @@ def solve(prob, alg, **kw):
             return solve_gale_dense(prob, alg, **kw)
         return solve_gmres(prob, alg, **kw) if isinstance(alg, GMRES) else solve_gale(prob, alg, **kw)
     if isinstance(prob, GAREProblem):
+        if isinstance(alg, MatrixSign):
+            return solve_gare_dense(prob, alg, **kw)
         return solve_gare(prob, alg, **kw)
     raise TypeError(f"unsupported problem type {type(prob).__name__}")

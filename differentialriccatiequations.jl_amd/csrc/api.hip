@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "comm.hpp"
+#include "dense_are.hpp"
 #include "dense_sign.hpp"
 #include "engine.hpp"
 #include "hostla.hpp"
@@ -66,7 +67,8 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 102; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096
+int dre_version(void) { return 103; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+                                        // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1091,6 +1093,30 @@ int dre_dense_invert(dre_ctx* ctx, dre_dense* A, int32_t* piv, double* logabsdet
         if (h.singular) throw Error(ERR_SINGULAR, "dre_dense_invert: singular matrix (exactly zero or non-finite pivot)");
         if (piv) { DRE_HIP(hipMemcpyAsync(piv, pv.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream)); c->sync(); }
         if (logabsdet) *logabsdet = h.logdet;
+    });
+}
+int dre_dense_gare_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                         const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && B && Ct && X, "dre_dense_gare_solve: null argument");
+        DenseGareResult r = dense_gare_solve(&ctx->c, E->m, A->m, B->m, Rinv ? &Rinv->m : nullptr, Ct->m, S ? &S->m : nullptr, maxiters, tol, max_refine);
+        if (iinfo) { iinfo[0] = r.iters; iinfo[1] = r.refinements; }
+        if (dinfo) { dinfo[0] = r.res0; dinfo[1] = r.res; }
+        auto* out = new dre_dense();
+        out->m = std::move(r.X);
+        *X = out;
+    });
+}
+int dre_dense_gare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                            const dre_dense* S, const dre_dense* X, dre_dense** Res, double* norm) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && B && Ct && X && Res, "dre_dense_gare_residual: null argument");
+        double fro = 0.0;
+        Mat R = dense_gare_residual(&ctx->c, E->m, A->m, B->m, Rinv ? &Rinv->m : nullptr, Ct->m, S ? &S->m : nullptr, X->m, &fro);
+        auto* out = new dre_dense();
+        out->m = std::move(R);
+        if (norm) *norm = fro;
+        *Res = out;
     });
 }
 int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X) {

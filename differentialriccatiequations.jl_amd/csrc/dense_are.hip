@@ -1,0 +1,392 @@
+// Dense GARE solver (GAREProblem + MatrixSign; in the place of the reference's riccati/newton.jl for dense data):
+//   Z0 = H = [[A, -G], [-Q, -A']], K = diag(E, E')        the Hamiltonian pencil, 2n x 2n, assembled on the device from the factors of G and Q;
+//   Z_{k+1} = struct((Z_k / c_k + c_k K Z_k^-1 K) / 2)     the generalized sign iteration with determinantal scaling, gj_invert on a copy of Z_k
+//                                                         and eight n x n GEMMs for K W K; the update kernel keeps JZ symmetric (Byers);
+//   (Z_inf + K)[I; XE] = 0                                extraction by the blocked Householder QR of the 2n x n operand [Z12; Z22 + E'];
+//   (A - GXE)'DE + E'D(A - GXE) = -R(X), X <- X + D       Newton-Kleinman refinement with SignLyap on the closed loop.
+// Every kernel indexes n x n blocks of the 2n x 2n operands in size_t (2n <= DENSE_MAX_N).  The host model of exactly this solver is
+// tests/_hamiltonian_sign_model.py.
+#include "dense_are.hpp"
+
+#include <cmath>
+#include <limits>
+#include <memory>
+
+#include "dense.hpp"
+#include "dense_device.hpp"
+#include "profiling.hpp"
+
+namespace dre {
+
+static constexpr int ARE_PARTS = 256;            // workgroups of the fused element-wise + partial-norm kernels
+static constexpr double ARE_SCALE_OFF = 1e-2;    // tests/_hamiltonian_sign_model.py: SCALE_OFF, STAG_WINDOW
+static constexpr int ARE_STAG_WINDOW = 3;
+static constexpr double EPS = 2.220446049250313e-16;
+
+// Device-side control words of the sign iteration and of the residual (read back once per step by the host).
+struct AreCtl {
+    double step;        // ||Z_{k+1} - Z_k||_F / ||Z_{k+1}||_F
+    double best;        // smallest step so far
+    double res;         // scaled residual ||R||_F / (||Q||_F + 2 ||A'XE||_F + ||E'XGXE||_F) of the last residual evaluation
+    double resnorm;     // ||R||_F
+    int since;          // unscaled iterations since the last new minimum of the step
+    int scale;          // determinantal scaling still on
+    int done;           // 0 running, 1 converged, 2 stagnated, 3 non-finite, 4 singular Z_k
+    int pad;
+};
+
+__global__ void k_are_ctl_init(AreCtl* c) {
+    c->step = 0.0; c->best = INFINITY; c->res = 0.0; c->resnorm = 0.0;
+    c->since = 0; c->scale = 1; c->done = 0; c->pad = 0;
+}
+
+static unsigned grid_for(size_t tot) { return (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (tot + 255) / 256)); }
+
+// Z0 = [[A, -sym(G)], [-sym(Q), -A']] into Z and Zi (ld 2n; A, G, Q ld n)
+__global__ __launch_bounds__(256) void k_are_assemble(int n, const double* __restrict__ A, const double* __restrict__ G, const double* __restrict__ Q,
+                                                      double* __restrict__ Z, double* __restrict__ Zi) {
+    const size_t L = 2 * (size_t)n, tot = (size_t)n * n;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = idx % n, j = idx / n, t = j + i * n;
+        const double a = A[idx], at = A[t], g = -0.5 * (G[idx] + G[t]), q = -0.5 * (Q[idx] + Q[t]);
+        const size_t p11 = i + j * L, p12 = i + (n + j) * L, p21 = (n + i) + j * L, p22 = (n + i) + (n + j) * L;
+        Z[p11] = a; Zi[p11] = a;
+        Z[p12] = g; Zi[p12] = g;
+        Z[p21] = q; Zi[p21] = q;
+        Z[p22] = -at; Zi[p22] = -at;
+    }
+}
+
+// Z_{k+1} = struct((Z_k / c + c Y) / 2) with Y = K Z_k^-1 K in Zi, written to Z and to Zi (the next inversion's operand), and the partial sums
+// of ||Z_{k+1} - Z_k||^2 and ||Z_{k+1}||^2 per workgroup.  c = (|det Z_k| / |det K|)^(1/2n) while ctl->scale, else 1.  Thread idx = (i, j) owns
+// the orbits {Z11(i,j), Z22(j,i)} and, for i <= j, {Z12(i,j), Z12(j,i)} and {Z21(i,j), Z21(j,i)}: it reads and writes only its own orbits, so
+// the structured average runs in place.
+__global__ __launch_bounds__(256) void k_are_update(int n, double* __restrict__ Z, double* __restrict__ Zi, const SignCtl* ictl, const AreCtl* actl,
+                                                    double logdetK, double* __restrict__ part) {
+    __shared__ double red[17];
+    if (ictl->singular) return;                     // (uniform: k_are_decide reports it)
+    const double c = actl->scale ? exp((ictl->logdet - logdetK) / (2.0 * n)) : 1.0;
+    const double h0 = 0.5 / c, h1 = 0.5 * c;
+    const size_t L = 2 * (size_t)n, tot = (size_t)n * n;
+    double sd = 0.0, sz = 0.0;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = idx % n, j = idx / n;
+        {   // Z11(i,j) and Z22(j,i):  Z11 := (Z11 - Z22')/2,  Z22 := -Z11'
+            const size_t pa = i + j * L, pb = (n + j) + (n + i) * L;
+            const double a = Z[pa], b = Z[pb];
+            const double s = 0.5 * ((h0 * a + h1 * Zi[pa]) - (h0 * b + h1 * Zi[pb]));
+            sd += (s - a) * (s - a) + (s + b) * (s + b);
+            sz += 2.0 * s * s;
+            Z[pa] = s; Zi[pa] = s;
+            Z[pb] = -s; Zi[pb] = -s;
+        }
+        if (i <= j) {   // Z12 and Z21 symmetrised
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk) {
+                const size_t r0 = blk ? n : 0, c0 = blk ? 0 : n;
+                const size_t pa = (r0 + i) + (c0 + j) * L, pb = (r0 + j) + (c0 + i) * L;
+                const double a = Z[pa], b = Z[pb];
+                const double s = 0.5 * ((h0 * a + h1 * Zi[pa]) + (h0 * b + h1 * Zi[pb]));
+                if (i < j) {
+                    sd += (s - a) * (s - a) + (s - b) * (s - b);
+                    sz += 2.0 * s * s;
+                } else {
+                    sd += (s - a) * (s - a);
+                    sz += s * s;
+                }
+                Z[pa] = s; Zi[pa] = s;
+                Z[pb] = s; Zi[pb] = s;
+            }
+        }
+    }
+    sd = block_sum(sd, red);
+    sz = block_sum(sz, red);
+    if (threadIdx.x == 0) { part[blockIdx.x] = sd; part[gridDim.x + blockIdx.x] = sz; }
+}
+
+// the stopping norm and the decision of the sign iteration (tests/_hamiltonian_sign_model.py: sign_iteration)
+__global__ __launch_bounds__(256) void k_are_decide(int nparts, const double* __restrict__ part, double tol, const SignCtl* ictl, AreCtl* c) {
+    __shared__ double red[17];
+    double sd = 0.0, sz = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += blockDim.x) { sd += part[i]; sz += part[nparts + i]; }
+    sd = block_sum(sd, red);
+    sz = block_sum(sz, red);
+    if (threadIdx.x != 0) return;
+    if (ictl->singular) { c->done = 4; return; }
+    const double d = sqrt(sd / sz);
+    c->step = d;
+    if (!isfinite(d)) { c->done = 3; return; }
+    if (d <= tol) { c->done = 1; return; }
+    if (d < c->best) {
+        c->best = d; c->since = 0;
+    } else if (!c->scale && ++c->since >= ARE_STAG_WINDOW) {     // (the scaled phase is not monotone: its first steps often grow)
+        c->done = 2; return;
+    }
+    if (d < ARE_SCALE_OFF) c->scale = 0;
+}
+
+// extraction operands: M = [Z12; Z22 + E'] into Zi(:, 0:n), rhs = -[Z11 + E; Z21] into Zi(:, n:2n)  (ld 2n; E ld n)
+__global__ __launch_bounds__(256) void k_are_extract_ops(int n, const double* __restrict__ Z, const double* __restrict__ E, double* __restrict__ Zi) {
+    const size_t L = 2 * (size_t)n, tot = (size_t)n * n;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = idx % n, j = idx / n;
+        const double e = E[idx], et = E[j + i * n];
+        Zi[i + j * L] = Z[i + (n + j) * L];                                  // Z12
+        Zi[(n + i) + j * L] = Z[(n + i) + (n + j) * L] + et;                 // Z22 + E'
+        Zi[i + (n + j) * L] = -(Z[i + j * L] + e);                           // -(Z11 + E)
+        Zi[(n + i) + (n + j) * L] = -Z[(n + i) + j * L];                     // -Z21
+    }
+}
+
+// out = (S + S')/2 (S n x n with ld lds, out ld n, no aliasing)
+__global__ __launch_bounds__(256) void k_are_sym(int n, const double* __restrict__ S, int lds, double* __restrict__ out) {
+    const size_t tot = (size_t)n * n;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = idx % n, j = idx / n;
+        out[idx] = 0.5 * (S[i + j * (size_t)lds] + S[j + i * (size_t)lds]);
+    }
+}
+
+// out = a0 M0 + a1 M1 (n x n, ld n; out may alias M0 or M1: element-wise)
+__global__ __launch_bounds__(256) void k_are_axpby(int n, double a0, const double* M0, double a1, const double* M1, double* out) {
+    const size_t tot = (size_t)n * n;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) out[idx] = a0 * M0[idx] + a1 * M1[idx];
+}
+
+// Res = sym(Q) + AXE + AXE' - sym(XGX) and the partial sums of ||Res||^2, ||Q||^2, ||AXE||^2, ||XGX||^2 (all n x n, ld n)
+__global__ __launch_bounds__(256) void k_are_residual(int n, const double* __restrict__ Q, const double* __restrict__ AXE, const double* __restrict__ XGX,
+                                                      double* __restrict__ Res, double* __restrict__ part) {
+    __shared__ double red[17];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    const size_t tot = (size_t)n * n;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = idx % n, j = idx / n, t = j + i * n;
+        const double v = 0.5 * (Q[idx] + Q[t]) + (AXE[idx] + AXE[t]) - 0.5 * (XGX[idx] + XGX[t]);     // (exactly symmetric)
+        Res[idx] = v;
+        s0 += v * v; s1 += Q[idx] * Q[idx]; s2 += AXE[idx] * AXE[idx]; s3 += XGX[idx] * XGX[idx];
+    }
+    s0 = block_sum(s0, red);
+    s1 = block_sum(s1, red);
+    s2 = block_sum(s2, red);
+    s3 = block_sum(s3, red);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = s0; part[gridDim.x + blockIdx.x] = s1; part[2 * gridDim.x + blockIdx.x] = s2; part[3 * gridDim.x + blockIdx.x] = s3;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_are_residual_finish(int nparts, const double* __restrict__ part, AreCtl* c) {
+    __shared__ double red[17];
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < nparts; i += blockDim.x)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += part[q * nparts + i];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = block_sum(s[q], red);
+    if (threadIdx.x == 0) {
+        const double r = sqrt(s[0]), den = sqrt(s[1]) + 2.0 * sqrt(s[2]) + sqrt(s[3]);
+        c->resnorm = r;
+        c->res = den > 0.0 ? r / den : r;
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// G = B Rinv B' (Rinv null: B B'), n x n
+void form_gram(Ctx* ctx, const Mat& B, const Mat* Rinv, Mat& G) {
+    if (B.cols == 0) { fill_mat(ctx, G, 0.0); return; }
+    if (Rinv) {
+        Mat BR(ctx, B.rows, B.cols);
+        gemm(ctx, false, false, 1.0, B, *Rinv, 0.0, BR, nullptr, "dense_are");
+        gemm(ctx, false, true, 1.0, BR, B, 0.0, G, nullptr, "dense_are");
+    } else {
+        gemm(ctx, false, true, 1.0, B, B, 0.0, G, nullptr, "dense_are");
+    }
+}
+
+void check_operands(const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S) {
+    const int n = E.rows;
+    DRE_REQUIRE(n >= 1 && 2 * n <= DENSE_MAX_N, "dense GARE: E must be square of order 1 .. " + std::to_string(DENSE_MAX_N / 2) +
+                                                    " (the Hamiltonian of order 2n, the device's 32-bit index limit)");
+    DRE_REQUIRE(E.cols == n && A.rows == n && A.cols == n && B.rows == n && Ct.rows == n, "dense GARE: E, A must be n x n, B n x m, Ct n x q");
+    DRE_REQUIRE(E.ld == n && A.ld == n, "dense GARE: E and A must be stored with leading dimension n");
+    DRE_REQUIRE(!Rinv || (Rinv->rows == B.cols && Rinv->cols == B.cols), "dense GARE: Rinv must be m x m");
+    DRE_REQUIRE(!S || (S->rows == Ct.cols && S->cols == Ct.cols), "dense GARE: S must be q x q");
+}
+
+struct Residual {
+    Ctx* c;
+    const Mat &E, &A, &G, &Q;
+    Mat XE, AXE, GXE, XGX, Res;
+    DevArr<double> part;
+    DevArr<AreCtl> ctl;
+    Residual(Ctx* ctx, const Mat& E_, const Mat& A_, const Mat& G_, const Mat& Q_, const DevArr<AreCtl>& ctl_)
+        : c(ctx), E(E_), A(A_), G(G_), Q(Q_), part(ctx, 4 * ARE_PARTS), ctl(ctl_) {
+        const int n = E.rows;
+        XE = Mat(c, n, n); AXE = Mat(c, n, n); GXE = Mat(c, n, n); XGX = Mat(c, n, n); Res = Mat(c, n, n);
+    }
+    // Res = R(X); returns the scaled residual, *fro = ||R(X)||_F (synchronising)
+    double eval(const Mat& X, double* fro = nullptr) {
+        const int n = E.rows;
+        gemm(c, false, false, 1.0, X, E, 0.0, XE, nullptr, "are_residual");        // X E
+        gemm(c, true, false, 1.0, A, XE, 0.0, AXE, nullptr, "are_residual");       // A' X E
+        gemm(c, false, false, 1.0, G, XE, 0.0, GXE, nullptr, "are_residual");      // G X E
+        gemm(c, true, false, 1.0, XE, GXE, 0.0, XGX, nullptr, "are_residual");     // E' X G X E
+        {
+            TimedScope ts(c, "are_residual_sym", 48.0 * n * n, 0.0);
+            hipLaunchKernelGGL(k_are_residual, dim3(ARE_PARTS), dim3(256), 0, c->stream, n, (const double*)Q.p, (const double*)AXE.p, (const double*)XGX.p,
+                               Res.p, part.p);
+            hipLaunchKernelGGL(k_are_residual_finish, dim3(1), dim3(256), 0, c->stream, ARE_PARTS, (const double*)part.p, ctl.p);
+        }
+        AreCtl h;
+        DRE_HIP(hipMemcpyAsync(&h, ctl.p, sizeof(AreCtl), hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        if (fro) *fro = h.resnorm;
+        return h.res;
+    }
+};
+
+}  // namespace
+
+Mat dense_gare_residual(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S, const Mat& X, double* fro) {
+    check_operands(E, A, B, Rinv, Ct, S);
+    const int n = E.rows;
+    DRE_REQUIRE(X.rows == n && X.cols == n && X.ld == n, "dense GARE residual: X must be n x n");
+    require_memory(ctx, 8 * (size_t)n * n);
+    Mat G(ctx, n, n), Q(ctx, n, n);
+    form_gram(ctx, B, Rinv, G);
+    form_gram(ctx, Ct, S, Q);
+    DevArr<AreCtl> ctl(ctx, 1);
+    hipLaunchKernelGGL(k_are_ctl_init, dim3(1), dim3(1), 0, ctx->stream, ctl.p);
+    Residual r(ctx, E, A, G, Q, ctl);
+    r.eval(X, fro);
+    return r.Res;
+}
+
+DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S, int maxiters,
+                                 double tol, int max_refine) {
+    check_operands(E, A, B, Rinv, Ct, S);
+    const int n = E.rows, n2 = 2 * n;
+    DRE_REQUIRE(ctx->dense_gj_panel != 1 || n2 <= GJ_REGISTER_MAX_N, "dense GARE: the register panel (dense_gj_panel = 1) takes 2n <= " +
+                                                                         std::to_string(GJ_REGISTER_MAX_N) + ", 2n = " + std::to_string(n2));
+    DRE_REQUIRE(maxiters >= 1 && maxiters <= 1000, "dense GARE: maxiters must be in 1 .. 1000");
+    DRE_REQUIRE(max_refine >= 0, "dense GARE: max_refine must be >= 0");
+    const double tol2 = tol > 0.0 ? tol : 10.0 * n2 * EPS;
+    // Up-front memory check, before any kernel: Z, Zi (8 n^2), the extraction's QR (V, VT, grouped VT: 6 n^2; R: n^2), E^-1, G, Q, X and the
+    // residual's five n x n work matrices (9 n^2): 24 n^2; with refinement also SignLyap's (maxiters + 10) n^2 and the step's two n x n.
+    const size_t own = 24;
+    std::unique_ptr<SignLyap> lyap;
+    if (max_refine > 0) lyap.reset(new SignLyap(ctx, E, maxiters, tol, max_refine, own + 2));     // (its constructor checks the whole sum)
+    else require_memory(ctx, own * (size_t)n * n);
+
+    DenseGareResult out;
+    Mat G(ctx, n, n), Q(ctx, n, n), Einv(ctx, n, n);
+    form_gram(ctx, B, Rinv, G);
+    form_gram(ctx, Ct, S, Q);
+    DevArr<int> piv(ctx, n2);
+    DevArr<SignCtl> ictl(ctx, 1);
+    DevArr<AreCtl> actl(ctx, 1);
+    DevArr<double> part(ctx, 2 * ARE_PARTS);
+    DRE_HIP(hipMemsetAsync(ictl.p, 0, sizeof(SignCtl), ctx->stream));
+    hipLaunchKernelGGL(k_are_ctl_init, dim3(1), dim3(1), 0, ctx->stream, actl.p);
+    auto read_ictl = [&] {
+        SignCtl h;
+        DRE_HIP(hipMemcpyAsync(&h, ictl.p, sizeof(SignCtl), hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        return h;
+    };
+    // E^-1 and log|det K| = 2 log|det E|
+    copy_mat(ctx, E, Einv);
+    gj_invert(ctx, Einv, piv.p, ictl.p);
+    const SignCtl he = read_ictl();
+    if (he.singular) throw Error(ERR_SINGULAR, "dense GARE: E is singular (zero pivot in the Gauss-Jordan inversion)");
+    const double logdetK = 2.0 * he.logdet;
+
+    // ---- sign iteration on the Hamiltonian pencil ----
+    Mat Z(ctx, n2, n2), Zi(ctx, n2, n2), T(ctx, n, n);
+    {
+        TimedScope ts(ctx, "are_assemble", 8.0 * 12 * n * n, 0.0);
+        hipLaunchKernelGGL(k_are_assemble, dim3(grid_for((size_t)n * n)), dim3(256), 0, ctx->stream, n, (const double*)A.p, (const double*)G.p,
+                           (const double*)Q.p, Z.p, Zi.p);
+    }
+    AreCtl h{};
+    bool converged = false;
+    for (int k = 0; k < maxiters && !converged; ++k) {
+        gj_invert(ctx, Zi, piv.p, ictl.p);
+        // Zi <- K Zi K block by block: W_ab <- K_a W_ab K_b with K_0 = E, K_1 = E'
+        for (int b = 0; b < 2; ++b) {
+            for (int a = 0; a < 2; ++a) {
+                Mat W = Zi.view(a * n, b * n, n, n);
+                gemm(ctx, false, b == 1, 1.0, W, E, 0.0, T, nullptr, "are_kwk");
+                gemm(ctx, a == 1, false, 1.0, E, T, 0.0, W, nullptr, "are_kwk");
+            }
+        }
+        {
+            TimedScope ts(ctx, "are_update", 8.0 * 4 * 4.0 * n * n, 0.0);
+            hipLaunchKernelGGL(k_are_update, dim3(ARE_PARTS), dim3(256), 0, ctx->stream, n, Z.p, Zi.p, (const SignCtl*)ictl.p, (const AreCtl*)actl.p,
+                               logdetK, part.p);
+            hipLaunchKernelGGL(k_are_decide, dim3(1), dim3(256), 0, ctx->stream, ARE_PARTS, (const double*)part.p, tol2, (const SignCtl*)ictl.p, actl.p);
+        }
+        DRE_HIP(hipMemcpyAsync(&h, actl.p, sizeof(AreCtl), hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        out.iters = k + 1;
+        if (h.done == 1) converged = true;
+        else if (h.done == 2)
+            throw Error(ERR_NOT_STABLE, "dense GARE: the sign iteration stagnated at a relative step " + std::to_string(h.step) +
+                                            " (Hamiltonian eigenvalues on or near the imaginary axis: not stabilizable or not detectable?)");
+        else if (h.done == 3) throw Error(ERR_NOT_STABLE, "dense GARE: the sign iteration produced non-finite values");
+        else if (h.done == 4) throw Error(ERR_SINGULAR, "dense GARE: singular Z_" + std::to_string(k) + " in the sign iteration");
+    }
+    if (!converged)
+        throw Error(ERR_NOT_STABLE, "dense GARE: the sign iteration did not converge in " + std::to_string(maxiters) + " iterations (relative step " +
+                                        std::to_string(h.step) + "; Hamiltonian eigenvalues on or near the imaginary axis?)");
+
+    // ---- extraction: [Z12; Z22 + E'] Y = -[Z11 + E; Z21] by Householder QR, X = sym(Y E^-1) ----
+    {
+        TimedScope ts(ctx, "are_extract_ops", 8.0 * 10 * n * n, 0.0);
+        hipLaunchKernelGGL(k_are_extract_ops, dim3(grid_for((size_t)n * n)), dim3(256), 0, ctx->stream, n, (const double*)Z.p, (const double*)E.p, Zi.p);
+    }
+    Mat M = Zi.colsview(0, n), rhs = Zi.colsview(n, n);
+    out.X = Mat(ctx, n, n);
+    {
+        QRFact f = qr_factor(ctx, M);
+        qr_apply_q(ctx, f, rhs, true);                                               // Q' rhs
+        gj_invert(ctx, f.R, piv.p, ictl.p);                                          // R^-1
+        if (read_ictl().singular)
+            throw Error(ERR_SINGULAR, "dense GARE: [Z12; Z22 + E'] is rank deficient (no stable deflating subspace of dimension n)");
+        const Mat top = rhs.view(0, 0, n, n);
+        gemm(ctx, false, false, 1.0, f.R, top, 0.0, T, nullptr, "are_extract");      // Y = R^-1 (Q' rhs)(0:n, :)
+        Mat YEi = Z.view(0, 0, n, n);
+        gemm(ctx, false, false, 1.0, T, Einv, 0.0, YEi, nullptr, "are_extract");     // Y E^-1
+        TimedScope ts(ctx, "are_sym", 24.0 * n * n, 0.0);
+        hipLaunchKernelGGL(k_are_sym, dim3(grid_for((size_t)n * n)), dim3(256), 0, ctx->stream, n, (const double*)YEi.p, YEi.ld, out.X.p);
+    }
+    Z = Mat(); Zi = Mat(); M = Mat(); rhs = Mat();      // (back to the pool for the refinement)
+
+    // ---- Newton-Kleinman refinement ----
+    Residual res(ctx, E, A, G, Q, actl);
+    out.res0 = out.res = res.eval(out.X);
+    const double target = 100.0 * n * EPS;
+    auto axpby = [&](Mat& o, double a0, const Mat& M0, double a1, const Mat& M1) {
+        TimedScope ts(ctx, "are_axpby", 24.0 * n * n, 0.0);
+        hipLaunchKernelGGL(k_are_axpby, dim3(grid_for((size_t)n * n)), dim3(256), 0, ctx->stream, n, a0, (const double*)M0.p, a1, (const double*)M1.p, o.p);
+    };
+    if (lyap && out.res > target) {
+        Mat F(ctx, n, n), D(ctx, n, n), Xn(ctx, n, n);
+        while (out.res > target && out.refinements < max_refine) {
+            axpby(F, 1.0, A, -1.0, res.GXE);                                         // F = A - G X E
+            lyap->factor(F);                                                         // NOT_STABLE: X is not the stabilizing solution
+            lyap->solve(res.Res, D);                                                 // F'DE + E'DF = -R(X)
+            axpby(Xn, 1.0, out.X, 1.0, D);
+            const double rn = res.eval(Xn);
+            ++out.refinements;
+            if (!(rn < out.res)) break;                                              // stopped decreasing: keep the better iterate
+            std::swap(out.X, Xn);
+            out.res = rn;
+        }
+    }
+    ctx->sync();
+    return out;
+}
+
+}  // namespace dre

@@ -539,7 +539,7 @@ static void comb(Ctx* ctx, Mat& out, double a0, const Mat& M0, double a1 = 0.0, 
 // ---- SignLyap --------------------------------------------------------------------------------------------------------------------
 static Mat square(Ctx* ctx, int n) { return Mat(ctx, n, n); }
 
-static void require_memory(Ctx* ctx, size_t doubles) {
+void require_memory(Ctx* ctx, size_t doubles) {
     size_t fr = 0, total = 0;
     DRE_HIP(hipMemGetInfo(&fr, &total));
     const size_t need = doubles * sizeof(double);

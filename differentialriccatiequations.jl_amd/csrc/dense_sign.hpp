@@ -32,6 +32,9 @@ struct SignCtl {
 // (the tournament panel's width is 32).  No synchronisation.
 void gj_invert(Ctx* ctx, Mat& A, int* piv_dev, SignCtl* ctl_dev);
 
+// DRE_ERR_ALLOC unless `doubles` doubles fit in the free device memory plus the pool's released buffers (no allocation, no kernel)
+void require_memory(Ctx* ctx, size_t doubles);
+
 struct SignStats { long iters = 0, refinements = 0; double res0 = 0.0, res = 0.0; };
 
 // One pencil E (fixed) with a stage matrix F: the sign iteration keeps its (P_k, c_k) sequence so that further right-hand sides

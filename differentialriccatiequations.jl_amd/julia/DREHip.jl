@@ -536,6 +536,42 @@ function CommonSolve.solve(prob::GALEProblem, alg::MatrixSign; ctx::Context=defa
     download(ctx, X[])
 end
 
+"""Dense GARE: Q + A'XE + E'XA - E'XGXE = 0 with G = β B R⁻¹ Bᵀ, Q = γ Cᵀ S C (riccati/types.jl:41-52), all dense.  `solve(prob, MatrixSign())`
+returns the stabilizing X from the sign function of the Hamiltonian pencil plus Newton-Kleinman refinement (DREError(-7) when the
+Hamiltonian has eigenvalues on or near the imaginary axis)."""
+Base.@kwdef struct DenseGAREProblem; E; A; B; Rinv = nothing; Ct; S = nothing; beta::Float64 = 1.0; gamma::Float64 = 1.0; end
+
+function gare_operands(ctx::Context, prob::DenseGAREProblem)
+    m, q = size(prob.B, 2), size(prob.Ct, 2)
+    Rinv = prob.Rinv === nothing && prob.beta == 1 ? nothing : prob.beta * (prob.Rinv === nothing ? Matrix(1.0I, m, m) : Matrix{Float64}(prob.Rinv))
+    S = prob.S === nothing && prob.gamma == 1 ? nothing : prob.gamma * (prob.S === nothing ? Matrix(1.0I, q, q) : Matrix{Float64}(prob.S))
+    ops = Any[upload(ctx, Matrix{Float64}(M)) for M in (prob.E, prob.A, prob.B, prob.Ct)]
+    push!(ops, Rinv === nothing ? nothing : upload(ctx, Rinv), S === nothing ? nothing : upload(ctx, S))
+    ops, (o -> o === nothing ? C_NULL : o.ptr)
+end
+
+"solve(GAREProblem, MatrixSign()): dense stabilizing X (X, info) — no reference counterpart (riccati/newton.jl solves the low-rank case)"
+function CommonSolve.solve(prob::DenseGAREProblem, alg::MatrixSign; ctx::Context=default_context())
+    ops, p = gare_operands(ctx, prob)
+    X = Ref{Ptr{Cvoid}}(C_NULL)
+    ii, dd = zeros(Int64, 2), zeros(2)
+    chk(ctx, ccall((:dre_dense_gare_solve, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Float64}),
+                   ctx.ptr, p(ops[1]), p(ops[2]), p(ops[3]), p(ops[5]), p(ops[4]), p(ops[6]), alg.maxiters, alg.tol, alg.max_refine, X, ii, dd))
+    download(ctx, X[]), (iters = ii[1], refinements = ii[2], res0 = dd[1], res = dd[2])
+end
+
+"residual(::DenseGAREProblem, X::Matrix) — riccati/residual.jl:54-66: (Q + A'XE + E'XA - E'XGXE, its Frobenius norm)"
+function residual(prob::DenseGAREProblem, X::AbstractMatrix; ctx::Context=default_context())
+    ops, p = gare_operands(ctx, prob)
+    Xd = upload(ctx, Matrix{Float64}(X))
+    R, nrm = Ref{Ptr{Cvoid}}(C_NULL), Ref{Cdouble}(0.0)
+    chk(ctx, ccall((:dre_dense_gare_residual, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cdouble}),
+                   ctx.ptr, p(ops[1]), p(ops[2]), p(ops[3]), p(ops[5]), p(ops[4]), p(ops[6]), Xd.ptr, R, nrm))
+    download(ctx, R[]), nrm[]
+end
+
 "solve(::GDREProblem{<:Matrix}, Ros1..Ros4(MatrixSign()); dt, save_state, observer)  — src/riccati/dense_ros{1,2,3,4}.jl"
 function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,Ros2,Ros3,Ros4}; dt::Real, save_state::Bool=false, observer=nothing,
                            ctx::Context=default_context())
@@ -575,6 +611,6 @@ function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,
 end
 
 export Context, Pencil, LDLᵀ, lowrank, compress!, compress_fast!, concatenate!, residual, lyapunov_apply, ADI, Shifts, Callbacks, GALEProblem, GDREProblem, DRESolution, Ros1, Ros2,
-       Ros3, Ros4, MatrixSign, LowRankUpdate, lr_update, ADISolver, isdone, solve
+       Ros3, Ros4, MatrixSign, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve
 
 end # module

@@ -99,4 +99,14 @@ end
 CommonSolve.solve(prob::DRE.GALEProblem, alg::HipMatrixSign) =
     DREHip.solve(DREHip.GALEProblem(collect(prob.E), collect(prob.A), prob.C isa DRE.LDLᵀ ? Matrix(prob.C) : Matrix{Float64}(prob.C)), to_hip(alg))
 
+# solve(::GAREProblem, ::HipMatrixSign): the dense stabilizing solution (no reference counterpart; riccati/types.jl:41-52 for the problem).
+# G = β B R⁻¹ Bᵀ and Q = γ Cᵀ S C are the problem's own LDLᵀ objects (riccati/types.jl:47-50: single-term lowrank(B, R⁻¹), lowrank(C', S)).
+function CommonSolve.solve(prob::DRE.GAREProblem, alg::HipMatrixSign)
+    (β, B, Rinv), (γ, Ct, S) = only(zip(prob.G.alphas, prob.G.Ls, prob.G.Ds)), only(zip(prob.Q.alphas, prob.Q.Ls, prob.Q.Ds))
+    hp = DREHip.DenseGAREProblem(E = collect(prob.E), A = collect(prob.A), B = Matrix{Float64}(B), Rinv = Matrix{Float64}(Rinv), Ct = Matrix{Float64}(Ct),
+                                 S = Matrix{Float64}(S), beta = β, gamma = γ)
+    X, _ = DREHip.solve(hp, to_hip(alg))
+    X
+end
+
 end # module

@@ -33,7 +33,7 @@ extern "C" {
 #define DRE_ERR_SINGULAR (-4)
 #define DRE_ERR_INTERNAL (-5)
 #define DRE_ERR_NODEVICE (-6)
-#define DRE_ERR_NOT_STABLE (-7)   /* dense path: (F, E) is not c-stable, the sign iteration did not reach -E */
+#define DRE_ERR_NOT_STABLE (-7)   /* dense path: (F, E) is not c-stable, the sign iteration did not reach -E; dense GARE: the Hamiltonian has eigenvalues on or near the imaginary axis */
 
 /* hard limits of the engine */
 #define DRE_ADI_MAX_ITERS 100000      /* largest dre_adi_options.maxiters (the device keeps the norm history as a ring that the host empties per chunk) */
@@ -386,6 +386,25 @@ int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, c
  * style with 0-based indices (row j was swapped with row piv[j] >= j); logabsdet (or NULL): log |det A|.  A singular A (an exactly zero or
  * non-finite pivot) is DRE_ERR_SINGULAR and leaves A undefined. */
 int dre_dense_invert(dre_ctx* ctx, dre_dense* A, int32_t* piv, double* logabsdet);
+/* solve(GAREProblem(E, A, G, Q), MatrixSign(maxiters, tol, max_refine)): the dense stabilizing solution X of
+ *     Q + A'XE + E'XA - E'XGXE = 0,   G = B Rinv B',  Q = Ct S Ct'
+ * (riccati/types.jl:41-52, riccati/newton.jl:3-147 for dense data; the reference has no dense GARE solver).  Rinv (m x m) and S (q x q) may be
+ * NULL: identity; the scalars of the LDL' objects are folded into them by the caller.  E, A n x n with 2n <= 46340 (the Hamiltonian is 2n x 2n).
+ * Generalized sign iteration of the Hamiltonian pencil (H, diag(E, E')) with determinantal scaling and Byers' structure averaging; tol <= 0
+ * selects 10 (2n) eps (stop when ||Z_{k+1} - Z_k||_F <= tol ||Z_{k+1}||_F); X from a Householder QR of [Z12; Z22 + E'] and then up to
+ * max_refine Newton-Kleinman steps (each a MatrixSign GALE solve on the closed loop (A - GXE, E)) while the scaled residual
+ * ||R(X)||_F / (||Q||_F + 2 ||A'XE||_F + ||E'XGXE||_F) exceeds 100 n eps and decreases.
+ * Errors: DRE_ERR_NOT_STABLE when the sign iteration stagnates, produces non-finite values or does not converge in maxiters (Hamiltonian
+ * eigenvalues on or near the imaginary axis: (A, B, E) not stabilizable or (A, C, E) not detectable), and when a refinement step finds the
+ * closed loop not c-stable; DRE_ERR_SINGULAR for a singular E, a singular Z_k or a rank-deficient [Z12; Z22 + E'].  Device memory of about
+ * 24 n^2 doubles, plus (maxiters + 12) n^2 when max_refine > 0, is checked up front (DRE_ERR_ALLOC, before any kernel runs).
+ * iinfo: [0] sign iterations [1] refinement steps;  dinfo: [0] scaled residual after extraction [1] final */
+int dre_dense_gare_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                         const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo);
+/* residual(::GAREProblem, X) for a dense X (riccati/residual.jl:54-66): Res = Q + A'XE + E'XA - E'XGXE (symmetrised) as a new n x n matrix,
+ * *norm = ||Res||_F.  G, Q as for dre_dense_gare_solve. */
+int dre_dense_gare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                            const dre_dense* S, const dre_dense* X, dre_dense** Res, double* norm);
 /* stored state i of a dense result as a new n x n matrix (sol.X[i]; index 0 is X0) */
 int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X);
 /* per Lyapunov solve j (info[4] of them): iters[j] sign iterations, refinements[j], residuals[2j], residuals[2j+1] relative residual before /
