@@ -156,6 +156,11 @@ PROTOTYPES = {
     "dre_gdre_result_dense_stats": (C.c_int, [_vp, _pi64, _pi64, _pd]),
     "dre_host_eigvals": (C.c_int, [C.c_int, _pd, _pd, _pd]),
     "dre_host_gen_eigvals": (C.c_int, [C.c_int, _pd, _pd, _pd, _pd]),
+    "dre_sign_create": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, _pvp]),
+    "dre_sign_info": (C.c_int, [_vp, _pi64]),
+    "dre_sign_solve_lr": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_int, C.c_int, _pvp, _pvp, _pi64, _pd]),
+    "dre_sign_solve_dense": (C.c_int, [_vp, _vp, _vp, C.c_int, _pvp, _pi64, _pd]),
+    "dre_sign_free": (C.c_int, [_vp, _vp]),
     "dre_host_svd_left": (C.c_int, [C.c_int, C.c_int, _pd, _pd, _pd]),
 }
 

@@ -13,6 +13,7 @@ import ctypes as C
 import math
 import time
 import warnings
+import weakref
 import dataclasses
 from dataclasses import dataclass, field
 from typing import Any, Optional
@@ -662,6 +663,22 @@ class MatrixSign:
     max_refine: int = 2
 
 
+@dataclass(frozen=True)
+class FactoredSign:
+    """Low-rank GALE algorithm tag: the matrix-sign-function iteration on the densified pencil with the kept (P_k, c_k) sequence applied to the
+    *factor* of the right-hand side (Benner & Quintana-Ortí 1999 §4).  LDLᵀ in, LDLᵀ out, no shifts; needs a c-stable pencil like `MatrixSign`
+    (DREError(-7) otherwise) and (maxiters + 7) n² doubles of device memory.  Distinct from `MatrixSign` on purpose: that tag keeps selecting the
+    dense solvers.
+    tol None: 10 n eps for the sign iteration; rtol None: n eps, the truncation threshold of `compress!` (LDLt.jl:237-245), relative to the
+    largest |eigenvalue|; max_width: the factor is compressed whenever it grows wider (and once at the end); max_refine: corrections by
+    replaying the compressed residual factor while the relative residual exceeds 100 n eps + 10 rtol."""
+    maxiters: int = 50
+    tol: Optional[float] = None
+    rtol: Optional[float] = None
+    max_width: int = 256
+    max_refine: int = 1
+
+
 @dataclass
 class Ros3:
     """DifferentialRiccatiEquations.jl:61 (dense only: X0 must be a matrix, inner_alg MatrixSign())"""
@@ -1034,6 +1051,8 @@ def solve_gdre(prob: GDREProblem, alg, dt, save_state=False, observer=None, ctx=
     (DifferentialRiccatiEquations.jl:78-94, riccati/lowrank_ros1.jl, lowrank_ros2.jl)"""
     dense_order = {Ros1: 1, Ros2: 2, Ros3: 3, Ros4: 4}.get(type(alg))
     if not isinstance(prob.X0, LDLt):
+        if isinstance(getattr(alg, "inner_alg", None), FactoredSign):
+            raise TypeError("FactoredSign() is a low-rank solver: it needs an LDLᵀ X0; a dense X0 (an ndarray) goes with MatrixSign()")
         if dense_order is None or not isinstance(alg.inner_alg, MatrixSign):
             raise TypeError("a dense X0 selects the dense Rosenbrock methods, which run on the device only with the matrix-sign-function solver "
                             "named explicitly, e.g. Ros1(MatrixSign()): it needs a c-stable pencil, unlike the reference's Bartels-Stewart default")
@@ -1046,6 +1065,8 @@ def solve_gdre(prob: GDREProblem, alg, dt, save_state=False, observer=None, ctx=
     if isinstance(alg.inner_alg, MatrixSign):
         raise TypeError("MatrixSign() is a dense solver: it needs a dense X0 (an ndarray), not an LDLᵀ object")
     ctx = ctx or dev.default_context()
+    if isinstance(alg.inner_alg, FactoredSign):
+        return _solve_gdre_factored_sign(prob, alg, order, alg.inner_alg, dt, save_state, observer, ctx, return_stats)
     inner = alg.inner_alg if alg.inner_alg is not None else ADI()
     if _needs_state(observer):
         return _solve_gdre_observed(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats)
@@ -1208,6 +1229,28 @@ def _solve_gdre_observed(prob, alg, order, inner, dt, save_state, observer, ctx,
     (`ADISolver`) whose hooks fire live with (X, residual) handles; feedback, right-hand sides and their compression are the library's
     (`dre_ldlt_feedback`, `compress_`).  Same equations as the device-resident loop (`dre_gdre_solve`), which is what runs when the
     observer does not ask for state."""
+    gales = []
+
+    def step_solver(F):
+        def lyap(rhs, guess):
+            solver = ADISolver(GALEProblem(prob.E, F, rhs), inner, guess, observer, ctx)
+            Xn = solver.solve()
+            info = solver.info
+            gales.append(info)
+            if not info["converged"] and inner.warn_convergence:
+                warnings.warn(f"ADI did not converge: residual={info['res_norm']} abstol={info['abstol']} maxiters={inner.maxiters}")
+            return Xn
+        return lyap
+
+    sol = _rosenbrock_lowrank_loop(prob, alg, order, dt, save_state, observer, step_solver)
+    if return_stats:
+        return sol, dict(adi_iters=sum(g["iters"] for g in gales), factorizations=None, gales=gales)
+    return sol
+
+
+def _rosenbrock_lowrank_loop(prob, alg, order, dt, save_state, observer, step_solver):
+    """Host-driven low-rank Ros1 / Ros2 loop shared by the inner Lyapunov solvers: `step_solver(F)` is called once per time step with the
+    step's operator and returns `lyap(rhs, guess) -> LDLᵀ` for that step's stage solves."""
     E, A, B, Cm = prob.E, prob.A, np.asarray(prob.B, float), np.asarray(prob.C, float)
     q = Cm.shape[0]
     nsteps = int(np.floor((prob.tspan[1] - prob.tspan[0]) / dt + 1e-9))
@@ -1226,16 +1269,6 @@ def _solve_gdre_observed(prob, alg, order, inner, dt, save_state, observer, ctx,
     L, Dm, BtLD, EtL, K = feedback(X)
     Ks = [K]
     _call(observer, "observe_gdre_step", t[0], X, K)
-    gales = []
-
-    def lyap(F, rhs, guess):
-        solver = ADISolver(GALEProblem(E, F, rhs), inner, guess, observer, ctx)
-        Xn = solver.solve()
-        info = solver.info
-        gales.append(info)
-        if not info["converged"] and inner.warn_convergence:
-            warnings.warn(f"ADI did not converge: residual={info['res_norm']} abstol={info['abstol']} maxiters={inner.maxiters}")
-        return Xn
 
     for i in range(1, nsteps + 1):
         tau = t[i - 1] - t[i]
@@ -1246,10 +1279,11 @@ def _solve_gdre_observed(prob, alg, order, inner, dt, save_state, observer, ctx,
             S[:q, :q] = np.eye(q)
             S[q:, q:] = BtLD.T @ BtLD + Dm / tau                                                          # lowrank_ros1.jl:42-43
             rhs = compress_(lowrank(G, S))                                                                # :44
-            X = lyap(F, rhs, X)                                                                           # :47-49 (warm start)
+            X = step_solver(F)(rhs, X)                                                                    # :47-49 (warm start)
         else:
             # lr_update(A, alpha, U, V) = A + inv(alpha) U V (LowRankUpdate.jl:18-39): the reference passes inv(-gamma tau) for the term -gamma tau B K
             F = lr_update(ScaledPencil(A, gamma * tau, E, -0.5), 1.0 / (-gamma * tau), B, K)             # lowrank_ros2.jl:41
+            lyap = step_solver(F)
             r = L.shape[1]
             G = np.hstack([Cm.T, np.asarray(A.T @ L), EtL])
             S = np.zeros((q + 2 * r,) * 2)
@@ -1257,12 +1291,12 @@ def _solve_gdre_observed(prob, alg, order, inner, dt, save_state, observer, ctx,
             S[q:q + r, q + r:] = Dm
             S[q + r:, q:q + r] = Dm
             S[q + r:, q + r:] = -(BtLD.T @ BtLD)                                                          # :44-55
-            K1 = lyap(F, compress_(lowrank(G, S)), None)                                                  # :58
+            K1 = lyap(compress_(lowrank(G, S)), None)                                                     # :58
             a1, T1, D1 = K1
             BtT1D1 = a1 * ((B.T @ T1) @ D1)
             G2 = np.asarray(E.T @ T1)
             S2 = tau * tau * (BtT1D1.T @ BtT1D1) + (2.0 - 1.0 / gamma) * (a1 * D1)                        # :61-66
-            K2 = lyap(F, lowrank(G2, S2), None)                                                           # :69
+            K2 = lyap(lowrank(G2, S2), None)                                                              # :69
             X = X + ((2.0 - 1.0 / (2.0 * gamma)) * tau) * K1 + (-tau / 2.0) * K2                          # :72
         L, Dm, BtLD, EtL, K = feedback(X)
         Ks.append(K)
@@ -1272,9 +1306,132 @@ def _solve_gdre_observed(prob, alg, order, inner, dt, save_state, observer, ctx,
     if not save_state:
         Xs.append(X)
     _call(observer, "observe_gdre_done")
-    sol = DRESolution(Xs, Ks, t)
+    return DRESolution(Xs, Ks, t)
+
+
+# ------------------------------------------------------------------------------------------------
+# Factored sign-function solver (FactoredSign): LDLᵀ in, LDLᵀ out on a densified pencil           csrc/dense_sign_lr.hip
+# in the place of solve(::GALEProblem{LDLᵀ}, ::ADI) (lyapunov/adi.jl) where no shifts can be found
+# ------------------------------------------------------------------------------------------------
+def _dense_operator(A):
+    """A GALE coefficient (matrix, ScaledPencil, or a LowRankUpdate of either) as a dense Fortran-ordered matrix."""
+    if isinstance(A, LowRankUpdate):
+        return np.asfortranarray(_dense_operator(A.A) + (1.0 / A.alpha) * (np.asarray(A.U, float) @ np.asarray(A.V, float)))
+    if isinstance(A, ScaledPencil):
+        return np.asfortranarray(A.cA * _dense_f64(A.A) + A.cE * _dense_f64(A.E))
+    return _dense_f64(A)
+
+
+def _factored_sign_params(alg: FactoredSign, n):
+    rtol = float(alg.rtol) if alg.rtol is not None else n * float(np.finfo(float).eps)
+    return int(alg.maxiters), float(alg.tol) if alg.tol is not None else 0.0, rtol, int(alg.max_width), int(alg.max_refine)
+
+
+class SignFactorization:
+    """A kept sign iteration of one pencil (F, E) on the device (`dre_sign_create`): every further right-hand side costs a replay only.
+    `E` and `F` are dense matrices (or anything `_dense_operator` densifies), or `DenseMatrix` objects already on the device."""
+
+    def __init__(self, E, F, maxiters=50, tol=None, ctx=None):
+        self.ctx = ctx or dev.default_context()
+        Ed = E if isinstance(E, dev.DenseMatrix) else self.ctx.upload(_dense_operator(E))
+        Fd = F if isinstance(F, dev.DenseMatrix) else self.ctx.upload(_dense_operator(F))
+        self.n = Ed.shape[0]
+        p = C.c_void_p()
+        self.ctx.chk(self.ctx.lib.dre_sign_create(self.ctx.ptr, Ed.ptr, Fd.ptr, int(maxiters), float(tol) if tol is not None else 0.0, C.byref(p)))
+        self.ptr = p
+        self._fin = weakref.finalize(self, self.ctx.lib.dre_sign_free, self.ctx.ptr, p)
+        it = C.c_int64()
+        self.ctx.lib.dre_sign_info(p, C.byref(it))
+        self.iters = int(it.value)
+
+    def close(self):
+        self._fin()
+
+    def solve_lr(self, G, S, rtol=None, max_width=256, max_refine=1, download=True):
+        """F'XE + E'XF = -G S G'  ->  (L, D, info) with X = L D L', D diagonal.  G, S: ndarrays or `DenseMatrix` objects on the device;
+        download=False leaves L and D there (`DenseMatrix`)."""
+        rtol = self.n * float(np.finfo(float).eps) if rtol is None else float(rtol)
+        if isinstance(G, dev.DenseMatrix):
+            Gd, Sd = G, S
+        else:
+            G = np.asarray(G, dtype=float).reshape(self.n, -1)
+            r = G.shape[1]
+            Gd, Sd = self.ctx.upload(G), self.ctx.upload(np.asarray(S, dtype=float).reshape(r, r))
+        lp, dp = C.c_void_p(), C.c_void_p()
+        ii, dd = (C.c_int64 * 4)(), (C.c_double * 2)()
+        self.ctx.chk(self.ctx.lib.dre_sign_solve_lr(self.ctx.ptr, self.ptr, Gd.ptr, Sd.ptr, rtol, int(max_width), int(max_refine), C.byref(lp), C.byref(dp), ii, dd))
+        L, Dm = dev.DenseMatrix(self.ctx, lp), dev.DenseMatrix(self.ctx, dp)
+        if download:
+            L, Dm = L.numpy(), Dm.numpy()
+        return L, Dm, dict(iters=self.iters, rank=int(ii[0]), peak_width=int(ii[1]), compressions=int(ii[2]), refinements=int(ii[3]),
+                           res0=float(dd[0]), res=float(dd[1]))
+
+    def solve_dense(self, R, max_refine=2, download=True):
+        """F'XE + E'XF = -R for a dense symmetric R (the `MatrixSign` replay on the kept factorisation) -> (X, info)"""
+        Rd = R if isinstance(R, dev.DenseMatrix) else self.ctx.upload(_dense_f64(R))
+        xp = C.c_void_p()
+        ii, dd = (C.c_int64 * 2)(), (C.c_double * 2)()
+        self.ctx.chk(self.ctx.lib.dre_sign_solve_dense(self.ctx.ptr, self.ptr, Rd.ptr, int(max_refine), C.byref(xp), ii, dd))
+        X = dev.DenseMatrix(self.ctx, xp)
+        return (X.numpy() if download else X), dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1]))
+
+
+def _single_block(Cl: LDLt):
+    """(L, alpha D) of an LDLᵀ object, its components concatenated first"""
+    if len(Cl.alphas) > 1:
+        Cl = concatenate_(LDLt(list(Cl.alphas), list(Cl.Ls), list(Cl.Ds)))
+    return np.asarray(Cl.Ls[0], float), Cl.alphas[0] * np.asarray(Cl.Ds[0], float)
+
+
+def solve_gale_factored_sign(prob: GALEProblem, alg: FactoredSign, ctx=None, return_info=False, _sign=None):
+    """solve(::GALEProblem{LDLᵀ}, ::FactoredSign) -> LDLᵀ: A'XE + E'XA = -C without shifts (in the place of lyapunov/adi.jl:3-147)."""
+    if not isinstance(prob.C, LDLt):
+        raise TypeError("FactoredSign() takes a low-rank right-hand side (an LDLᵀ object); a dense C (an ndarray) goes with MatrixSign()")
+    n = prob.C.n
+    maxiters, tol, rtol, max_width, max_refine = _factored_sign_params(alg, n)
+    sign = _sign if _sign is not None else SignFactorization(prob.E, prob.A, maxiters, tol if tol > 0 else None, ctx)
+    try:
+        if prob.C.rank() == 0:
+            G, S = np.zeros((n, 0)), np.zeros((0, 0))
+        else:
+            G, S = _single_block(prob.C)
+        L, Dm, info = sign.solve_lr(G, S, rtol, max_width, max_refine)
+    finally:
+        if _sign is None:
+            sign.close()
+    X = lowrank(L, Dm)
+    return (X, info) if return_info else X
+
+
+def _solve_gdre_factored_sign(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats):
+    """solve(::GDREProblem{<:LDLᵀ}, ::Ros1/Ros2(FactoredSign()); dt, save_state, observer): the host-driven Rosenbrock loop with one kept sign
+    factorisation per time step and one factored replay per stage.  The observe_gdre_* hooks fire as on the other paths; there are no ADI
+    iterations to report."""
+    Ed = ctx.upload(_dense_f64(prob.E))
+    n = Ed.shape[0]
+    maxiters, tol, rtol, max_width, max_refine = _factored_sign_params(inner, n)
+    solves = []
+    live = []                       # the current step's factorisation: (maxiters + 7) n² doubles, released before the next one is made
+
+    def step_solver(F):
+        while live:
+            live.pop().close()
+        sign = SignFactorization(Ed, F, maxiters, tol if tol > 0 else None, ctx)
+        live.append(sign)
+
+        def lyap(rhs, guess):
+            X, info = solve_gale_factored_sign(GALEProblem(prob.E, F, rhs), inner, ctx, True, _sign=sign)
+            solves.append(info)
+            return X
+        return lyap
+
+    try:
+        sol = _rosenbrock_lowrank_loop(prob, alg, order, dt, save_state, observer, step_solver)
+    finally:
+        while live:
+            live.pop().close()
     if return_stats:
-        return sol, dict(adi_iters=sum(g["iters"] for g in gales), factorizations=None, gales=gales)
+        return sol, dict(lyapunov_solves=len(solves), solves=solves, ranks=[X.rank() for X in sol.X])
     return sol
 
 
@@ -1626,6 +1783,8 @@ def solve(prob, alg, **kw):
     if isinstance(prob, GALEProblem):
         if isinstance(alg, MatrixSign):
             return solve_gale_dense(prob, alg, **kw)
+        if isinstance(alg, FactoredSign):
+            return solve_gale_factored_sign(prob, alg, **kw)
         return solve_gmres(prob, alg, **kw) if isinstance(alg, GMRES) else solve_gale(prob, alg, **kw)
     if isinstance(prob, GAREProblem):
         if isinstance(alg, MatrixSign):

@@ -9,6 +9,7 @@
 #include "comm.hpp"
 #include "dense_are.hpp"
 #include "dense_sign.hpp"
+#include "dense_sign_lr.hpp"
 #include "engine.hpp"
 #include "hostla.hpp"
 #include "profiling.hpp"
@@ -46,6 +47,8 @@ struct dre_gdre_result {
     std::vector<SignStats> solves;
 };
 
+struct dre_sign { std::unique_ptr<SignLyap> s; };
+
 static thread_local std::string g_noctx_error;
 
 template <typename F>
@@ -67,8 +70,8 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 103; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
-                                        // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual)
+int dre_version(void) { return 104; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+                                        // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1143,6 +1146,56 @@ int dre_gdre_result_dense_stats(const dre_gdre_result* r, int64_t* iters, int64_
 }
 
 // ---- host helpers ------------------------------------------------------------------------------
+// ---- factored sign-function Lyapunov solver (dense_sign_lr.hip) -----------------------------------------------------------------------
+int dre_sign_create(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, int maxiters, double tol, dre_sign** out) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && F && out, "dre_sign_create: null argument");
+        const int n = E->m.rows;
+        DRE_REQUIRE(F->m.rows == n && F->m.cols == n, "dre_sign_create: E and F must be n x n");
+        auto h = std::make_unique<dre_sign>();
+        Mat Ec(c, n, E->m.cols);            // the handle outlives the caller's E
+        copy_mat(c, E->m, Ec);
+        h->s = std::make_unique<SignLyap>(c, Ec, maxiters, tol, 0, 0, true);
+        h->s->factor(F->m);
+        *out = h.release();
+    });
+}
+int dre_sign_info(const dre_sign* s, int64_t* n_iters) {
+    if (!s || !n_iters) return DRE_ERR_INVALID;
+    *n_iters = s->s->iters();
+    return DRE_OK;
+}
+int dre_sign_solve_lr(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
+                      dre_dense** L, dre_dense** D, int64_t* ii, double* dd) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(s && G && S && L && D, "dre_sign_solve_lr: null argument");
+        auto Lo = std::make_unique<dre_dense>(), Do = std::make_unique<dre_dense>();
+        const SignLrStats st = s->s->solve_lr(G->m, S->m, rtol, max_width, max_refine, Lo->m, Do->m);
+        c->sync();
+        if (ii) { ii[0] = st.rank; ii[1] = st.peak_width; ii[2] = st.compressions; ii[3] = st.refinements; }
+        if (dd) { dd[0] = st.res0; dd[1] = st.res; }
+        *L = Lo.release(); *D = Do.release();
+    });
+}
+int dre_sign_solve_dense(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(s && R && X && max_refine >= 0, "dre_sign_solve_dense: null argument or negative max_refine");
+        const int n = s->s->n();
+        auto out = std::make_unique<dre_dense>();
+        out->m = Mat(c, n, n);
+        s->s->set_max_refine(max_refine);
+        const SignStats st = s->s->solve(R->m, out->m);
+        c->sync();
+        if (iinfo) { iinfo[0] = st.iters; iinfo[1] = st.refinements; }
+        if (dinfo) { dinfo[0] = st.res0; dinfo[1] = st.res; }
+        *X = out.release();
+    });
+}
+int dre_sign_free(dre_ctx*, dre_sign* s) { delete s; return DRE_OK; }
+
 int dre_host_eigvals(int n, const double* A, double* wr, double* wi) {
     return guarded(nullptr, [&] {
         std::vector<double> M(A, A + (size_t)n * n);

@@ -549,7 +549,7 @@ void require_memory(Ctx* ctx, size_t doubles) {
                                    " MiB available");
 }
 
-SignLyap::SignLyap(Ctx* ctx, const Mat& E, int maxiters, double tol, int max_refine, size_t extra_n2)
+SignLyap::SignLyap(Ctx* ctx, const Mat& E, int maxiters, double tol, int max_refine, size_t extra_n2, bool lazy_dense)
     : c_(ctx), n_(E.rows), maxiters_(maxiters), max_refine_(max_refine), tol_(tol) {
     const int n = n_;
     DRE_REQUIRE(E.cols == n && n >= 1 && n <= DENSE_MAX_N, "dense path: E must be square of order 1 .. " + std::to_string(DENSE_MAX_N) +
@@ -560,11 +560,11 @@ SignLyap::SignLyap(Ctx* ctx, const Mat& E, int maxiters, double tol, int max_ref
     DRE_REQUIRE(maxiters >= 1 && maxiters <= 1000, "dense path: maxiters must be in 1 .. 1000");
     DRE_REQUIRE(max_refine >= 0, "dense path: max_refine must be >= 0");
     if (!(tol_ > 0.0)) tol_ = 10.0 * n * 2.220446049250313e-16;
-    require_memory(ctx, ((size_t)maxiters + 10 + extra_n2) * n * n);
+    require_memory(ctx, ((size_t)maxiters + (lazy_dense ? 7 : 10) + extra_n2) * n * n);
     Pstore_ = Mat(ctx, n, n * maxiters);
     E_ = E;
-    Einv_ = square(ctx, n); F_ = square(ctx, n); Z_ = square(ctx, n); Zi_ = square(ctx, n); Y_ = square(ctx, n); W_ = square(ctx, n);
-    T_ = square(ctx, n); Res_ = square(ctx, n);
+    Einv_ = square(ctx, n); F_ = square(ctx, n); Z_ = square(ctx, n); Zi_ = square(ctx, n); Y_ = square(ctx, n);
+    if (!lazy_dense) { W_ = square(ctx, n); T_ = square(ctx, n); Res_ = square(ctx, n); }
     piv_ = DevArr<int>(ctx, n);
     ctl_ = DevArr<SignCtl>(ctx, 1);
     part_ = DevArr<double>(ctx, 3 * SIGN_PARTS);
@@ -578,6 +578,12 @@ SignLyap::SignLyap(Ctx* ctx, const Mat& E, int maxiters, double tol, int max_ref
     read_ctl(&h);
     if (h.singular) throw Error(ERR_SINGULAR, "dense path: E is singular (zero pivot in the Gauss-Jordan inversion)");
     logdetE_ = h.logdet;
+}
+
+void SignLyap::ensure_dense_work() {
+    if (W_.p) return;
+    require_memory(c_, (size_t)3 * n_ * n_);
+    W_ = square(c_, n_); T_ = square(c_, n_); Res_ = square(c_, n_);
 }
 
 void SignLyap::read_ctl(SignCtl* h) {
@@ -654,6 +660,7 @@ SignStats SignLyap::solve(const Mat& R, Mat& X) {
     const int n = n_;
     DRE_REQUIRE(R.rows == n && R.cols == n && R.ld == n && X.rows == n && X.cols == n && X.ld == n, "dense path: R and X must be n x n");
     DRE_REQUIRE(iters_ > 0, "dense path: factor() first");
+    ensure_dense_work();
     frob2_device(c_, R, nrm_.p + 1);
     SignStats s;
     s.iters = iters_;

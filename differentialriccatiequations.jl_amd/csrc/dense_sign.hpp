@@ -36,19 +36,28 @@ void gj_invert(Ctx* ctx, Mat& A, int* piv_dev, SignCtl* ctl_dev);
 void require_memory(Ctx* ctx, size_t doubles);
 
 struct SignStats { long iters = 0, refinements = 0; double res0 = 0.0, res = 0.0; };
+struct SignLrStats;      // dense_sign_lr.hpp
 
 // One pencil E (fixed) with a stage matrix F: the sign iteration keeps its (P_k, c_k) sequence so that further right-hand sides
 // on the same pencil cost only the W recursion (replay).
 class SignLyap {
   public:
-    SignLyap(Ctx* ctx, const Mat& E, int maxiters, double tol, int max_refine, size_t extra_n2 = 0);
+    // lazy_dense: the n x n work matrices W, T, Res of solve() are allocated by the first solve() instead of here (a solver that is only used
+    // through solve_lr never needs them)
+    SignLyap(Ctx* ctx, const Mat& E, int maxiters, double tol, int max_refine, size_t extra_n2 = 0, bool lazy_dense = false);
     // sign iteration on (F, E): throws Error(ERR_NOT_STABLE) / Error(ERR_SINGULAR)
     void factor(const Mat& F);
     // F'XE + E'XF = -R (R symmetric) with the kept sequence, refined by replay; X is n x n
     SignStats solve(const Mat& R, Mat& X);
     int iters() const { return iters_; }
+    int n() const { return n_; }
+    void set_max_refine(int max_refine) { max_refine_ = max_refine; }      // refinement steps of the following solve() calls
+    // Factored replay (dense_sign_lr.hip): F'XE + E'XF = -G S G' (G n x r, S r x r symmetric, indefinite allowed) with the kept sequence applied
+    // to the factor; X = L D L' with D diagonal (r = 0: L is n x 0).  Throws Error(ERR_INVALID) on rtol outside (0, 1) or max_width < max(r, 1).
+    SignLrStats solve_lr(const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D);
 
   private:
+    void ensure_dense_work();
     void replay(const Mat& R, Mat& X);
     double residual(const Mat& R, const Mat& X);
     void read_ctl(SignCtl* h);

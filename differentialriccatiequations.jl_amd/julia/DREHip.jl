@@ -536,6 +536,70 @@ function CommonSolve.solve(prob::GALEProblem, alg::MatrixSign; ctx::Context=defa
     download(ctx, X[])
 end
 
+# ---- factored sign-function solver: solve(::GALEProblem{LDLᵀ}, FactoredSign()) -> LDLᵀ (in the place of lyapunov/adi.jl where no shifts are at hand) ----
+"Low-rank GALE algorithm tag: the sign iteration on the densified pencil with its kept sequence applied to the factor of the right-hand side; LDLᵀ in, LDLᵀ out, no shifts (c-stable pencils only; DREError(-7) otherwise).  tol = 0: 10 n eps; rtol = 0: n eps (compress!, LDLt.jl:237-245)."
+Base.@kwdef struct FactoredSign; maxiters::Int = 50; tol::Float64 = 0.0; rtol::Float64 = 0.0; max_width::Int = 256; max_refine::Int = 1; end
+
+dense_operator(A::LowRankUpdate) = Matrix{Float64}(A.A) + inv(A.α) * (A.U * A.V)
+dense_operator(A) = Matrix{Float64}(A)
+
+"A kept sign factorisation of one pencil (F, E) on the device (dre_sign_create): further right-hand sides cost a replay only (the two stages of Ros2, lowrank_ros2.jl:41-69)"
+mutable struct SignFactorization
+    ctx::Context
+    ptr::Ptr{Cvoid}
+    n::Int
+    iters::Int
+end
+function SignFactorization(ctx::Context, E, F; maxiters::Int=50, tol::Float64=0.0)
+    Ed, Fd = upload(ctx, dense_operator(E)), upload(ctx, dense_operator(F))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ctx, ccall((:dre_sign_create, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Ref{Ptr{Cvoid}}), ctx.ptr, Ed.ptr, Fd.ptr, maxiters, tol, h))
+    it = Ref{Int64}(0)
+    ccall((:dre_sign_info, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), h[], it)
+    s = SignFactorization(ctx, h[], size(E, 1), it[])
+    finalizer(x -> ccall((:dre_sign_free, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ctx.ptr, x.ptr), s)
+end
+
+"F'XE + E'XF = -G S G' on a kept factorisation: (L, D, info) with X = L D L', D diagonal"
+function solve_lr(s::SignFactorization, G::AbstractMatrix, S::AbstractMatrix; rtol::Float64=0.0, max_width::Int=256, max_refine::Int=1)
+    ctx = s.ctx
+    Gd, Sd = upload(ctx, Matrix{Float64}(G)), upload(ctx, Matrix{Float64}(S))
+    L, D = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    ii, dd = zeros(Int64, 4), zeros(2)
+    chk(ctx, ccall((:dre_sign_solve_lr, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Cint, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Float64}),
+                   ctx.ptr, s.ptr, Gd.ptr, Sd.ptr, rtol > 0 ? rtol : s.n * eps(), max_width, max_refine, L, D, ii, dd))
+    download(ctx, L[]), download(ctx, D[]), (iters = s.iters, rank = ii[1], peak_width = ii[2], compressions = ii[3], refinements = ii[4], res0 = dd[1], res = dd[2])
+end
+
+"F'XE + E'XF = -R for a dense symmetric R on a kept factorisation (the MatrixSign replay): (X, info)"
+function solve_dense(s::SignFactorization, R::AbstractMatrix; max_refine::Int=2)
+    ctx = s.ctx
+    Rd = upload(ctx, Matrix{Float64}(R))
+    X = Ref{Ptr{Cvoid}}(C_NULL)
+    ii, dd = zeros(Int64, 2), zeros(2)
+    chk(ctx, ccall((:dre_sign_solve_dense, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Float64}),
+                   ctx.ptr, s.ptr, Rd.ptr, max_refine, X, ii, dd))
+    download(ctx, X[]), (iters = ii[1], refinements = ii[2], res0 = dd[1], res = dd[2])
+end
+
+"solve(GALEProblem(E, A, C::LDLᵀ), FactoredSign()) -> LDLᵀ; A may be a matrix or a LowRankUpdate (densified); a multi-component C is concatenated"
+function CommonSolve.solve(prob::GALEProblem, alg::FactoredSign; ctx::Context=default_context())
+    prob.C isa LDLᵀ || throw(ArgumentError("FactoredSign() takes an LDLᵀ right-hand side; a dense C goes with MatrixSign()"))
+    G = reduce(hcat, prob.C.Ls)
+    S = zeros(size(G, 2), size(G, 2))
+    o = 0
+    for (a, L, D) in zip(prob.C.alphas, prob.C.Ls, prob.C.Ds)
+        k = size(L, 2)
+        S[o+1:o+k, o+1:o+k] = a * D
+        o += k
+    end
+    s = SignFactorization(ctx, prob.E, prob.A; maxiters = alg.maxiters, tol = alg.tol)
+    L, D, _ = solve_lr(s, G, S; rtol = alg.rtol, max_width = alg.max_width, max_refine = alg.max_refine)
+    finalize(s)
+    LDLᵀ([1.0], [L], [D], C_NULL, nothing)
+end
+
 """Dense GARE: Q + A'XE + E'XA - E'XGXE = 0 with G = β B R⁻¹ Bᵀ, Q = γ Cᵀ S C (riccati/types.jl:41-52), all dense.  `solve(prob, MatrixSign())`
 returns the stabilizing X from the sign function of the Hamiltonian pencil plus Newton-Kleinman refinement (DREError(-7) when the
 Hamiltonian has eigenvalues on or near the imaginary axis)."""
@@ -611,6 +675,6 @@ function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,
 end
 
 export Context, Pencil, LDLᵀ, lowrank, compress!, compress_fast!, concatenate!, residual, lyapunov_apply, ADI, Shifts, Callbacks, GALEProblem, GDREProblem, DRESolution, Ros1, Ros2,
-       Ros3, Ros4, MatrixSign, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve
+       Ros3, Ros4, MatrixSign, FactoredSign, SignFactorization, solve_lr, solve_dense, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve
 
 end # module

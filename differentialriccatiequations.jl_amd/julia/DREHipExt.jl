@@ -15,7 +15,7 @@ import CommonSolve
 import DifferentialRiccatiEquations as DRE
 import DREHip
 
-export HipRos1, HipRos2, HipRos3, HipRos4, HipADI, HipMatrixSign
+export HipRos1, HipRos2, HipRos3, HipRos4, HipADI, HipMatrixSign, HipFactoredSign
 
 "Algorithm tags: the reference's inner `ADI` options object is reused unchanged"
 struct HipRos1; inner_alg; end
@@ -30,6 +30,9 @@ HipRos2() = HipRos2(nothing)
 HipRos3() = HipRos3(nothing)
 HipRos4() = HipRos4(nothing)
 to_hip(s::HipMatrixSign) = DREHip.MatrixSign(s.maxiters, s.tol, s.max_refine)
+"Low-rank GALE tag without shifts: the device's factored sign-function solver (LDLᵀ in, LDLᵀ out; c-stable pencils only)"
+Base.@kwdef struct HipFactoredSign; maxiters::Int = 50; tol::Float64 = 0.0; rtol::Float64 = 0.0; max_width::Int = 256; max_refine::Int = 1; end
+to_hip(s::HipFactoredSign) = DREHip.FactoredSign(s.maxiters, s.tol, s.rtol, s.max_width, s.max_refine)
 
 # ---- conversions ------------------------------------------------------------------------------------------------------------------
 function to_hip(X::DRE.LDLᵀ)
@@ -98,6 +101,10 @@ end
 # solve(::GALEProblem, ::HipMatrixSign) in the place of solve(::GALEProblem, ::BartelsStewart) (bartels-stewart.jl:3-12)
 CommonSolve.solve(prob::DRE.GALEProblem, alg::HipMatrixSign) =
     DREHip.solve(DREHip.GALEProblem(collect(prob.E), collect(prob.A), prob.C isa DRE.LDLᵀ ? Matrix(prob.C) : Matrix{Float64}(prob.C)), to_hip(alg))
+
+# solve(::GALEProblem{LDLᵀ}, ::HipFactoredSign) -> LDLᵀ in the place of solve(::GALEProblem{LDLᵀ}, ::ADI) (lyapunov/adi.jl:3-147): no shifts
+CommonSolve.solve(prob::DRE.GALEProblem{<:DRE.LDLᵀ}, alg::HipFactoredSign) =
+    from_hip(DREHip.solve(DREHip.GALEProblem(collect(prob.E), to_hip(prob.A), to_hip(prob.C)), to_hip(alg)))
 
 # solve(::GAREProblem, ::HipMatrixSign): the dense stabilizing solution (no reference counterpart; riccati/types.jl:41-52 for the problem).
 # G = β B R⁻¹ Bᵀ and Q = γ Cᵀ S C are the problem's own LDLᵀ objects (riccati/types.jl:47-50: single-term lowrank(B, R⁻¹), lowrank(C', S)).

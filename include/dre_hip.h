@@ -411,6 +411,31 @@ int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_d
    after refinement; any array may be NULL */
 int dre_gdre_result_dense_stats(const dre_gdre_result* r, int64_t* iters, int64_t* refinements, double* residuals /* 2 per solve */);
 
+/* ---- factored sign-function Lyapunov solver (dense pencil, LDL' right-hand side in, LDL' solution out; no ADI shifts) -----------------
+ * A kept sign factorisation of one pencil (F, E): several right-hand sides share it (the two stages of Ros2, lowrank_ros2.jl:41-69).
+ * Plain dre_dense operands in the caller's row order; no dre_pencil, no dre_ldlt. */
+typedef struct dre_sign dre_sign;
+/* runs the generalized sign iteration on (F, E) and keeps its (P_k, c_k) sequence; replaces the shift selection + factorisations of an ADI
+ * solve (lyapunov/adi.jl:37-72).  maxiters, tol as for dre_dense_gale_solve.  Errors: DRE_ERR_NOT_STABLE (pencil not c-stable), DRE_ERR_SINGULAR,
+ * DRE_ERR_ALLOC when (maxiters + 7) n^2 doubles do not fit (checked before any kernel). */
+int dre_sign_create(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, int maxiters, double tol, dre_sign** out);
+/* *n_iters: sign iterations the factorisation took */
+int dre_sign_info(const dre_sign* s, int64_t* n_iters);
+/* solve(GALEProblem(E, F, C::LDLt), FactoredSign()):  F'XE + E'XF = -G S G'  with G n x r, S r x r symmetric (indefinite allowed);
+ * X = L D L' with *L n x rank and *D rank x rank diagonal (replaces solve(::GALEProblem{LDLt}, ::ADI), lyapunov/adi.jl:3-147).  The kept
+ * sequence is applied to the factor, L_{k+1} = [L_k, P_k'L_k], with a compression (QR, eigenvalues, |lambda| > rtol max|lambda| kept, the
+ * rule of compress!, LDLt.jl:237-245) whenever the width exceeds max_width and once at the end; up to max_refine corrections by replaying the
+ * compressed residual factor while the relative residual exceeds 100 n eps + 10 rtol.
+ * rtol in (0, 1), max(r, 1) <= max_width <= 4096, max_refine >= 0: DRE_ERR_INVALID otherwise.  r = 0 returns rank 0.  Device memory of
+ * 5 n (2 max_width) + 6 (2 max_width)^2 doubles is checked before any kernel (DRE_ERR_ALLOC).
+ * ii: [0] rank [1] peak width [2] compressions [3] refinements;  dd: [0] relative residual before refinement [1] after.  Either may be NULL. */
+int dre_sign_solve_lr(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
+                      dre_dense** L, dre_dense** D, int64_t* ii, double* dd);
+/* F'XE + E'XF = -R for a dense symmetric R on the kept factorisation (what dre_dense_gale_solve does after its own sign iteration);
+ * iinfo / dinfo as there.  The three n x n work matrices of this replay are allocated by the first call. */
+int dre_sign_solve_dense(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo);
+int dre_sign_free(dre_ctx* ctx, dre_sign* s);
+
 /* ---- host helpers exposed for CPU tests of the Projection shift pipeline ---------------------- */
 int dre_host_eigvals(int n, const double* A, double* wr, double* wi);
 int dre_host_gen_eigvals(int n, const double* A, const double* E, double* wr, double* wi);
