@@ -8,6 +8,7 @@
 
 #include "comm.hpp"
 #include "dense_are.hpp"
+#include "dense_gj.hpp"
 #include "dense_sign.hpp"
 #include "dense_sign_lr.hpp"
 #include "engine.hpp"
@@ -1047,7 +1048,7 @@ int dre_gdre_result_gales_all(const dre_gdre_result* r, int64_t* iinfo, double* 
 }
 int dre_gdre_result_free(dre_gdre_result* r) { delete r; return DRE_OK; }
 
-// ---- dense path (dense_sign.hip) ---------------------------------------------------------------------------------------------------
+// ---- dense path (dense_sign.hip, dense_gj.hip, dense_are.hip) ---------------------------------------------------------------------------------------------------
 int dre_dense_gale_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, const dre_dense* R, int maxiters, double tol, int max_refine,
                          dre_dense** X, int64_t* iinfo, double* dinfo) {
     return guarded(ctx, [&] {
@@ -1087,12 +1088,10 @@ int dre_dense_invert(dre_ctx* ctx, dre_dense* A, int32_t* piv, double* logabsdet
         const int n = A->m.rows;
         DRE_REQUIRE(A->m.cols == n && n >= 1 && n <= DENSE_MAX_N, "dre_dense_invert: square matrix of order 1 .. " + std::to_string(DENSE_MAX_N) + " expected");
         DevArr<int> pv(c, n);
-        DevArr<SignCtl> ctl(c, 1);
-        DRE_HIP(hipMemsetAsync(ctl.p, 0, sizeof(SignCtl), c->stream));
+        DevArr<GjCtl> ctl(c, 1);
+        DRE_HIP(hipMemsetAsync(ctl.p, 0, sizeof(GjCtl), c->stream));
         gj_invert(c, A->m, pv.p, ctl.p);
-        SignCtl h;
-        DRE_HIP(hipMemcpyAsync(&h, ctl.p, sizeof(SignCtl), hipMemcpyDeviceToHost, c->stream));
-        c->sync();
+        const GjCtl h = read_back(c, ctl.p);
         if (h.singular) throw Error(ERR_SINGULAR, "dre_dense_invert: singular matrix (exactly zero or non-finite pivot)");
         if (piv) { DRE_HIP(hipMemcpyAsync(piv, pv.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream)); c->sync(); }
         if (logabsdet) *logabsdet = h.logdet;

@@ -193,7 +193,7 @@ struct Ctx {
     // dense-X time loop: warm-started compression of the residual (warm.hip: Rayleigh-Ritz in the previous step's basis, probe verified); 0: the
     // full band reduction at every step
     int dense_warm = 1;
-    // dense path (dense_sign.hip, gj_invert): the pivoting panel of the Gauss-Jordan inversion.  0 auto (the register panel for n <= 4096,
+    // dense path (dense_gj.hip, gj_invert): the pivoting panel of the Gauss-Jordan inversion.  0 auto (the register panel for n <= 4096,
     // the tournament panel above), 1 the register panel only (n > 4096 is DRE_ERR_INVALID), 2 the tournament panel at every n
     int dense_gj_panel = 0;
     // dense-X time loop: the side stream's set-up of step i + 1 is enqueued by a parked host thread at the end of step i (0: inside step i + 1)

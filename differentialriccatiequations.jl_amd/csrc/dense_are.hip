@@ -9,7 +9,6 @@
 #include "dense_are.hpp"
 
 #include <cmath>
-#include <limits>
 #include <memory>
 
 #include "dense.hpp"
@@ -18,10 +17,8 @@
 
 namespace dre {
 
-static constexpr int ARE_PARTS = 256;            // workgroups of the fused element-wise + partial-norm kernels
 static constexpr double ARE_SCALE_OFF = 1e-2;    // tests/_hamiltonian_sign_model.py: SCALE_OFF, STAG_WINDOW
 static constexpr int ARE_STAG_WINDOW = 3;
-static constexpr double EPS = 2.220446049250313e-16;
 
 // Device-side control words of the sign iteration and of the residual (read back once per step by the host).
 struct AreCtl {
@@ -39,8 +36,6 @@ __global__ void k_are_ctl_init(AreCtl* c) {
     c->step = 0.0; c->best = INFINITY; c->res = 0.0; c->resnorm = 0.0;
     c->since = 0; c->scale = 1; c->done = 0; c->pad = 0;
 }
-
-static unsigned grid_for(size_t tot) { return (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (tot + 255) / 256)); }
 
 // Z0 = [[A, -sym(G)], [-sym(Q), -A']] into Z and Zi (ld 2n; A, G, Q ld n)
 __global__ __launch_bounds__(256) void k_are_assemble(int n, const double* __restrict__ A, const double* __restrict__ G, const double* __restrict__ Q,
@@ -61,9 +56,8 @@ __global__ __launch_bounds__(256) void k_are_assemble(int n, const double* __res
 // of ||Z_{k+1} - Z_k||^2 and ||Z_{k+1}||^2 per workgroup.  c = (|det Z_k| / |det K|)^(1/2n) while ctl->scale, else 1.  Thread idx = (i, j) owns
 // the orbits {Z11(i,j), Z22(j,i)} and, for i <= j, {Z12(i,j), Z12(j,i)} and {Z21(i,j), Z21(j,i)}: it reads and writes only its own orbits, so
 // the structured average runs in place.
-__global__ __launch_bounds__(256) void k_are_update(int n, double* __restrict__ Z, double* __restrict__ Zi, const SignCtl* ictl, const AreCtl* actl,
+__global__ __launch_bounds__(256) void k_are_update(int n, double* __restrict__ Z, double* __restrict__ Zi, const GjCtl* ictl, const AreCtl* actl,
                                                     double logdetK, double* __restrict__ part) {
-    __shared__ double red[17];
     if (ictl->singular) return;                     // (uniform: k_are_decide reports it)
     const double c = actl->scale ? exp((ictl->logdet - logdetK) / (2.0 * n)) : 1.0;
     const double h0 = 0.5 / c, h1 = 0.5 * c;
@@ -99,21 +93,16 @@ __global__ __launch_bounds__(256) void k_are_update(int n, double* __restrict__ 
             }
         }
     }
-    sd = block_sum(sd, red);
-    sz = block_sum(sz, red);
-    if (threadIdx.x == 0) { part[blockIdx.x] = sd; part[gridDim.x + blockIdx.x] = sz; }
+    store_partials(part, sd, sz);
 }
 
 // the stopping norm and the decision of the sign iteration (tests/_hamiltonian_sign_model.py: sign_iteration)
-__global__ __launch_bounds__(256) void k_are_decide(int nparts, const double* __restrict__ part, double tol, const SignCtl* ictl, AreCtl* c) {
-    __shared__ double red[17];
-    double sd = 0.0, sz = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) { sd += part[i]; sz += part[nparts + i]; }
-    sd = block_sum(sd, red);
-    sz = block_sum(sz, red);
+__global__ __launch_bounds__(256) void k_are_decide(int nparts, const double* __restrict__ part, double tol, const GjCtl* ictl, AreCtl* c) {
+    double s[2];                                    // ||Z_{k+1} - Z_k||^2, ||Z_{k+1}||^2
+    load_partials(nparts, part, s);
     if (threadIdx.x != 0) return;
     if (ictl->singular) { c->done = 4; return; }
-    const double d = sqrt(sd / sz);
+    const double d = sqrt(s[0] / s[1]);
     c->step = d;
     if (!isfinite(d)) { c->done = 3; return; }
     if (d <= tol) { c->done = 1; return; }
@@ -138,25 +127,9 @@ __global__ __launch_bounds__(256) void k_are_extract_ops(int n, const double* __
     }
 }
 
-// out = (S + S')/2 (S n x n with ld lds, out ld n, no aliasing)
-__global__ __launch_bounds__(256) void k_are_sym(int n, const double* __restrict__ S, int lds, double* __restrict__ out) {
-    const size_t tot = (size_t)n * n;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n;
-        out[idx] = 0.5 * (S[i + j * (size_t)lds] + S[j + i * (size_t)lds]);
-    }
-}
-
-// out = a0 M0 + a1 M1 (n x n, ld n; out may alias M0 or M1: element-wise)
-__global__ __launch_bounds__(256) void k_are_axpby(int n, double a0, const double* M0, double a1, const double* M1, double* out) {
-    const size_t tot = (size_t)n * n;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) out[idx] = a0 * M0[idx] + a1 * M1[idx];
-}
-
 // Res = sym(Q) + AXE + AXE' - sym(XGX) and the partial sums of ||Res||^2, ||Q||^2, ||AXE||^2, ||XGX||^2 (all n x n, ld n)
 __global__ __launch_bounds__(256) void k_are_residual(int n, const double* __restrict__ Q, const double* __restrict__ AXE, const double* __restrict__ XGX,
                                                       double* __restrict__ Res, double* __restrict__ part) {
-    __shared__ double red[17];
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     const size_t tot = (size_t)n * n;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
@@ -165,23 +138,12 @@ __global__ __launch_bounds__(256) void k_are_residual(int n, const double* __res
         Res[idx] = v;
         s0 += v * v; s1 += Q[idx] * Q[idx]; s2 += AXE[idx] * AXE[idx]; s3 += XGX[idx] * XGX[idx];
     }
-    s0 = block_sum(s0, red);
-    s1 = block_sum(s1, red);
-    s2 = block_sum(s2, red);
-    s3 = block_sum(s3, red);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = s0; part[gridDim.x + blockIdx.x] = s1; part[2 * gridDim.x + blockIdx.x] = s2; part[3 * gridDim.x + blockIdx.x] = s3;
-    }
+    store_partials(part, s0, s1, s2, s3);
 }
 
 __global__ __launch_bounds__(256) void k_are_residual_finish(int nparts, const double* __restrict__ part, AreCtl* c) {
-    __shared__ double red[17];
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += part[q * nparts + i];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) s[q] = block_sum(s[q], red);
+    double s[4];
+    load_partials(nparts, part, s);
     if (threadIdx.x == 0) {
         const double r = sqrt(s[0]), den = sqrt(s[1]) + 2.0 * sqrt(s[2]) + sqrt(s[3]);
         c->resnorm = r;
@@ -221,7 +183,7 @@ struct Residual {
     DevArr<double> part;
     DevArr<AreCtl> ctl;
     Residual(Ctx* ctx, const Mat& E_, const Mat& A_, const Mat& G_, const Mat& Q_, const DevArr<AreCtl>& ctl_)
-        : c(ctx), E(E_), A(A_), G(G_), Q(Q_), part(ctx, 4 * ARE_PARTS), ctl(ctl_) {
+        : c(ctx), E(E_), A(A_), G(G_), Q(Q_), part(ctx, 4 * NORM_PARTS), ctl(ctl_) {
         const int n = E.rows;
         XE = Mat(c, n, n); AXE = Mat(c, n, n); GXE = Mat(c, n, n); XGX = Mat(c, n, n); Res = Mat(c, n, n);
     }
@@ -234,13 +196,11 @@ struct Residual {
         gemm(c, true, false, 1.0, XE, GXE, 0.0, XGX, nullptr, "are_residual");     // E' X G X E
         {
             TimedScope ts(c, "are_residual_sym", 48.0 * n * n, 0.0);
-            hipLaunchKernelGGL(k_are_residual, dim3(ARE_PARTS), dim3(256), 0, c->stream, n, (const double*)Q.p, (const double*)AXE.p, (const double*)XGX.p,
+            hipLaunchKernelGGL(k_are_residual, dim3(NORM_PARTS), dim3(256), 0, c->stream, n, (const double*)Q.p, (const double*)AXE.p, (const double*)XGX.p,
                                Res.p, part.p);
-            hipLaunchKernelGGL(k_are_residual_finish, dim3(1), dim3(256), 0, c->stream, ARE_PARTS, (const double*)part.p, ctl.p);
+            hipLaunchKernelGGL(k_are_residual_finish, dim3(1), dim3(256), 0, c->stream, NORM_PARTS, (const double*)part.p, ctl.p);
         }
-        AreCtl h;
-        DRE_HIP(hipMemcpyAsync(&h, ctl.p, sizeof(AreCtl), hipMemcpyDeviceToHost, c->stream));
-        c->sync();
+        const AreCtl h = read_back(c, ctl.p);
         if (fro) *fro = h.resnorm;
         return h.res;
     }
@@ -267,11 +227,10 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
                                  double tol, int max_refine) {
     check_operands(E, A, B, Rinv, Ct, S);
     const int n = E.rows, n2 = 2 * n;
-    DRE_REQUIRE(ctx->dense_gj_panel != 1 || n2 <= GJ_REGISTER_MAX_N, "dense GARE: the register panel (dense_gj_panel = 1) takes 2n <= " +
-                                                                         std::to_string(GJ_REGISTER_MAX_N) + ", 2n = " + std::to_string(n2));
+    gj_check_order(ctx, n2, "dense GARE (the Hamiltonian of order 2n)");
     DRE_REQUIRE(maxiters >= 1 && maxiters <= 1000, "dense GARE: maxiters must be in 1 .. 1000");
     DRE_REQUIRE(max_refine >= 0, "dense GARE: max_refine must be >= 0");
-    const double tol2 = tol > 0.0 ? tol : 10.0 * n2 * EPS;
+    const double tol2 = tol > 0.0 ? tol : 10.0 * n2 * DBL_EPS;
     // Up-front memory check, before any kernel: Z, Zi (8 n^2), the extraction's QR (V, VT, grouped VT: 6 n^2; R: n^2), E^-1, G, Q, X and the
     // residual's five n x n work matrices (9 n^2): 24 n^2; with refinement also SignLyap's (maxiters + 10) n^2 and the step's two n x n.
     const size_t own = 24;
@@ -284,21 +243,15 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
     form_gram(ctx, B, Rinv, G);
     form_gram(ctx, Ct, S, Q);
     DevArr<int> piv(ctx, n2);
-    DevArr<SignCtl> ictl(ctx, 1);
+    DevArr<GjCtl> ictl(ctx, 1);
     DevArr<AreCtl> actl(ctx, 1);
-    DevArr<double> part(ctx, 2 * ARE_PARTS);
-    DRE_HIP(hipMemsetAsync(ictl.p, 0, sizeof(SignCtl), ctx->stream));
+    DevArr<double> part(ctx, 2 * NORM_PARTS);
+    DRE_HIP(hipMemsetAsync(ictl.p, 0, sizeof(GjCtl), ctx->stream));
     hipLaunchKernelGGL(k_are_ctl_init, dim3(1), dim3(1), 0, ctx->stream, actl.p);
-    auto read_ictl = [&] {
-        SignCtl h;
-        DRE_HIP(hipMemcpyAsync(&h, ictl.p, sizeof(SignCtl), hipMemcpyDeviceToHost, ctx->stream));
-        ctx->sync();
-        return h;
-    };
     // E^-1 and log|det K| = 2 log|det E|
     copy_mat(ctx, E, Einv);
     gj_invert(ctx, Einv, piv.p, ictl.p);
-    const SignCtl he = read_ictl();
+    const GjCtl he = read_back(ctx, ictl.p);
     if (he.singular) throw Error(ERR_SINGULAR, "dense GARE: E is singular (zero pivot in the Gauss-Jordan inversion)");
     const double logdetK = 2.0 * he.logdet;
 
@@ -323,12 +276,11 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
         }
         {
             TimedScope ts(ctx, "are_update", 8.0 * 4 * 4.0 * n * n, 0.0);
-            hipLaunchKernelGGL(k_are_update, dim3(ARE_PARTS), dim3(256), 0, ctx->stream, n, Z.p, Zi.p, (const SignCtl*)ictl.p, (const AreCtl*)actl.p,
+            hipLaunchKernelGGL(k_are_update, dim3(NORM_PARTS), dim3(256), 0, ctx->stream, n, Z.p, Zi.p, (const GjCtl*)ictl.p, (const AreCtl*)actl.p,
                                logdetK, part.p);
-            hipLaunchKernelGGL(k_are_decide, dim3(1), dim3(256), 0, ctx->stream, ARE_PARTS, (const double*)part.p, tol2, (const SignCtl*)ictl.p, actl.p);
+            hipLaunchKernelGGL(k_are_decide, dim3(1), dim3(256), 0, ctx->stream, NORM_PARTS, (const double*)part.p, tol2, (const GjCtl*)ictl.p, actl.p);
         }
-        DRE_HIP(hipMemcpyAsync(&h, actl.p, sizeof(AreCtl), hipMemcpyDeviceToHost, ctx->stream));
-        ctx->sync();
+        h = read_back(ctx, actl.p);
         out.iters = k + 1;
         if (h.done == 1) converged = true;
         else if (h.done == 2)
@@ -352,25 +304,21 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
         QRFact f = qr_factor(ctx, M);
         qr_apply_q(ctx, f, rhs, true);                                               // Q' rhs
         gj_invert(ctx, f.R, piv.p, ictl.p);                                          // R^-1
-        if (read_ictl().singular)
+        if (read_back(ctx, ictl.p).singular)
             throw Error(ERR_SINGULAR, "dense GARE: [Z12; Z22 + E'] is rank deficient (no stable deflating subspace of dimension n)");
         const Mat top = rhs.view(0, 0, n, n);
         gemm(ctx, false, false, 1.0, f.R, top, 0.0, T, nullptr, "are_extract");      // Y = R^-1 (Q' rhs)(0:n, :)
         Mat YEi = Z.view(0, 0, n, n);
         gemm(ctx, false, false, 1.0, T, Einv, 0.0, YEi, nullptr, "are_extract");     // Y E^-1
-        TimedScope ts(ctx, "are_sym", 24.0 * n * n, 0.0);
-        hipLaunchKernelGGL(k_are_sym, dim3(grid_for((size_t)n * n)), dim3(256), 0, ctx->stream, n, (const double*)YEi.p, YEi.ld, out.X.p);
+        comb(ctx, out.X, 1.0, YEi, 0.0, nullptr, 0.0, nullptr, true, "are_sym", 3);  // X = sym(Y E^-1), YEi with ld 2n; 3 words: YEi is read twice
     }
     Z = Mat(); Zi = Mat(); M = Mat(); rhs = Mat();      // (back to the pool for the refinement)
 
     // ---- Newton-Kleinman refinement ----
     Residual res(ctx, E, A, G, Q, actl);
     out.res0 = out.res = res.eval(out.X);
-    const double target = 100.0 * n * EPS;
-    auto axpby = [&](Mat& o, double a0, const Mat& M0, double a1, const Mat& M1) {
-        TimedScope ts(ctx, "are_axpby", 24.0 * n * n, 0.0);
-        hipLaunchKernelGGL(k_are_axpby, dim3(grid_for((size_t)n * n)), dim3(256), 0, ctx->stream, n, a0, (const double*)M0.p, a1, (const double*)M1.p, o.p);
-    };
+    const double target = 100.0 * n * DBL_EPS;
+    auto axpby = [&](Mat& o, double a0, const Mat& M0, double a1, const Mat& M1) { comb(ctx, o, a0, M0, a1, &M1, 0.0, nullptr, false, "are_axpby"); };
     if (lyap && out.res > target) {
         Mat F(ctx, n, n), D(ctx, n, n), Xn(ctx, n, n);
         while (out.res > target && out.refinements < max_refine) {

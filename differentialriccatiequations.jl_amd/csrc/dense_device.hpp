@@ -1,5 +1,6 @@
-// Device-side helpers shared by the dense translation units (gemm.hip, dense.hip, qr_band.hip): wave / workgroup sums, the band reductions'
-// termination tolerance, the MFMA accumulator type; and the one kernel of gemm.hip that dense.hip launches itself.
+// Device-side helpers shared by the dense translation units (gemm.hip, dense.hip, qr_band.hip, dense_sign.hip, dense_are.hip): wave / workgroup
+// sums, the two halves of a norm in two launches, the band reductions' termination tolerance, the MFMA accumulator type; and the one kernel of
+// gemm.hip that dense.hip launches itself.
 #pragma once
 #include "dense.hpp"
 
@@ -50,6 +51,34 @@ __device__ inline double block_sum(double v, double* red /* >= 17 doubles */) {
     }
     __syncthreads();
     return red[16];
+}
+
+// Norms in two launches (the fused element-wise + partial-norm kernels of dense_sign.hip and dense_are.hip): every workgroup of the first kernel
+// leaves its share of the Q sums in part[q * gridDim.x + blockIdx.x]; the one workgroup of the second kernel adds the nparts shares of each sum
+// in a fixed order.  On return of load_partials every thread holds the totals.
+template <class... S>
+__device__ inline void store_partials(double* __restrict__ part, S... sums) {
+    __shared__ double red[17];
+    constexpr int Q = sizeof...(S);
+    double s[Q] = {sums...};
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = block_sum(s[q], red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) part[q * gridDim.x + blockIdx.x] = s[q];
+    }
+}
+template <int Q>
+__device__ inline void load_partials(int nparts, const double* __restrict__ part, double (&s)[Q]) {
+    __shared__ double red[17];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] += part[q * nparts + i];
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = block_sum(s[q], red);
 }
 
 // fixed-order sum of split-K slabs (gemm.hip)

@@ -1,39 +1,25 @@
-// Dense path (GDREProblem{<:Matrix}): in-place Gauss-Jordan inversion with partial pivoting, the generalized matrix-sign-function
-// Lyapunov solver built on it, and the dense Rosenbrock drivers Ros1..Ros4 (dense_sign.hip).  See DESIGN.md, "Dense path".
+// Dense path (GDREProblem{<:Matrix}): the generalized matrix-sign-function Lyapunov solver on the Gauss-Jordan inversion of dense_gj.hip, and
+// the dense Rosenbrock drivers Ros1..Ros4 (dense_sign.hip; the factored replay solve_lr: dense_sign_lr.hip).  See DESIGN.md, "Dense path".
 #pragma once
-#include "common.hpp"
+#include "dense_gj.hpp"
 
 namespace dre {
 
 enum : int { ERR_NOT_STABLE = -7 };    // = DRE_ERR_NOT_STABLE of include/dre_hip.h
 
-// Order limits of the dense path.  DENSE_MAX_N is the index limit: every device kernel the dense path launches (dense_sign.hip, the element-wise
-// copies and norms of dense.hip, the GEMM family of gemm.hip) forms element offsets inside an n x n operand either in size_t or as an int
-// row / column index below n, and every int product it forms (row + col * ld of the n x n, n x nb and nb x n operands, the
-// k * n column offset of a stored P_k) stays below 2^31 - 1 while n <= 46340 = floor(sqrt(2^31 - 1)).  Below that limit the device memory
-// decides (require_memory).  GJ_REGISTER_MAX_N is the limit of the register panel, which keeps ceil(n / 512) rows per thread in registers
-// (dense_gj_panel = 1 refuses larger n; the default 0 switches to the tournament panel above it).
-#define DENSE_MAX_N 46340
-#define GJ_REGISTER_MAX_N 4096
-
-// Device-side control words of the inversion and of one sign iteration (read back once per step by the host).
+// Device-side control words of one sign iteration, the inversion's in front (read back once per step by the host).
 struct SignCtl {
-    double logdet;      // log |det| of the last inverted matrix (sum of log |pivot|)
-    int singular;       // the inversion met an exactly zero (or non-finite) pivot column
+    GjCtl gj;           // of the last inverted matrix
     int done;           // sign iteration: 0 running, 1 converged, 2 stagnated away from -E (not c-stable), 3 non-finite
     double dist;        // ||Z_{k+1} + E||_F / ||E||_F
     double step;        // ||Z_{k+1} - Z_k||_F / ||Z_{k+1}||_F
     double res;         // relative residual ||R + F'XE + E'XF||_F / ||R||_F of the last residual evaluation
-    double pad[3];
 };
 
-// A <- inv(A) in place (n x n, n <= DENSE_MAX_N); ctl->logdet = log|det A|, ctl->singular set on a zero pivot; piv[0..n) the row interchanges
-// (LAPACK style: row j was swapped with row piv[j] >= j).  The panel follows ctx->dense_gj_panel (0 auto, 1 register, 2 tournament) and
-// (the tournament panel's width is 32).  No synchronisation.
-void gj_invert(Ctx* ctx, Mat& A, int* piv_dev, SignCtl* ctl_dev);
-
-// DRE_ERR_ALLOC unless `doubles` doubles fit in the free device memory plus the pool's released buffers (no allocation, no kernel)
-void require_memory(Ctx* ctx, size_t doubles);
+// out = sym?(a0 M0 + a1 M1 + a2 M2) for n x n matrices (M1, M2 may be null; M0 with any leading dimension, the others and out with ld n; under
+// sym out must not alias an input).  tag and words: the profiler's class and the 8-byte words it counts per element (0: one per matrix).
+void comb(Ctx* ctx, Mat& out, double a0, const Mat& M0, double a1 = 0.0, const Mat* M1 = nullptr, double a2 = 0.0, const Mat* M2 = nullptr,
+          bool sym = false, const char* tag = "dense_comb", int words = 0);
 
 struct SignStats { long iters = 0, refinements = 0; double res0 = 0.0, res = 0.0; };
 struct SignLrStats;      // dense_sign_lr.hpp
@@ -60,7 +46,6 @@ class SignLyap {
     void ensure_dense_work();
     void replay(const Mat& R, Mat& X);
     double residual(const Mat& R, const Mat& X);
-    void read_ctl(SignCtl* h);
     Ctx* c_;
     int n_, maxiters_, max_refine_, iters_ = 0;
     double tol_, logdetE_ = 0.0;

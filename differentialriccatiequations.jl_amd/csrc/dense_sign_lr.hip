@@ -14,10 +14,8 @@
 
 namespace dre {
 
-static constexpr double LR_EPS = 2.220446049250313e-16;
-
 // Every kernel below indexes matrices of order <= 2 SIGN_LR_MAX_WIDTH + DENSE_MAX_N columns through size_t offsets; the int row / column
-// indices stay below 2^31 by the DENSE_MAX_N argument of dense_sign.hpp.
+// indices stay below 2^31 by the DENSE_MAX_N argument of dense_gj.hpp.
 
 // Out ((wa + wb) x (wa + wb)) = blkdiag(a A, b B); A and B may be the same matrix (the D recursion: both scalings in one pass)
 __global__ __launch_bounds__(256) void k_lr_blkdiag(int wa, const double* __restrict__ A, int lda, double a, int wb, const double* __restrict__ B, int ldb,
@@ -62,12 +60,10 @@ __global__ __launch_bounds__(256) void k_lr_res_t(int r, const double* __restric
 
 namespace {
 
-unsigned lr_grid(size_t tot) { return (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (tot + 255) / 256)); }
-
 void blkdiag(Ctx* c, const Mat& A, double a, const Mat& B, double b, Mat& Out) {
     const int w = A.rows + B.rows;
     TimedScope ts(c, "signlr_small", 16.0 * w * w, 0.0);
-    hipLaunchKernelGGL(k_lr_blkdiag, dim3(lr_grid((size_t)w * w)), dim3(256), 0, c->stream, A.rows, (const double*)A.p, A.ld, a, B.rows,
+    hipLaunchKernelGGL(k_lr_blkdiag, dim3(grid_for((size_t)w * w)), dim3(256), 0, c->stream, A.rows, (const double*)A.p, A.ld, a, B.rows,
                        (const double*)B.p, B.ld, b, Out.p, Out.ld);
 }
 
@@ -79,7 +75,7 @@ Mat diag_mat(Ctx* c, const std::vector<double>& vals, double scale) {
     DevArr<double> dv(c, (size_t)r);
     dv.upload(c, vals);
     TimedScope ts(c, "signlr_small", 8.0 * r * r, 0.0);
-    hipLaunchKernelGGL(k_lr_diag, dim3(lr_grid((size_t)r * r)), dim3(256), 0, c->stream, r, (const double*)dv.p, scale, D.p, D.ld);
+    hipLaunchKernelGGL(k_lr_diag, dim3(grid_for((size_t)r * r)), dim3(256), 0, c->stream, r, (const double*)dv.p, scale, D.p, D.ld);
     c->sync();              // (dv dies with this scope)
     return D;
 }
@@ -123,15 +119,12 @@ struct Compressor {
 
     double norm() {
         frob2_device(c, S, nrm.p);
-        double h = 0.0;
-        DRE_HIP(hipMemcpyAsync(&h, nrm.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        c->sync();
-        return std::sqrt(h);
+        return std::sqrt(read_back(c, nrm.p));
     }
 
     std::vector<double> finish(Mat& dst, double rtol) {
         // the tridiagonalisation may stop early once the remainder is below tolfac eps ||S||_F: keep that below the truncation threshold
-        const double tolfac = std::max(0.25, std::min(4.0, rtol / (8.0 * LR_EPS)));
+        const double tolfac = std::max(0.25, std::min(4.0, rtol / (8.0 * DBL_EPS)));
         SymEig e = sym_eig(c, S, tolfac, true);
         double wmax = 0.0;
         for (double v : e.w) wmax = std::max(wmax, std::fabs(v));
@@ -231,7 +224,7 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
     replay_lr(G, S, LX, DX);
 
     // factored residual [G, F'L, E'L] blkdiag(S, [[0, D], [D, 0]]) [..]': its norm through the small matrix on the QR's basis
-    const double target = 100.0 * n * LR_EPS + 10.0 * rtol;
+    const double target = 100.0 * n * DBL_EPS + 10.0 * rtol;
     Mat Rf, T;
     auto residual = [&]() -> double {
         const int p = LX.cols, w = r + 2 * p;
@@ -246,7 +239,7 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
         T = Mat(c, w, w);
         {
             TimedScope ts(c, "signlr_small", 8.0 * w * w, 0.0);
-            hipLaunchKernelGGL(k_lr_res_t, dim3(lr_grid((size_t)w * w)), dim3(256), 0, c->stream, r, (const double*)S.p, S.ld, p, (const double*)DX.p,
+            hipLaunchKernelGGL(k_lr_res_t, dim3(grid_for((size_t)w * w)), dim3(256), 0, c->stream, r, (const double*)S.p, S.ld, p, (const double*)DX.p,
                                DX.ld, T.p, T.ld);
         }
         comp.form(Rf, T);

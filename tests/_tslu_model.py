@@ -1,4 +1,4 @@
-"""Host NumPy model of the device's tournament-pivoting Gauss-Jordan inversion (csrc/dense_sign.hip: k_gj_tslu, k_gj_swap, k_gj_apply,
+"""Host NumPy model of the device's tournament-pivoting Gauss-Jordan inversion (csrc/dense_gj.hip: k_gj_tslu, k_gj_swap, k_gj_apply,
 k_gj_unpivot, gj_invert_tournament), step for step:
 
   per panel of nb columns J = k .. k+kb-1

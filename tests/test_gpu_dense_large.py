@@ -1,4 +1,4 @@
-"""Dense path beyond n = 4096: the tournament-pivoting Gauss-Jordan panel (csrc/dense_sign.hip, k_gj_tslu) through dre_dense_invert, the
+"""Dense path beyond n = 4096: the tournament-pivoting Gauss-Jordan panel (csrc/dense_gj.hip, k_gj_tslu) through dre_dense_invert, the
 matrix-sign GALE solver and dense Ros1 at SteelProfile(5177) against the committed low-rank fixture (the reference's dense == low-rank
 criterion, test/rail.jl:52-70), the forced tournament panel against the dense fixtures of the register panel, and the option dense_gj_panel."""
 import os
