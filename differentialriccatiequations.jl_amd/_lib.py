@@ -162,6 +162,11 @@ PROTOTYPES = {
     "dre_sign_solve_dense": (C.c_int, [_vp, _vp, _vp, C.c_int, _pvp, _pi64, _pd]),
     "dre_sign_free": (C.c_int, [_vp, _vp]),
     "dre_host_svd_left": (C.c_int, [C.c_int, C.c_int, _pd, _pd, _pd]),
+    "dre_dense_invert_batched": (C.c_int, [_vp, C.c_int, _pvp, _pi32, _pd, _pi32]),
+    "dre_dense_gale_solve_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pvp, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd, _pi32]),
+    "dre_dense_gdre_solve_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pvp, _pvp, _pvp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                C.c_int, C.c_double, C.c_int, _pvp, _pi32]),
+    "dre_batch_member_error": (C.c_char_p, [_vp, C.c_int]),
 }
 
 _lib = None

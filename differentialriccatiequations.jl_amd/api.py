@@ -1223,6 +1223,173 @@ def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_st
     return sol
 
 
+# ------------------------------------------------------------------------------------------------
+# Batched dense path: an ensemble of same-size problems in shared launches                       csrc/dense_batch.hip
+# ------------------------------------------------------------------------------------------------
+def _handle_array(objs):
+    return (C.c_void_p * len(objs))(*[o.ptr for o in objs])
+
+
+def _batch_errors(ctx, status):
+    """DREError per failed member of the last batched call (None for the others)"""
+    errs = []
+    for b, code in enumerate(status):
+        if code == 0:
+            errs.append(None)
+        else:
+            msg = ctx.lib.dre_batch_member_error(ctx.ptr, b)
+            errs.append(DREError(int(code), msg.decode() if msg else f"member {b} failed"))
+    return errs
+
+
+def _check_batch(probs, alg, observer):
+    """The argument errors of solve_batch, raised before any device call: -> ("gale" | "gdre", order)"""
+    if observer is not None:
+        raise TypeError("solve_batch: observers are not supported in the batched call")
+    probs = list(probs)
+    if len(probs) == 0:
+        raise ValueError("solve_batch: empty list of problems")
+    if all(isinstance(p, GALEProblem) for p in probs):
+        if not isinstance(alg, MatrixSign):
+            raise TypeError("solve_batch: a list of GALEProblem is solved with MatrixSign()")
+        kind, order = "gale", 0
+    elif all(isinstance(p, GDREProblem) for p in probs):
+        order = {Ros1: 1, Ros2: 2}.get(type(alg))
+        if order is None or not isinstance(getattr(alg, "inner_alg", None), MatrixSign):
+            raise TypeError("solve_batch: a list of GDREProblem is solved with Ros1(MatrixSign()) or Ros2(MatrixSign()); Ros3 and Ros4 are not batched")
+        if any(isinstance(p.X0, LDLt) for p in probs):
+            raise TypeError("solve_batch: the batched Rosenbrock methods are the dense ones, X0 must be a dense matrix")
+        kind = "gdre"
+    else:
+        raise TypeError("solve_batch: the problems must be all GALEProblem or all GDREProblem")
+
+    def shape(p):
+        n = p.E.shape[0]
+        if kind == "gale":
+            return (n,)
+        return (n, np.asarray(p.B).shape[1] if np.ndim(p.B) == 2 else 1, np.asarray(p.C).shape[0] if np.ndim(p.C) == 2 else 1)
+
+    s0 = shape(probs[0])
+    for b, p in enumerate(probs):
+        if shape(p) != s0:
+            raise ValueError(f"solve_batch: member {b} has (n, m, q) = {shape(p)}, member 0 has {s0}: the members of a batch share n, m and q")
+    if kind == "gdre" and any(tuple(p.tspan) != tuple(probs[0].tspan) for p in probs):
+        raise ValueError("solve_batch: the members of a batch share tspan")
+    return kind, order
+
+
+def solve_batch(probs, alg, *, dt=None, save_state=False, errors="raise", ctx=None, return_stats=False, observer=None):
+    """An ensemble of independent problems of one size side by side on one device (dre_dense_gale_solve_batched /
+    dre_dense_gdre_solve_batched): a list of GALEProblem with MatrixSign(), or of GDREProblem with dense X0 with Ros1(MatrixSign()) /
+    Ros2(MatrixSign()).  Returns the list of results in member order (what `solve` returns for each; with return_stats the pairs
+    (result, stats)).  A member's result depends on that member's data only.  errors="raise": the first failed member's DREError (its message
+    names the member); errors="return": the DREError object in that member's slot (a failed GDRE member's completed steps are in its
+    `partial` attribute)."""
+    if errors not in ("raise", "return"):
+        raise ValueError('solve_batch: errors must be "raise" or "return"')
+    probs = list(probs)
+    kind, order = _check_batch(probs, alg, observer)
+    if kind == "gdre" and dt is None:
+        raise ValueError("solve_batch: dt is required for GDRE problems")
+    ctx = ctx or dev.default_context()
+    nb = len(probs)
+    status = np.zeros(nb, dtype=np.int32)
+    pst = status.ctypes.data_as(C.POINTER(C.c_int32))
+    lib = ctx.lib
+    if kind == "gale":
+        maxiters, tol, max_refine = _sign_params(alg)
+        Es, Fs, Rs = [], [], []
+        for p in probs:
+            Cm = p.C.dense() if isinstance(p.C, LDLt) else p.C
+            Es.append(ctx.upload(_dense_f64(p.E))); Fs.append(ctx.upload(_dense_f64(p.A))); Rs.append(ctx.upload(_dense_f64(Cm)))
+        xs = (C.c_void_p * nb)()
+        ii, dd = np.zeros(2 * nb, dtype=np.int64), np.zeros(2 * nb)
+        ctx.chk(lib.dre_dense_gale_solve_batched(ctx.ptr, nb, _handle_array(Es), _handle_array(Fs), _handle_array(Rs), maxiters, tol, max_refine, xs,
+                                                 ii.ctypes.data_as(C.POINTER(C.c_int64)), dd.ctypes.data_as(C.POINTER(C.c_double)), pst))
+        errs = _batch_errors(ctx, status)
+        out = []
+        for b in range(nb):
+            if errs[b] is not None:
+                out.append(errs[b])
+                continue
+            X = dev.DenseMatrix(ctx, C.c_void_p(xs[b])).numpy()
+            info = dict(iters=int(ii[2 * b]), refinements=int(ii[2 * b + 1]), res0=float(dd[2 * b]), res=float(dd[2 * b + 1]))
+            out.append((X, info) if return_stats else X)
+    else:
+        maxiters, tol, max_refine = _sign_params(alg.inner_alg)
+        ups = [[ctx.upload(_dense_f64(M)) for M in (p.E, p.A, p.B, p.C, p.X0)] for p in probs]
+        rs = (C.c_void_p * nb)()
+        p0 = probs[0]
+        ctx.chk(lib.dre_dense_gdre_solve_batched(ctx.ptr, nb, *[_handle_array([u[j] for u in ups]) for j in range(5)], float(p0.tspan[0]),
+                                                 float(p0.tspan[1]), float(dt), int(order), int(bool(save_state)), maxiters, tol, max_refine, rs, pst))
+        errs = _batch_errors(ctx, status)
+        out = []
+        for b in range(nb):
+            res = _dense_result(ctx, C.c_void_p(rs[b]), probs[b], return_stats)
+            if errs[b] is not None:
+                errs[b].partial = res
+                out.append(errs[b])
+            else:
+                out.append(res)
+    if errors == "raise":
+        for e in out:
+            if isinstance(e, DREError):
+                raise e
+    return out
+
+
+def dense_invert_batch(As, ctx=None):
+    """inv(A_b) for a list of square matrices of one order n <= 4096 in shared launches (dre_dense_invert_batched, the register panel):
+    the list of (Ainv, piv, logabsdet) as `dense_invert` returns them.  A singular member raises DREError(-4) naming it."""
+    As = [_dense_f64(A) for A in As]
+    if len(As) == 0:
+        raise ValueError("dense_invert_batch: empty list of matrices")
+    n = As[0].shape[0]
+    for b, A in enumerate(As):
+        if A.shape != (n, n):
+            raise ValueError(f"dense_invert_batch: member {b} has shape {A.shape}, expected ({n}, {n})")
+    ctx = ctx or dev.default_context()
+    nb = len(As)
+    Ad = [ctx.upload(A) for A in As]
+    piv, ld, status = np.zeros((nb, n), dtype=np.int32), np.zeros(nb), np.zeros(nb, dtype=np.int32)
+    ctx.chk(ctx.lib.dre_dense_invert_batched(ctx.ptr, nb, _handle_array(Ad), piv.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             ld.ctypes.data_as(C.POINTER(C.c_double)), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    for e in _batch_errors(ctx, status):
+        if e is not None:
+            raise e
+    return [(Ad[b].numpy(), piv[b].copy(), float(ld[b])) for b in range(nb)]
+
+
+def _dense_result(ctx, r, prob, return_stats):
+    """a dense dre_gdre_result handle -> DRESolution (or (DRESolution, stats)); frees the handle"""
+    lib = ctx.lib
+    try:
+        ii = (C.c_int64 * 7)()
+        lib.dre_gdre_result_info(r, ii)
+        nt, nx, _, _, nsolve, m, n = list(ii)
+        t = np.zeros(nt)
+        lib.dre_gdre_result_times(r, t.ctypes.data_as(C.POINTER(C.c_double)))
+        Kall = np.zeros((nt, n, m))
+        ctx.chk(lib.dre_gdre_result_K_all(ctx.ptr, r, Kall.ctypes.data_as(C.POINTER(C.c_double))))
+        Ks = [Kall[i].T for i in range(nt)]
+        Xs = [prob.X0]
+        for i in range(1, nx):
+            xp = C.c_void_p()
+            ctx.chk(lib.dre_gdre_result_X_dense(ctx.ptr, r, i, C.byref(xp)))
+            Xs.append(dev.DenseMatrix(ctx, xp).numpy())
+        its, refs = np.zeros(max(nsolve, 1), dtype=np.int64), np.zeros(max(nsolve, 1), dtype=np.int64)
+        res = np.zeros(2 * max(nsolve, 1))
+        lib.dre_gdre_result_dense_stats(r, its.ctypes.data_as(C.POINTER(C.c_int64)), refs.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        res.ctypes.data_as(C.POINTER(C.c_double)))
+    finally:
+        lib.dre_gdre_result_free(r)
+    sol = DRESolution(Xs, Ks, t)
+    if return_stats:
+        solves = [dict(iters=int(its[j]), refinements=int(refs[j]), res0=float(res[2 * j]), res=float(res[2 * j + 1])) for j in range(nsolve)]
+        return sol, dict(lyapunov_solves=nsolve, solves=solves)
+    return sol
+
+
 def _solve_gdre_observed(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats):
     """The Rosenbrock time loop driven from the host for observers that look at the state of every ADI iteration
     (src/riccati/lowrank_ros1.jl:19-63, lowrank_ros2.jl:19-86): every Lyapunov solve is a device-resident stepwise solver

@@ -8,6 +8,7 @@
 
 #include "comm.hpp"
 #include "dense_are.hpp"
+#include "dense_batch.hpp"
 #include "dense_gj.hpp"
 #include "dense_sign.hpp"
 #include "dense_sign_lr.hpp"
@@ -17,7 +18,7 @@
 
 using namespace dre;
 
-struct dre_ctx { Ctx c; std::map<std::string, KernelStat> merged; };
+struct dre_ctx { Ctx c; std::map<std::string, KernelStat> merged; std::vector<std::string> batch_errors; };
 struct dre_dense { Mat m; };
 struct dre_pencil {
     std::unique_ptr<Pencil> p;
@@ -71,8 +72,8 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 104; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
-                                        // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*)
+int dre_version(void) { return 105; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+                                        // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1142,6 +1143,148 @@ int dre_gdre_result_dense_stats(const dre_gdre_result* r, int64_t* iters, int64_
         if (residuals) { residuals[2 * j] = s.res0; residuals[2 * j + 1] = s.res; }
     }
     return DRE_OK;
+}
+
+// ---- batched dense path (dense_batch.hip) ---------------------------------------------------------------------------------------------
+// member handles -> one stack (rows x cols*batch, member b at b * rows * cols)
+static Mat pack_stack(Ctx* c, int batch, const dre_dense* const* h, int rows, int cols) {
+    Mat S(c, rows, cols * batch);
+    for (int b = 0; b < batch; ++b) {
+        Mat v = S.colsview(b * cols, cols);
+        copy_mat(c, h[b]->m, v);
+    }
+    return S;
+}
+static void check_members(int batch, const dre_dense* const* h, int rows, int cols, const char* who, const char* what) {
+    for (int b = 0; b < batch; ++b)
+        DRE_REQUIRE(h[b] && h[b]->m.rows == rows && h[b]->m.cols == cols, std::string(who) + ": " + what + " of member " + std::to_string(b) + " must be " +
+                                                                              std::to_string(rows) + " x " + std::to_string(cols));
+}
+static void check_batch_order(int batch, int n, const char* who) {
+    DRE_REQUIRE(batch >= 1 && batch <= 65535, std::string(who) + ": batch must be in 1 .. 65535");
+    DRE_REQUIRE(n >= 1 && n <= GJ_REGISTER_MAX_N, std::string(who) + ": the batched dense path inverts with the register panel, order 1 .. " +
+                                                      std::to_string(GJ_REGISTER_MAX_N) + " (n = " + std::to_string(n) + ")");
+}
+// per-member outcomes -> status[], the context's per-member messages, dre_last_error = the first failed member's
+static void report_members(dre_ctx* ctx, const std::vector<BatchMemberStatus>& st, int32_t* status) {
+    ctx->batch_errors.assign(st.size(), std::string());
+    bool first = true;
+    for (size_t b = 0; b < st.size(); ++b) {
+        if (status) status[b] = st[b].code;
+        if (!st[b].code) continue;
+        ctx->batch_errors[b] = st[b].msg;
+        if (first) { ctx->c.last_error = st[b].msg; first = false; }
+    }
+}
+const char* dre_batch_member_error(dre_ctx* ctx, int b) {
+    if (!ctx || b < 0 || b >= (int)ctx->batch_errors.size()) return "";
+    return ctx->batch_errors[(size_t)b].c_str();
+}
+int dre_dense_invert_batched(dre_ctx* ctx, int batch, dre_dense* const* A, int32_t* piv, double* logabsdet, int32_t* status) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(A && status && batch >= 1 && A[0], "dre_dense_invert_batched: null argument or batch < 1");
+        const int n = A[0]->m.rows;
+        check_batch_order(batch, n, "dre_dense_invert_batched");
+        check_members(batch, A, n, n, "dre_dense_invert_batched", "A");
+        const int nb = gj_batch_nb(n);
+        require_memory(c, (size_t)batch * ((size_t)n * n + (size_t)2 * n * nb + n));
+        Mat S = pack_stack(c, batch, A, n, n);
+        Mat Pn(c, n, nb * batch), W(c, nb, n * batch);
+        DevArr<int> pv(c, (size_t)n * batch);
+        DevArr<BatchCtl> ctl(c, batch);
+        DRE_HIP(hipMemsetAsync(ctl.p, 0, sizeof(BatchCtl) * batch, c->stream));
+        gj_invert_batched(c, batch, n, S.p, pv.p, ctl.p, BM_GJ, Pn.p, W.p);
+        std::vector<BatchCtl> h((size_t)batch);
+        DRE_HIP(hipMemcpyAsync(h.data(), ctl.p, sizeof(BatchCtl) * batch, hipMemcpyDeviceToHost, c->stream));
+        if (piv) DRE_HIP(hipMemcpyAsync(piv, pv.p, (size_t)n * batch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        std::vector<BatchMemberStatus> st((size_t)batch);
+        for (int b = 0; b < batch; ++b) {
+            if (h[(size_t)b].s.gj.singular) {
+                st[(size_t)b].code = ERR_SINGULAR;
+                st[(size_t)b].msg = "dre_dense_invert_batched, member " + std::to_string(b) + ": singular matrix (exactly zero or non-finite pivot)";
+                continue;
+            }
+            Mat v = S.colsview(b * n, n);
+            copy_mat(c, v, A[b]->m);
+            if (logabsdet) logabsdet[b] = h[(size_t)b].s.gj.logdet;
+        }
+        c->sync();
+        report_members(ctx, st, status);
+    });
+}
+int dre_dense_gale_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* F, const dre_dense* const* R,
+                                 int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo, int32_t* status) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && F && R && X && status && batch >= 1 && E[0], "dre_dense_gale_solve_batched: null argument or batch < 1");
+        const int n = E[0]->m.rows;
+        check_batch_order(batch, n, "dre_dense_gale_solve_batched");
+        check_members(batch, E, n, n, "dre_dense_gale_solve_batched", "E");
+        check_members(batch, F, n, n, "dre_dense_gale_solve_batched", "F");
+        check_members(batch, R, n, n, "dre_dense_gale_solve_batched", "R");
+        DRE_REQUIRE(maxiters >= 1 && maxiters <= 1000, "dense path: maxiters must be in 1 .. 1000");
+        require_memory(c, BatchedSignLyap::doubles_needed(batch, n, maxiters, 4));       // + the stacks of E, F, R and X
+        for (int b = 0; b < batch; ++b) X[b] = nullptr;
+        Mat Es = pack_stack(c, batch, E, n, n), Fs = pack_stack(c, batch, F, n, n), Rs = pack_stack(c, batch, R, n, n);
+        Mat Xs(c, n, n * batch);
+        BatchedSignLyap lyap(c, batch, Es, maxiters, tol, max_refine, 4);
+        lyap.factor(Fs);
+        std::vector<SignStats> stats;
+        lyap.solve(Rs, Xs, stats);
+        for (int b = 0; b < batch; ++b) {
+            if (!lyap.alive(b)) continue;
+            auto* out = new dre_dense();
+            out->m = Mat(c, n, n);
+            Mat v = Xs.colsview(b * n, n);
+            copy_mat(c, v, out->m);
+            X[b] = out;
+            if (iinfo) { iinfo[2 * b] = stats[(size_t)b].iters; iinfo[2 * b + 1] = stats[(size_t)b].refinements; }
+            if (dinfo) { dinfo[2 * b] = stats[(size_t)b].res0; dinfo[2 * b + 1] = stats[(size_t)b].res; }
+        }
+        c->sync();
+        report_members(ctx, lyap.status(), status);
+    });
+}
+int dre_dense_gdre_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                                 const dre_dense* const* C, const dre_dense* const* X0, double t0, double tf, double dt, int order,
+                                 int save_state, int maxiters, double tol, int max_refine, dre_gdre_result** out, int32_t* status) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && A && B && C && X0 && out && status && batch >= 1 && E[0] && B[0] && C[0],
+                    "dre_dense_gdre_solve_batched: null argument or batch < 1");
+        DRE_REQUIRE(order >= 1 && order <= 4, "dense path: order must be 1 .. 4");
+        DRE_REQUIRE(order <= 2, "dre_dense_gdre_solve_batched: only Ros1 and Ros2 (order 1, 2) are batched; order " + std::to_string(order) +
+                                    " runs through dre_dense_gdre_solve");
+        const int n = E[0]->m.rows, m = B[0]->m.cols, q = C[0]->m.rows;
+        check_batch_order(batch, n, "dre_dense_gdre_solve_batched");
+        check_members(batch, E, n, n, "dre_dense_gdre_solve_batched", "E");
+        check_members(batch, A, n, n, "dre_dense_gdre_solve_batched", "A");
+        check_members(batch, B, n, m, "dre_dense_gdre_solve_batched", "B");
+        check_members(batch, C, q, n, "dre_dense_gdre_solve_batched", "C");
+        check_members(batch, X0, n, n, "dre_dense_gdre_solve_batched", "X0");
+        DRE_REQUIRE(dt != 0.0 && std::isfinite(dt), "dense path: dt must be finite and nonzero");
+        DRE_REQUIRE(maxiters >= 1 && maxiters <= 1000, "dense path: maxiters must be in 1 .. 1000");
+        const int nsteps = (int)std::floor((tf - t0) / dt + 1e-9);
+        DRE_REQUIRE(nsteps >= 0, "tspan and dt point in opposite directions");
+        require_memory(c, dense_gdre_batched_doubles(batch, n, m, q, nsteps, order, save_state != 0, maxiters));
+        for (int b = 0; b < batch; ++b) out[b] = nullptr;
+        Mat Es = pack_stack(c, batch, E, n, n), As = pack_stack(c, batch, A, n, n), Bs = pack_stack(c, batch, B, n, m),
+            Cs = pack_stack(c, batch, C, q, n), Xs = pack_stack(c, batch, X0, n, n);
+        std::vector<DenseGdreResult> res;
+        std::vector<BatchMemberStatus> st;
+        dense_gdre_solve_batched(c, batch, Es, As, Bs, Cs, Xs, m, q, t0, tf, dt, order, save_state != 0, maxiters, tol, max_refine, res, st);
+        for (int b = 0; b < batch; ++b) {
+            auto* r = new dre_gdre_result();
+            DenseGdreResult& d = res[(size_t)b];
+            r->dense = true; r->n = n; r->m = m;
+            r->r.t = std::move(d.t); r->r.Kt = std::move(d.Kt);
+            r->Xd = std::move(d.X); r->solves = std::move(d.solves);
+            out[b] = r;
+        }
+        report_members(ctx, st, status);
+    });
 }
 
 // ---- host helpers ------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
 // Dense f64 GEMM family for gfx950 (v_mfma_f64_16x16x4_f64): split-K GEMM, batched and z-batched products, the thin single-launch form.
+#include "dense_batch.hpp"
 #include "dense_device.hpp"
 #include <functional>
 #include "profiling.hpp"
@@ -245,6 +246,33 @@ void gemm_batched(Ctx* ctx, const std::vector<GemmBatchDesc>& descs, const char*
     TimedScope ts(ctx, tag, by, fl);
     hipLaunchKernelGGL(k_gemm_batched, dim3(ceil_div(maxM, GB_M), std::max(1, ceil_div(maxN, GB_N)), (unsigned)descs.size()), dim3(256), 0, ctx->stream,
                        (const GemmBatchDesc*)dd.p);
+    DRE_HIP(hipGetLastError());
+}
+
+// Strided-batched GEMM of the batched dense path (dense_batch.hpp): C_b = alpha op(A_b) op(B_b) + beta C_b with member b = blockIdx.z at
+// base + b * stride of every operand.  One workgroup per 64 x 64 tile over the whole K: no split-K, no atomics, and the tiling of one member
+// does not depend on the batch, so a member's result is the same in every batch.  A member that the mask leaves out returns at once.
+template <bool TA, bool TB>
+__global__ __launch_bounds__(256) void k_gemm_strided(int M, int N, int K, double alpha, const double* __restrict__ A, int lda, size_t sA,
+                                                      const double* __restrict__ B, int ldb, size_t sB, double beta, double* __restrict__ C, int ldc,
+                                                      size_t sC, const double* __restrict__ coef, size_t coef_stride, BatchMask mask) {
+    const int b = blockIdx.z;
+    if (batch_off(mask, b)) return;
+    if (coef) { alpha = coef[(size_t)b * coef_stride]; beta = coef[(size_t)b * coef_stride + 1]; }
+    gemm_tile<TA, TB>(M, N, K, alpha, A + (size_t)b * sA, lda, B + (size_t)b * sB, ldb, beta, C + (size_t)b * sC, ldc, blockIdx.x * GB_M,
+                      blockIdx.y * GB_N, 0, K, nullptr);
+}
+void gemm_strided(Ctx* ctx, int batch, bool tA, bool tB, int M, int N, int K, double alpha, const double* A, int lda, size_t sA, const double* B,
+                  int ldb, size_t sB, double beta, double* C, int ldc, size_t sC, BatchMask mask, const char* tag, const double* coef,
+                  size_t coef_stride) {
+    if (M <= 0 || N <= 0 || batch <= 0) return;
+    DRE_REQUIRE(batch <= 65535 && ceil_div(N, GB_N) <= 65535, "gemm_strided: grid limits (batch, N / 64 <= 65535)");
+    TimedScope ts(ctx, tag, 8.0 * batch * ((double)M * K + (double)K * N + 2.0 * M * N), 2.0 * batch * M * N * (double)K);
+    const dim3 grid(ceil_div(M, GB_M), ceil_div(N, GB_N), batch), block(256);
+    if (!tA && !tB) hipLaunchKernelGGL((k_gemm_strided<false, false>), grid, block, 0, ctx->stream, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, coef, coef_stride, mask);
+    else if (tA && !tB) hipLaunchKernelGGL((k_gemm_strided<true, false>), grid, block, 0, ctx->stream, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, coef, coef_stride, mask);
+    else if (!tA && tB) hipLaunchKernelGGL((k_gemm_strided<false, true>), grid, block, 0, ctx->stream, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, coef, coef_stride, mask);
+    else hipLaunchKernelGGL((k_gemm_strided<true, true>), grid, block, 0, ctx->stream, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, coef, coef_stride, mask);
     DRE_HIP(hipGetLastError());
 }
 

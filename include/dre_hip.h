@@ -411,6 +411,33 @@ int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_d
    after refinement; any array may be NULL */
 int dre_gdre_result_dense_stats(const dre_gdre_result* r, int64_t* iters, int64_t* refinements, double* residuals /* 2 per solve */);
 
+/* ---- batched dense path: `batch` independent problems of one order n <= 4096 (the register panel) side by side on the device ---------
+ * Members come as ordinary dre_dense handles (arrays of `batch` pointers); the library packs them into strided stacks and unpacks the
+ * results.  Every launch carries member b on a grid axis, with per-member control words: a member's result is a function of that member's
+ * data only, bit for bit the same whatever the other members are, however many there are and wherever it sits in the batch (no atomics, no
+ * split-K, per-member grids independent of `batch`).  The return value is DRE_OK whenever the batch was processed; per-member outcomes are in
+ * status[b]: 0, DRE_ERR_SINGULAR or DRE_ERR_NOT_STABLE, dre_last_error names the first failed member and dre_batch_member_error(ctx, b)
+ * gives the message of member b of the context's last batched call.  A failed member is dropped from the following launches; the others go
+ * on.  Argument errors are the call's own DRE_ERR_INVALID (batch < 1, mismatched shapes, n > 4096, order 3 or 4); DRE_ERR_ALLOC comes from
+ * the up-front memory check (batch times the single call's count plus the stacks), before any kernel runs. */
+/* A[b] <- inv(A[b]) in place; piv: batch * n interchanges (or NULL), logabsdet: batch values (or NULL); a singular member: DRE_ERR_SINGULAR
+ * in status[b], its A[b] is left as it came */
+int dre_dense_invert_batched(dre_ctx* ctx, int batch, dre_dense* const* A, int32_t* piv /* batch*n */, double* logabsdet /* batch */,
+                             int32_t* status /* batch */);
+/* dre_dense_gale_solve per member: X[b] is a new n x n matrix (NULL for a failed member); iinfo, dinfo as there, 2 per member */
+int dre_dense_gale_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* F, const dre_dense* const* R,
+                                 int maxiters, double tol, int max_refine, dre_dense** X /* batch */, int64_t* iinfo /* 2*batch */,
+                                 double* dinfo /* 2*batch */, int32_t* status /* batch */);
+/* dre_dense_gdre_solve per member, order 1 or 2 (Ros1, Ros2; orders 3 and 4 are DRE_ERR_INVALID here: they run through the single call).
+ * The members share n, m, q, the time grid, order, save_state and the sign parameters and differ in E, A, B, C and X0.  out[b] is an
+ * ordinary dense dre_gdre_result (all its accessors work unchanged); for a member that failed at step i it holds the steps completed before. */
+int dre_dense_gdre_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                                 const dre_dense* const* C, const dre_dense* const* X0, double t0, double tf, double dt, int order,
+                                 int save_state, int maxiters, double tol, int max_refine, dre_gdre_result** out /* batch */,
+                                 int32_t* status /* batch */);
+/* message of member b of the context's last batched call ("" when it did not fail or b is out of range) */
+const char* dre_batch_member_error(dre_ctx* ctx, int b);
+
 /* ---- factored sign-function Lyapunov solver (dense pencil, LDL' right-hand side in, LDL' solution out; no ADI shifts) -----------------
  * A kept sign factorisation of one pencil (F, E): several right-hand sides share it (the two stages of Ros2, lowrank_ros2.jl:41-69).
  * Plain dre_dense operands in the caller's row order; no dre_pencil, no dre_ldlt. */
