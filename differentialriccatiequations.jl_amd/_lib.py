@@ -166,6 +166,7 @@ PROTOTYPES = {
     "dre_dense_gale_solve_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pvp, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd, _pi32]),
     "dre_dense_gdre_solve_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pvp, _pvp, _pvp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
                                                 C.c_int, C.c_double, C.c_int, _pvp, _pi32]),
+    "dre_dense_gare_solve_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pvp, _pvp, _pvp, _pvp, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd, _pi32]),
     "dre_batch_member_error": (C.c_char_p, [_vp, C.c_int]),
 }
 

@@ -1243,7 +1243,7 @@ def _batch_errors(ctx, status):
 
 
 def _check_batch(probs, alg, observer):
-    """The argument errors of solve_batch, raised before any device call: -> ("gale" | "gdre", order)"""
+    """The argument errors of solve_batch, raised before any device call: -> ("gale" | "gdre" | "gare", order)"""
     if observer is not None:
         raise TypeError("solve_batch: observers are not supported in the batched call")
     probs = list(probs)
@@ -1260,13 +1260,20 @@ def _check_batch(probs, alg, observer):
         if any(isinstance(p.X0, LDLt) for p in probs):
             raise TypeError("solve_batch: the batched Rosenbrock methods are the dense ones, X0 must be a dense matrix")
         kind = "gdre"
+    elif all(isinstance(p, GAREProblem) for p in probs):
+        if not isinstance(alg, MatrixSign):
+            raise TypeError("solve_batch: a list of GAREProblem is solved with MatrixSign()")
+        kind, order = "gare", 0
     else:
-        raise TypeError("solve_batch: the problems must be all GALEProblem or all GDREProblem")
+        raise TypeError("solve_batch: the problems must be all GALEProblem, all GDREProblem or all GAREProblem")
 
     def shape(p):
         n = p.E.shape[0]
         if kind == "gale":
             return (n,)
+        if kind == "gare":
+            (_, Bm, _), (_, Ct, _) = p.G, p.Q
+            return (n, np.shape(Bm)[1] if np.ndim(Bm) == 2 else 1, np.shape(Ct)[1] if np.ndim(Ct) == 2 else 1)
         return (n, np.asarray(p.B).shape[1] if np.ndim(p.B) == 2 else 1, np.asarray(p.C).shape[0] if np.ndim(p.C) == 2 else 1)
 
     s0 = shape(probs[0])
@@ -1280,8 +1287,9 @@ def _check_batch(probs, alg, observer):
 
 def solve_batch(probs, alg, *, dt=None, save_state=False, errors="raise", ctx=None, return_stats=False, observer=None):
     """An ensemble of independent problems of one size side by side on one device (dre_dense_gale_solve_batched /
-    dre_dense_gdre_solve_batched): a list of GALEProblem with MatrixSign(), or of GDREProblem with dense X0 with Ros1(MatrixSign()) /
-    Ros2(MatrixSign()).  Returns the list of results in member order (what `solve` returns for each; with return_stats the pairs
+    dre_dense_gdre_solve_batched / dre_dense_gare_solve_batched): a list of GALEProblem with MatrixSign(), of GDREProblem with dense X0
+    with Ros1(MatrixSign()) / Ros2(MatrixSign()), or of GAREProblem with MatrixSign() (2n <= 4096; with return_stats the info dict of
+    solve_gare_dense: iters, refinements, res0, res, K).  Returns the list of results in member order (what `solve` returns for each; with return_stats the pairs
     (result, stats)).  A member's result depends on that member's data only.  errors="raise": the first failed member's DREError (its message
     names the member); errors="return": the DREError object in that member's slot (a failed GDRE member's completed steps are in its
     `partial` attribute)."""
@@ -1291,6 +1299,8 @@ def solve_batch(probs, alg, *, dt=None, save_state=False, errors="raise", ctx=No
     kind, order = _check_batch(probs, alg, observer)
     if kind == "gdre" and dt is None:
         raise ValueError("solve_batch: dt is required for GDRE problems")
+    if kind == "gare" and (dt is not None or save_state):
+        raise ValueError("solve_batch: dt and save_state belong to GDRE problems, a list of GAREProblem takes neither")
     ctx = ctx or dev.default_context()
     nb = len(probs)
     status = np.zeros(nb, dtype=np.int32)
@@ -1315,6 +1325,31 @@ def solve_batch(probs, alg, *, dt=None, save_state=False, errors="raise", ctx=No
             X = dev.DenseMatrix(ctx, C.c_void_p(xs[b])).numpy()
             info = dict(iters=int(ii[2 * b]), refinements=int(ii[2 * b + 1]), res0=float(dd[2 * b]), res=float(dd[2 * b + 1]))
             out.append((X, info) if return_stats else X)
+    elif kind == "gare":
+        maxiters, tol, max_refine = _sign_params(alg)
+        ops = [_gare_dense_operands(p, ctx) for p in probs]                          # (uploads kept alive, (E, A, B, Rinv, Ct, S) handles)
+        arrs = [(C.c_void_p * nb)(*[o[1][j] for o in ops]) for j in range(6)]
+        xs = (C.c_void_p * nb)()
+        ii, dd = np.zeros(2 * nb, dtype=np.int64), np.zeros(2 * nb)
+        rc = lib.dre_dense_gare_solve_batched(ctx.ptr, nb, *arrs, maxiters, tol, max_refine, xs, ii.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              dd.ctypes.data_as(C.POINTER(C.c_double)), pst)
+        if rc != 0 and not status.any():                                             # the call's own error; a member's code comes with status
+            ctx.chk(rc)
+        del ops
+        errs = _batch_errors(ctx, status)
+        out = []
+        for b, p in enumerate(probs):
+            if errs[b] is not None:
+                out.append(errs[b])
+                continue
+            X = dev.DenseMatrix(ctx, C.c_void_p(xs[b])).numpy()
+            if return_stats:
+                beta, Bm, Rinv = p.G
+                E = p.E.toarray() if sp.issparse(p.E) else np.asarray(p.E, dtype=float)
+                K = (beta * np.asarray(Rinv, dtype=float)) @ (np.asarray(Bm, dtype=float).T @ X @ E)
+                out.append((X, dict(iters=int(ii[2 * b]), refinements=int(ii[2 * b + 1]), res0=float(dd[2 * b]), res=float(dd[2 * b + 1]), K=K)))
+            else:
+                out.append(X)
     else:
         maxiters, tol, max_refine = _sign_params(alg.inner_alg)
         ups = [[ctx.upload(_dense_f64(M)) for M in (p.E, p.A, p.B, p.C, p.X0)] for p in probs]

@@ -8,6 +8,7 @@
 
 #include "comm.hpp"
 #include "dense_are.hpp"
+#include "dense_are_batch.hpp"
 #include "dense_batch.hpp"
 #include "dense_gj.hpp"
 #include "dense_sign.hpp"
@@ -72,8 +73,9 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 105; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
-                                        // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched)
+int dre_version(void) { return 106; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+                                        // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
+                                        // 106: batched dense GARE (dre_dense_gare_solve_batched)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1285,6 +1287,77 @@ int dre_dense_gdre_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const
         }
         report_members(ctx, st, status);
     });
+}
+
+// dre_dense_gare_solve per member (dense_are_batch.hip).  Unlike the three calls above the return value is the first failed member's code.
+int dre_dense_gare_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                                 const dre_dense* const* Rinv, const dre_dense* const* Ct, const dre_dense* const* S, int maxiters, double tol,
+                                 int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo, int32_t* status) {
+    int first_fail = DRE_OK;
+    const int rc = guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        const char* who = "dre_dense_gare_solve_batched";
+        DRE_REQUIRE(E && A && B && Ct && X && status && batch >= 1 && E[0] && B[0] && Ct[0], std::string(who) + ": null argument or batch < 1");
+        DRE_REQUIRE(batch <= 65535, std::string(who) + ": batch must be in 1 .. 65535");
+        const int n = E[0]->m.rows, m = B[0]->m.cols, q = Ct[0]->m.cols;
+        DRE_REQUIRE(n >= 1 && 2 * n <= DENSE_MAX_N, std::string(who) + ": E must be square of order 1 .. " + std::to_string(DENSE_MAX_N / 2));
+        check_members(batch, E, n, n, who, "E");
+        check_members(batch, A, n, n, who, "A");
+        check_members(batch, B, n, m, who, "B");
+        check_members(batch, Ct, n, q, who, "Ct");
+        // the inner matrices are optional per member: the array or single entries may be null (identity)
+        bool anyR = false, anyS = false;
+        for (int b = 0; b < batch; ++b) {
+            if (Rinv && Rinv[b]) {
+                anyR = true;
+                DRE_REQUIRE(Rinv[b]->m.rows == m && Rinv[b]->m.cols == m, std::string(who) + ": Rinv of member " + std::to_string(b) + " must be m x m");
+            }
+            if (S && S[b]) {
+                anyS = true;
+                DRE_REQUIRE(S[b]->m.rows == q && S[b]->m.cols == q, std::string(who) + ": S of member " + std::to_string(b) + " must be q x q");
+            }
+        }
+        // the batched inversion is the register panel's whatever dense_gj_panel says: gj_check_order's refusal, in its wording
+        DRE_REQUIRE(2 * n <= GJ_REGISTER_MAX_N, std::string(who) + " (the Hamiltonian of order 2n): the register panel inverts matrices of order <= " +
+                                                    std::to_string(GJ_REGISTER_MAX_N) + ", order = " + std::to_string(2 * n));
+        DRE_REQUIRE(maxiters >= 1 && maxiters <= 1000, "dense GARE: maxiters must be in 1 .. 1000");
+        DRE_REQUIRE(max_refine >= 0, "dense GARE: max_refine must be >= 0");
+        require_memory(c, dense_gare_batched_doubles(batch, n, m, q, maxiters, max_refine));
+        for (int b = 0; b < batch; ++b) X[b] = nullptr;
+        Mat Es = pack_stack(c, batch, E, n, n), As = pack_stack(c, batch, A, n, n), Bs = pack_stack(c, batch, B, n, m),
+            Cs = pack_stack(c, batch, Ct, n, q);
+        auto pack_inner = [&](const dre_dense* const* h, int w) {
+            Mat St(c, w, w * batch), I(c, w, w);
+            set_identity(c, I);
+            for (int b = 0; b < batch; ++b) {
+                Mat v = St.colsview(b * w, w);
+                copy_mat(c, h[b] ? h[b]->m : I, v);
+            }
+            return St;
+        };
+        Mat Rs, Ss;
+        if (anyR && m > 0) Rs = pack_inner(Rinv, m);
+        if (anyS && q > 0) Ss = pack_inner(S, q);
+        std::vector<DenseGareResult> res;
+        std::vector<BatchMemberStatus> st;
+        dense_gare_solve_batched(c, batch, Es, As, Bs, Rs.p ? &Rs : nullptr, Cs, Ss.p ? &Ss : nullptr, m, q, maxiters, tol, max_refine, res, st);
+        for (int b = 0; b < batch; ++b) {
+            const DenseGareResult& r = res[(size_t)b];
+            if (iinfo) { iinfo[2 * b] = r.iters; iinfo[2 * b + 1] = r.refinements; }
+            if (dinfo) { dinfo[2 * b] = r.res0; dinfo[2 * b + 1] = r.res; }
+            if (st[(size_t)b].code) {
+                if (first_fail == DRE_OK) first_fail = st[(size_t)b].code;
+                continue;
+            }
+            auto* o = new dre_dense();
+            o->m = Mat(c, n, n);
+            copy_mat(c, r.X, o->m);
+            X[b] = o;
+        }
+        c->sync();
+        report_members(ctx, st, status);
+    });
+    return rc != DRE_OK ? rc : first_fail;
 }
 
 // ---- host helpers ------------------------------------------------------------------------------

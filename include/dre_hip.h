@@ -435,6 +435,20 @@ int dre_dense_gdre_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const
                                  const dre_dense* const* C, const dre_dense* const* X0, double t0, double tf, double dt, int order,
                                  int save_state, int maxiters, double tol, int max_refine, dre_gdre_result** out /* batch */,
                                  int32_t* status /* batch */);
+/* dre_dense_gare_solve per member (dre_version >= 106): the members share n, m, q (2n <= 4096: the Hamiltonian of order 2n goes through the
+ * register panel) and the sign parameters and differ in E, A, B, Ct and the inner matrices.  Rinv and S: the array may be NULL (identity for
+ * every member) and so may single entries (identity for that member).  X[b] is a new n x n matrix, NULL for a failed member;
+ * iters_refinements[2b], [2b+1] and res0_res[2b], [2b+1] as iinfo and dinfo of dre_dense_gare_solve.  status[b]: 0, DRE_ERR_SINGULAR (singular
+ * E_b, singular Z_k, rank-deficient extraction) or DRE_ERR_NOT_STABLE (stagnation, non-finite values, maxiters exhausted, a refinement whose
+ * closed loop is not c-stable).  The return value is the first failed member's code (DRE_OK when none failed); every surviving member's X
+ * is delivered all the same, and dre_last_error / dre_batch_member_error work as above.  DRE_ERR_INVALID: batch < 1, mismatched shapes,
+ * 2n > 4096, maxiters outside 1 .. 1000, max_refine < 0.  DRE_ERR_ALLOC: batch * ((26 + (max_refine > 0 ? maxiters + 12 : 0)) n^2 +
+ * n (m + q) + m^2 + q^2 + the panel's work stacks) doubles do not fit; checked before any kernel, nothing is allocated. */
+int dre_dense_gare_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                                 const dre_dense* const* Rinv /* array or entries may be NULL */, const dre_dense* const* Ct,
+                                 const dre_dense* const* S /* likewise */, int maxiters, double tol, int max_refine,
+                                 dre_dense** X /* batch, NULL for a failed member */, int64_t* iters_refinements /* 2*batch */,
+                                 double* res0_res /* 2*batch */, int32_t* status /* batch */);
 /* message of member b of the context's last batched call ("" when it did not fail or b is out of range) */
 const char* dre_batch_member_error(dre_ctx* ctx, int b);
 
