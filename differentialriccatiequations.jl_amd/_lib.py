@@ -152,6 +152,9 @@ PROTOTYPES = {
     "dre_dense_gare_solve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd]),
     "dre_dense_gare_residual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pvp, _pd]),
     "dre_dense_gdre_solve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _pvp]),
+    "dre_dense_gdre_solve_adaptive": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                 C.c_double, C.c_int64, _pd, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _pvp]),
+    "dre_gdre_result_step_stats": (C.c_int, [_vp, _pi64, _pd]),
     "dre_gdre_result_X_dense": (C.c_int, [_vp, _vp, C.c_int, _pvp]),
     "dre_gdre_result_dense_stats": (C.c_int, [_vp, _pi64, _pi64, _pd]),
     "dre_host_eigvals": (C.c_int, [C.c_int, _pd, _pd, _pd]),

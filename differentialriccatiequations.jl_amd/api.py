@@ -664,6 +664,21 @@ class MatrixSign:
 
 
 @dataclass(frozen=True)
+class StepControl:
+    """Step-size control of the dense Ros2 path: `solve(prob, Ros2(MatrixSign()), dt=dt0, adaptive=StepControl(...))`.  A trial step of size τ is
+    judged by Ros2's embedded first-order solution: D = Xnew − (X + τ K1), err = sqrt(mean_ij (D_ij / (atol + rtol·max(|X_ij|, |Xnew_ij|)))²);
+    it is accepted iff err ≤ 1 and the next size is τ·clamp(0.9·err^(−1/2), 0.2, 5) (no growth right after a rejection), kept inside
+    [dt_min, dt_max].  `tspan[1]` and the `tstops` (strictly between the ends of tspan, strictly monotone in the direction of integration) are hit
+    exactly.  A rejection at dt_min, or more than max_steps trial steps (rejected ones included), raises DREError(-8, DRE_ERR_STEP)."""
+    rtol: float = 1e-3
+    atol: float = 1e-6
+    dt_min: float = 0.0
+    dt_max: float = math.inf
+    max_steps: int = 10_000
+    tstops: tuple = ()
+
+
+@dataclass(frozen=True)
 class FactoredSign:
     """Low-rank GALE algorithm tag: the matrix-sign-function iteration on the densified pencil with the kept (P_k, c_k) sequence applied to the
     *factor* of the right-hand side (Benner & Quintana-Ortí 1999 §4).  LDLᵀ in, LDLᵀ out, no shifts; needs a c-stable pencil like `MatrixSign`
@@ -1046,9 +1061,53 @@ def residual(prob, X: LDLt, ctx=None) -> LDLt:
     return LDLt([], [], [], _handle=dev.DeviceLDLt(ctx, out, pencil))
 
 
-def solve_gdre(prob: GDREProblem, alg, dt, save_state=False, observer=None, ctx=None, return_stats=False):
+def _check_adaptive(prob, alg, dt, adaptive):
+    """the argument errors of adaptive= (raised before any device work)"""
+    if not isinstance(adaptive, StepControl):
+        raise TypeError("adaptive= takes a StepControl(...) object")
+    if isinstance(prob.X0, LDLt):
+        raise TypeError("adaptive= (step-size control) exists for the dense path only: it needs a dense X0 (an ndarray), not an LDLᵀ object; "
+                        "nothing was run on the device")
+    if not isinstance(alg, Ros2):
+        raise TypeError(f"adaptive= (step-size control) exists for Ros2 only, not {type(alg).__name__}: Ros2's embedded first-order solution is "
+                        "the error estimator; nothing was run on the device")
+    if not isinstance(alg.inner_alg, MatrixSign):
+        raise TypeError("adaptive= (step-size control) runs with the inner algorithm MatrixSign() named explicitly, Ros2(MatrixSign()); "
+                        "nothing was run on the device")
+    t0, tf = float(prob.tspan[0]), float(prob.tspan[1])
+    dt0 = float(dt)
+    bad = None
+    if not (math.isfinite(t0) and math.isfinite(tf) and tf != t0):
+        bad = "tspan must have two finite, different ends"
+    elif not (math.isfinite(dt0) and dt0 != 0.0 and (dt0 > 0) == (tf > t0)):
+        bad = "dt (the first step) must be finite, nonzero and of the sign of tspan[1] - tspan[0]"
+    elif not (adaptive.rtol > 0 and math.isfinite(adaptive.rtol)):
+        bad = "rtol must be positive"
+    elif not (adaptive.atol > 0 and math.isfinite(adaptive.atol)):
+        bad = "atol must be positive (with atol = 0 a zero entry of X has no error scale)"
+    elif not (0 <= adaptive.dt_min <= adaptive.dt_max):
+        bad = "0 <= dt_min <= dt_max expected"
+    elif int(adaptive.max_steps) < 1:
+        bad = "max_steps must be >= 1"
+    else:
+        prev = t0
+        for s_ in adaptive.tstops:
+            s_ = float(s_)
+            if not ((prev < s_ < tf) if tf > t0 else (prev > s_ > tf)):
+                bad = "tstops must lie strictly between the ends of tspan and be strictly monotone in the direction of integration"
+                break
+            prev = s_
+    if bad:
+        raise ValueError(f"adaptive=: {bad}; nothing was run on the device")
+
+
+def solve_gdre(prob: GDREProblem, alg, dt, save_state=False, observer=None, ctx=None, return_stats=False, adaptive=None):
     """solve(::GDREProblem{<:LDLᵀ}, ::Ros1/Ros2; dt, save_state, observer)
-    (DifferentialRiccatiEquations.jl:78-94, riccati/lowrank_ros1.jl, lowrank_ros2.jl)"""
+    (DifferentialRiccatiEquations.jl:78-94, riccati/lowrank_ros1.jl, lowrank_ros2.jl)
+    adaptive=StepControl(...): Ros2(MatrixSign()) with a dense X0 under step-size control, dt being the first step (_solve_gdre_dense)."""
+    if adaptive is not None:
+        _check_adaptive(prob, alg, dt, adaptive)
+        return _solve_gdre_dense(prob, alg, 2, dt, save_state, observer, ctx, return_stats, adaptive=adaptive)
     dense_order = {Ros1: 1, Ros2: 2, Ros3: 3, Ros4: 4}.get(type(alg))
     if not isinstance(prob.X0, LDLt):
         if isinstance(getattr(alg, "inner_alg", None), FactoredSign):
@@ -1179,9 +1238,11 @@ def dense_invert(A, ctx=None):
     return Ad.numpy(), piv, float(ld.value)
 
 
-def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_stats):
+def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_stats, adaptive=None):
     """solve(::GDREProblem{<:Matrix}, ::Ros<order>(MatrixSign()); dt, save_state, observer)  (dense_ros{1,2,3,4}.jl), device resident;
-    the observer hooks are replayed afterwards in dense_ros1.jl's order."""
+    the observer hooks are replayed afterwards in dense_ros1.jl's order.  adaptive (a StepControl): Ros2 under step-size control
+    (dre_dense_gdre_solve_adaptive); the solution's t is the non-uniform grid of the accepted steps, which are all the observer sees, and
+    return_stats adds accepted, rejected and err (one value per accepted step)."""
     ctx = ctx or dev.default_context()
     E, A, X0 = _dense_f64(prob.E), _dense_f64(prob.A), _dense_f64(prob.X0)
     Bm, Cm = _dense_f64(prob.B), _dense_f64(prob.C)
@@ -1189,8 +1250,15 @@ def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_st
     maxiters, tol, max_refine = _sign_params(alg.inner_alg)
     r = C.c_void_p()
     lib = ctx.lib
-    ctx.chk(lib.dre_dense_gdre_solve(ctx.ptr, *[u.ptr for u in ups], float(prob.tspan[0]), float(prob.tspan[1]), float(dt), int(order),
-                                     int(bool(save_state)), maxiters, tol, max_refine, C.byref(r)))
+    if adaptive is not None:
+        ts = np.array([float(s_) for s_ in adaptive.tstops], dtype=float)
+        ctx.chk(lib.dre_dense_gdre_solve_adaptive(ctx.ptr, *[u.ptr for u in ups], float(prob.tspan[0]), float(prob.tspan[1]), float(dt), int(order),
+                                                  float(adaptive.rtol), float(adaptive.atol), float(adaptive.dt_min), float(adaptive.dt_max),
+                                                  int(adaptive.max_steps), ts.ctypes.data_as(C.POINTER(C.c_double)), len(ts),
+                                                  int(bool(save_state)), maxiters, tol, max_refine, C.byref(r)))
+    else:
+        ctx.chk(lib.dre_dense_gdre_solve(ctx.ptr, *[u.ptr for u in ups], float(prob.tspan[0]), float(prob.tspan[1]), float(dt), int(order),
+                                         int(bool(save_state)), maxiters, tol, max_refine, C.byref(r)))
     try:
         ii = (C.c_int64 * 7)()
         lib.dre_gdre_result_info(r, ii)
@@ -1209,6 +1277,9 @@ def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_st
         res = np.zeros(2 * max(nsolve, 1))
         lib.dre_gdre_result_dense_stats(r, its.ctypes.data_as(C.POINTER(C.c_int64)), refs.ctypes.data_as(C.POINTER(C.c_int64)),
                                         res.ctypes.data_as(C.POINTER(C.c_double)))
+        if adaptive is not None:
+            counts, errs = (C.c_int64 * 2)(), np.zeros(max(nt - 1, 1))
+            lib.dre_gdre_result_step_stats(r, counts, errs.ctypes.data_as(C.POINTER(C.c_double)))
     finally:
         lib.dre_gdre_result_free(r)
     _call(observer, "observe_gdre_start", prob, alg)
@@ -1219,7 +1290,10 @@ def _solve_gdre_dense(prob, alg, order, dt, save_state, observer, ctx, return_st
     sol = DRESolution(Xs, Ks, t)
     if return_stats:
         solves = [dict(iters=int(its[j]), refinements=int(refs[j]), res0=float(res[2 * j]), res=float(res[2 * j + 1])) for j in range(nsolve)]
-        return sol, dict(lyapunov_solves=nsolve, solves=solves)
+        stats = dict(lyapunov_solves=nsolve, solves=solves)
+        if adaptive is not None:
+            stats.update(accepted=int(counts[0]), rejected=int(counts[1]), err=errs[:nt - 1].copy())
+        return sol, stats
     return sol
 
 
@@ -1285,7 +1359,7 @@ def _check_batch(probs, alg, observer):
     return kind, order
 
 
-def solve_batch(probs, alg, *, dt=None, save_state=False, errors="raise", ctx=None, return_stats=False, observer=None):
+def solve_batch(probs, alg, *, dt=None, save_state=False, errors="raise", ctx=None, return_stats=False, observer=None, adaptive=None):
     """An ensemble of independent problems of one size side by side on one device (dre_dense_gale_solve_batched /
     dre_dense_gdre_solve_batched / dre_dense_gare_solve_batched): a list of GALEProblem with MatrixSign(), of GDREProblem with dense X0
     with Ros1(MatrixSign()) / Ros2(MatrixSign()), or of GAREProblem with MatrixSign() (2n <= 4096; with return_stats the info dict of
@@ -1295,6 +1369,9 @@ def solve_batch(probs, alg, *, dt=None, save_state=False, errors="raise", ctx=No
     `partial` attribute)."""
     if errors not in ("raise", "return"):
         raise ValueError('solve_batch: errors must be "raise" or "return"')
+    if adaptive is not None:
+        raise TypeError("solve_batch: adaptive= (step-size control) is not batched, the members of a batch share one fixed grid; solve the problems "
+                        "one by one with solve(prob, Ros2(MatrixSign()), dt=dt0, adaptive=...); nothing was run on the device")
     probs = list(probs)
     kind, order = _check_batch(probs, alg, observer)
     if kind == "gdre" and dt is None:

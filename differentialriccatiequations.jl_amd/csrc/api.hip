@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "comm.hpp"
+#include "dense_adaptive.hpp"
 #include "dense_are.hpp"
 #include "dense_are_batch.hpp"
 #include "dense_batch.hpp"
@@ -48,6 +49,10 @@ struct dre_gdre_result {
     int n = 0;
     std::vector<Mat> Xd;
     std::vector<SignStats> solves;
+    // adaptive dense path (dre_dense_gdre_solve_adaptive): trial steps accepted / rejected, the error measure of every accepted step
+    bool adaptive = false;
+    int64_t accepted = 0, rejected = 0;
+    std::vector<double> step_err;
 };
 
 struct dre_sign { std::unique_ptr<SignLyap> s; };
@@ -73,9 +78,10 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 106; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 107; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
-                                        // 106: batched dense GARE (dre_dense_gare_solve_batched)
+                                        // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
+                                        // dre_gdre_result_step_stats, DRE_ERR_STEP)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1083,6 +1089,31 @@ int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, c
         r->Xd = std::move(d.X); r->solves = std::move(d.solves);
         *out = r;
     });
+}
+int dre_dense_gdre_solve_adaptive(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
+                                  double t0, double tf, double dt0, int order, double rtol, double atol, double dt_min, double dt_max, int64_t max_steps,
+                                  const double* tstops, int ntstops, int save_state, int maxiters, double tol, int max_refine, dre_gdre_result** out) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && A && B && C && X0 && out, "dre_dense_gdre_solve_adaptive: null argument");
+        DRE_REQUIRE(ntstops >= 0 && (ntstops == 0 || tstops), "dre_dense_gdre_solve_adaptive: ntstops must be >= 0, with tstops given when it is positive");
+        StepControl sc;
+        sc.rtol = rtol; sc.atol = atol; sc.dt_min = dt_min; sc.dt_max = dt_max; sc.max_steps = (long)max_steps;
+        sc.tstops.assign(tstops, tstops + ntstops);
+        DenseAdaptiveResult d = dense_gdre_solve_adaptive(c, E->m, A->m, B->m, C->m, X0->m, t0, tf, dt0, order, sc, save_state != 0, maxiters, tol, max_refine);
+        auto* r = new dre_gdre_result();
+        r->dense = true; r->n = E->m.rows; r->m = B->m.cols;
+        r->r.t = std::move(d.r.t); r->r.Kt = std::move(d.r.Kt);
+        r->Xd = std::move(d.r.X); r->solves = std::move(d.r.solves);
+        r->adaptive = true; r->accepted = d.accepted; r->rejected = d.rejected; r->step_err = std::move(d.err);
+        *out = r;
+    });
+}
+int dre_gdre_result_step_stats(const dre_gdre_result* r, int64_t* accepted_rejected, double* err) {
+    if (!r || !r->adaptive) return DRE_ERR_INVALID;
+    if (accepted_rejected) { accepted_rejected[0] = r->accepted; accepted_rejected[1] = r->rejected; }
+    if (err) std::memcpy(err, r->step_err.data(), r->step_err.size() * sizeof(double));
+    return DRE_OK;
 }
 int dre_dense_invert(dre_ctx* ctx, dre_dense* A, int32_t* piv, double* logabsdet) {
     return guarded(ctx, [&] {

@@ -636,18 +636,43 @@ function residual(prob::DenseGAREProblem, X::AbstractMatrix; ctx::Context=defaul
     download(ctx, R[]), nrm[]
 end
 
-"solve(::GDREProblem{<:Matrix}, Ros1..Ros4(MatrixSign()); dt, save_state, observer)  — src/riccati/dense_ros{1,2,3,4}.jl"
+"""Step-size control of the dense Ros2 path, `solve(prob, Ros2(inner_alg = MatrixSign()); dt = dt0, adaptive = StepControl(...))`: a trial step is
+judged by Ros2's embedded first-order solution (weighted RMS error with `rtol`, `atol`), accepted iff err ≤ 1, the next size is
+τ·clamp(0.9·err^(−1/2), 0.2, 5) inside [dt_min, dt_max]; `tspan[2]` and the `tstops` are hit exactly.  DREError(-8) on a rejection at `dt_min`
+or more than `max_steps` trial steps."""
+Base.@kwdef struct StepControl
+    rtol::Float64 = 1e-3
+    atol::Float64 = 1e-6
+    dt_min::Float64 = 0.0
+    dt_max::Float64 = Inf
+    max_steps::Int = 10_000
+    tstops::Vector{Float64} = Float64[]
+end
+
+"""solve(::GDREProblem{<:Matrix}, Ros1..Ros4(MatrixSign()); dt, save_state, observer)  — src/riccati/dense_ros{1,2,3,4}.jl
+`adaptive = StepControl(...)` (Ros2 only): `dt` is the first step and `sol.t` the non-uniform grid of the accepted steps; `stats = true`
+returns `(sol, (accepted, rejected, err))`."""
 function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,Ros2,Ros3,Ros4}; dt::Real, save_state::Bool=false, observer=nothing,
-                           ctx::Context=default_context())
+                           ctx::Context=default_context(), adaptive::Union{Nothing,StepControl}=nothing, stats::Bool=false)
     alg.inner_alg isa MatrixSign || throw(ArgumentError("a dense X0 runs on the device only with the inner algorithm named: Ros1(inner_alg = MatrixSign())"))
+    adaptive === nothing || alg isa Ros2 || throw(ArgumentError("adaptive = StepControl(...) exists for Ros2 only (its embedded first-order solution is the estimator)"))
     sa = alg.inner_alg
     order = alg isa Ros1 ? 1 : alg isa Ros2 ? 2 : alg isa Ros3 ? 3 : 4
     ops = [upload(ctx, Matrix(M)) for M in (prob.E, prob.A, prob.B, prob.C, prob.X0)]
     res = Ref{Ptr{Cvoid}}(C_NULL)
-    chk(ctx, ccall((:dre_dense_gdre_solve, LIB), Cint,
-                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}),
-                   ctx.ptr, ops[1].ptr, ops[2].ptr, ops[3].ptr, ops[4].ptr, ops[5].ptr, prob.tspan[1], prob.tspan[2], dt, order, save_state,
-                   sa.maxiters, sa.tol, sa.max_refine, res))
+    if adaptive === nothing
+        chk(ctx, ccall((:dre_dense_gdre_solve, LIB), Cint,
+                       (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cint, Cint, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}),
+                       ctx.ptr, ops[1].ptr, ops[2].ptr, ops[3].ptr, ops[4].ptr, ops[5].ptr, prob.tspan[1], prob.tspan[2], dt, order, save_state,
+                       sa.maxiters, sa.tol, sa.max_refine, res))
+    else
+        sc = adaptive
+        chk(ctx, ccall((:dre_dense_gdre_solve_adaptive, LIB), Cint,
+                       (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cint, Cdouble, Cdouble, Cdouble, Cdouble,
+                        Int64, Ptr{Float64}, Cint, Cint, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}),
+                       ctx.ptr, ops[1].ptr, ops[2].ptr, ops[3].ptr, ops[4].ptr, ops[5].ptr, prob.tspan[1], prob.tspan[2], dt, order, sc.rtol, sc.atol,
+                       sc.dt_min, sc.dt_max, sc.max_steps, sc.tstops, length(sc.tstops), save_state, sa.maxiters, sa.tol, sa.max_refine, res))
+    end
     info = zeros(Int64, 7)
     ccall((:dre_gdre_result_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), res[], info)
     nt, nx, m, n = info[1], info[2], info[6], info[7]
@@ -662,6 +687,8 @@ function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,
         chk(ctx, ccall((:dre_gdre_result_X_dense, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}), ctx.ptr, res[], i, h))
         push!(Xs, download(ctx, h[]))
     end
+    counts, errs = zeros(Int64, 2), zeros(max(nt - 1, 1))
+    adaptive === nothing || ccall((:dre_gdre_result_step_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}), res[], counts, errs)
     ccall((:dre_gdre_result_free, LIB), Cint, (Ptr{Cvoid},), res[])
     if observer !== nothing                            # dense_ros1.jl's order, replayed after the device run
         Callbacks.observe_gdre_start!(observer, prob, alg)
@@ -671,10 +698,11 @@ function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,
         end
         Callbacks.observe_gdre_done!(observer)
     end
-    DRESolution(Xs, Ks, t)
+    sol = DRESolution(Xs, Ks, t)
+    stats && adaptive !== nothing ? (sol, (accepted = counts[1], rejected = counts[2], err = errs[1:nt-1])) : sol
 end
 
 export Context, Pencil, LDLᵀ, lowrank, compress!, compress_fast!, concatenate!, residual, lyapunov_apply, ADI, Shifts, Callbacks, GALEProblem, GDREProblem, DRESolution, Ros1, Ros2,
-       Ros3, Ros4, MatrixSign, FactoredSign, SignFactorization, solve_lr, solve_dense, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve
+       Ros3, Ros4, MatrixSign, StepControl, FactoredSign, SignFactorization, solve_lr, solve_dense, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve
 
 end # module

@@ -34,6 +34,7 @@ extern "C" {
 #define DRE_ERR_INTERNAL (-5)
 #define DRE_ERR_NODEVICE (-6)
 #define DRE_ERR_NOT_STABLE (-7)   /* dense path: (F, E) is not c-stable, the sign iteration did not reach -E; dense GARE: the Hamiltonian has eigenvalues on or near the imaginary axis */
+#define DRE_ERR_STEP (-8)         /* adaptive dense path: a step was rejected at dt_min, or more than max_steps trial steps were needed */
 
 /* hard limits of the engine */
 #define DRE_ADI_MAX_ITERS 100000      /* largest dre_adi_options.maxiters (the device keeps the norm history as a ring that the host empties per chunk) */
@@ -382,6 +383,26 @@ int dre_dense_gale_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, c
 int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
                          double t0, double tf, double dt, int order, int save_state, int maxiters, double tol, int max_refine,
                          dre_gdre_result** out);
+/* solve(GDREProblem{<:Matrix}, Ros2(MatrixSign()); dt = dt0, adaptive = StepControl(...)) (dre_version >= 107): Ros2 with step-size control by
+ * its embedded first-order solution.  One trial step of size tau from (t, X): Xnew as a Ros2 step of dre_dense_gdre_solve, D = Xnew - (X + tau K1),
+ * err = sqrt(mean_ij (D_ij / (atol + rtol max(|X_ij|, |Xnew_ij|)))^2); accepted iff err <= 1; the next size is tau * clamp(0.9 err^(-1/2), 0.2, 5)
+ * (5 when err == 0; 0.2 and a rejection when err is not finite; at most 1 on the trial right after a rejection), clamped to [dt_min, dt_max].
+ * tf and the ntstops values of tstops (strictly between t0 and tf, strictly monotone in the direction of integration) are hit exactly: with d the
+ * distance to the next of them, a step is d when d <= 1.1 |h| and d/2 when d < 2 |h|.  dt0: the first step, of the sign of tf - t0.  The
+ * step tau is |h| in either direction of integration.
+ * The result is an ordinary dense dre_gdre_result over the ACCEPTED steps (_info, _times, _K, _K_all, _K_device, _X_dense, _dense_stats, _free;
+ * info[4] and _dense_stats count the Lyapunov solves of every trial, two per trial); dre_gdre_result_step_stats adds the counts and errors.
+ * Errors: DRE_ERR_INVALID for order != 2, rtol <= 0, atol <= 0, dt0 zero or of the wrong sign, dt_min < 0 or dt_min > dt_max, max_steps < 1,
+ * tstops outside the open span or not monotone; DRE_ERR_STEP for a rejection at a step <= dt_min or more than max_steps trial steps (rejected
+ * ones included); DRE_ERR_NOT_STABLE / DRE_ERR_SINGULAR of a factorisation are passed up, not turned into rejections; DRE_ERR_ALLOC when the
+ * fixed part, (maxiters + 28) n^2 doubles, does not fit (checked before any kernel) or when the result, which grows in chunks of 64 K(t) and
+ * of 8 saved states, cannot grow (the message names the step).  The context stays usable after every one of them. */
+int dre_dense_gdre_solve_adaptive(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
+                                  double t0, double tf, double dt0, int order, double rtol, double atol, double dt_min, double dt_max, int64_t max_steps,
+                                  const double* tstops, int ntstops, int save_state, int maxiters, double tol, int max_refine, dre_gdre_result** out);
+/* of an adaptive result (DRE_ERR_INVALID on any other): accepted_rejected[0], [1] trial steps accepted / rejected; err[i] the error measure of
+   accepted step i (accepted_rejected[0] = info[0] - 1 values); either array may be NULL */
+int dre_gdre_result_step_stats(const dre_gdre_result* r, int64_t* accepted_rejected /* 2 */, double* err /* per accepted step */);
 /* A <- inv(A) in place with the configured pivoting panel (n x n, n <= 46340); piv (n entries, or NULL): the row interchanges, LAPACK
  * style with 0-based indices (row j was swapped with row piv[j] >= j); logabsdet (or NULL): log |det A|.  A singular A (an exactly zero or
  * non-finite pivot) is DRE_ERR_SINGULAR and leaves A undefined. */
