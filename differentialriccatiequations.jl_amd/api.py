@@ -199,6 +199,42 @@ def orthf(L):
     return dev.DenseMatrix(ctx, q).numpy(), dev.DenseMatrix(ctx, r).numpy()
 
 
+def sym_eigh(A, method="jacobi", tol=None, ctx=None, return_stats=False):
+    """eigh(A) of a dense symmetric matrix on the device: (w, V) with w ascending and A V = V diag(w).
+    method "jacobi": the whole-device block Jacobi solver (dre_sym_eig_jacobi; converged when off(A) <= tol ||A||_F, tol None: n eps);
+    method "ql": the library's Householder + implicit-QL solver (dre_sym_eig), which returns the eigenpairs its early-terminating reduction
+    kept (all of them unless A is numerically rank deficient) and ignores tol; it is that solver whatever the context option sym_eig_method
+    says (the option chooses the solver of the compressions, not of this call).  return_stats adds dict(sweeps, rounds) (zeros for "ql").
+    A non-square A, an A that is not symmetric to 100 eps max|A|, and an unknown method are errors before anything runs on the device."""
+    A = np.asarray(A, dtype=float)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError(f"sym_eigh: a square matrix is expected, got shape {A.shape}; nothing was run on the device")
+    if method not in ("jacobi", "ql"):
+        raise ValueError(f"sym_eigh: unknown method {method!r} (\"jacobi\" or \"ql\"); nothing was run on the device")
+    if tol is not None and not float(tol) > 0.0:
+        raise ValueError("sym_eigh: tol must be positive; nothing was run on the device")
+    if A.size and np.isfinite(A).all():           # (a non-finite entry is the device solver's DRE_ERR_INVALID)
+        asym = np.abs(A - A.T).max()
+        if asym > 100 * np.finfo(float).eps * np.abs(A).max():
+            raise ValueError(f"sym_eigh: the matrix is not symmetric (max |A - A'| = {asym:.3e}); nothing was run on the device")
+    n = A.shape[0]
+    stats = dict(sweeps=0, rounds=0)
+    if n == 0:
+        w, V = np.zeros(0), np.zeros((0, 0))
+        return (w, V, stats) if return_stats else (w, V)
+    ctx = ctx or dev.default_context()
+    Ad = ctx.upload(np.asfortranarray(A))
+    wp, vp = C.c_void_p(), C.c_void_p()
+    if method == "jacobi":
+        ii = (C.c_int64 * 2)()
+        ctx.chk(ctx.lib.dre_sym_eig_jacobi(ctx.ptr, Ad.ptr, float(tol) if tol is not None else 0.0, C.byref(wp), C.byref(vp), ii))
+        stats = dict(sweeps=int(ii[0]), rounds=int(ii[1]))
+    else:
+        ctx.chk(ctx.lib.dre_sym_eig(ctx.ptr, Ad.ptr, 4.0, C.byref(wp), C.byref(vp)))
+    w, V = dev.DenseMatrix(ctx, wp).numpy().ravel(), dev.DenseMatrix(ctx, vp).numpy()
+    return (w, V, stats) if return_stats else (w, V)
+
+
 def delta(a, b):
     """Stuff.delta (src/Stuff.jl:21)"""
     return np.linalg.norm(a - b) / max(np.linalg.norm(a), np.linalg.norm(b))

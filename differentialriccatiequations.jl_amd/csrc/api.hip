@@ -17,6 +17,7 @@
 #include "engine.hpp"
 #include "hostla.hpp"
 #include "profiling.hpp"
+#include "sym_jacobi.hpp"
 
 using namespace dre;
 
@@ -214,6 +215,7 @@ static OptionRef option_ref(Ctx& c, const std::string& key) {
     DRE_OPT_I("setup_batched", setup_batched)
     DRE_OPT_I("dense_warm", dense_warm)
     DRE_OPT_I("dense_gj_panel", dense_gj_panel)
+    DRE_OPT_I("sym_eig_method", sym_eig_method)
     DRE_OPT_I("side_prefetch", side_prefetch)
     DRE_OPT_I("side_gate", side_gate)
     DRE_OPT_I("recurrence_wide", recurrence_wide)
@@ -249,6 +251,8 @@ int dre_ctx_set_option(dre_ctx* ctx, const char* name, double value) {
         }
         if (key == "dense_gj_panel" && !(value == 0.0 || value == 1.0 || value == 2.0))
             throw Error(ERR_INVALID, "dre_ctx_set_option: dense_gj_panel must be 0 (auto), 1 (register) or 2 (tournament)");
+        if (key == "sym_eig_method" && !(value == 0.0 || value == 1.0))
+            throw Error(ERR_INVALID, "dre_ctx_set_option: sym_eig_method must be 0 (Householder + QL) or 1 (block Jacobi)");
         const OptionRef r = option_ref(ctx->c, key);
         if (r.i) *r.i = (int)value;
         else if (r.d) *r.d = value;
@@ -482,6 +486,9 @@ int dre_sym_eig(dre_ctx* ctx, const dre_dense* S, double tolfac, dre_dense** val
         Ctx* c = &ctx->c;
         Mat A(c, S->m.rows, S->m.cols);
         copy_mat(c, S->m, A);
+        // (this entry IS the Householder + QL solver, whatever sym_eig_method says; the Jacobi solver has dre_sym_eig_jacobi)
+        struct Method0 { Ctx* c; int was; ~Method0() { c->sym_eig_method = was; } } method0{c, c->sym_eig_method};
+        c->sym_eig_method = 0;
         SymEig e = sym_eig(c, A, tolfac > 0 ? tolfac : 4.0);
         std::vector<int> ids(e.j);
         for (int i = 0; i < e.j; ++i) ids[i] = i;
@@ -496,6 +503,29 @@ int dre_sym_eig(dre_ctx* ctx, const dre_dense* S, double tolfac, dre_dense** val
             DRE_HIP(hipMemcpyAsync(W->m.p, w.data(), e.j * sizeof(double), hipMemcpyHostToDevice, c->stream));
             DRE_HIP(hipStreamSynchronize(c->stream));
         }
+        *values = W; *vectors = V;
+    });
+}
+int dre_sym_eig_jacobi(dre_ctx* ctx, const dre_dense* S, double tol, dre_dense** values, dre_dense** vectors, int64_t* stats) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(S && values && vectors, "dre_sym_eig_jacobi: null argument");
+        BjStats bs;
+        SymEig e = sym_eig_jacobi(c, S->m, tol, &bs);
+        std::vector<int> ids(e.j);
+        for (int i = 0; i < e.j; ++i) ids[i] = i;
+        std::sort(ids.begin(), ids.end(), [&](int a, int b) { return e.w[a] < e.w[b]; });
+        std::vector<double> w(e.j);
+        for (int i = 0; i < e.j; ++i) w[i] = e.w[ids[i]];
+        auto* V = new dre_dense();
+        V->m = sym_eig_backtransform(c, e, ids);
+        auto* W = new dre_dense();
+        W->m = Mat(c, e.j, 1);
+        if (e.j) {
+            DRE_HIP(hipMemcpyAsync(W->m.p, w.data(), e.j * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            DRE_HIP(hipStreamSynchronize(c->stream));
+        }
+        if (stats) { stats[0] = bs.sweeps; stats[1] = bs.rounds; }
         *values = W; *vectors = V;
     });
 }

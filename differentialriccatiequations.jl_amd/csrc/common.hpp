@@ -196,6 +196,9 @@ struct Ctx {
     // dense path (dense_gj.hip, gj_invert): the pivoting panel of the Gauss-Jordan inversion.  0 auto (the register panel for n <= 4096,
     // the tournament panel above), 1 the register panel only (n > 4096 is DRE_ERR_INVALID), 2 the tournament panel at every n
     int dense_gj_panel = 0;
+    // symmetric eigensolver behind every rank-revealing compression (qr_band.hip, sym_eig with want_eig): 0 Householder tridiagonalisation + implicit QL
+    // (one workgroup), 1 block Jacobi on the whole device (sym_jacobi.hip)
+    int sym_eig_method = 0;
     // dense-X time loop: the side stream's set-up of step i + 1 is enqueued by a parked host thread at the end of step i (0: inside step i + 1)
     int recurrence_wide = 1;    // residual-recurrence loop: the increments of a solve may exceed the factor-form limit (c + 64 <= n); 0: round 4's in-loop compression
     int side_gate = 0;          // residual-recurrence loop: the parked thread enqueues the side stream only while the time loop's thread waits (launch gate below; measured at n = 5177: 85.1 ms with, 85.4 ms without — inside the noise, off)

@@ -3,6 +3,7 @@
 #include "dense_device.hpp"
 #include <functional>
 #include "profiling.hpp"
+#include "sym_jacobi.hpp"
 #include <atomic>
 #include <chrono>
 
@@ -1366,6 +1367,8 @@ __global__ void k_tri_to_dense(int n, const double* __restrict__ d, const double
 
 SymEig sym_eig(Ctx* ctx, Mat& S, double tolfac, bool want_eig, double abs_tol, bool tol_is_floor, double deflate) {
     DRE_REQUIRE(S.rows == S.cols, "sym_eig: square matrix expected");
+    if (want_eig) sym_eig_dump_input(ctx, S);          // (DRE_SYM_EIG_DUMP=<dir>: the matrix goes to a file first; off: one getenv)
+    if (want_eig && ctx->sym_eig_method == 1) return sym_eig_jacobi(ctx, S);          // (option sym_eig_method: the whole-device block Jacobi solver)
     SymEig out;
     const int q = S.rows;
     out.q = q;

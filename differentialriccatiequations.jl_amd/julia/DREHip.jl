@@ -702,7 +702,23 @@ function CommonSolve.solve(prob::GDREProblem{<:AbstractMatrix}, alg::Union{Ros1,
     stats && adaptive !== nothing ? (sol, (accepted = counts[1], rejected = counts[2], err = errs[1:nt-1])) : sol
 end
 
+"eigen(Symmetric(A)) on the device: (values ascending, vectors).  method = :jacobi: whole-device block Jacobi (dre_sym_eig_jacobi; converged when off(A) <= tol ||A||_F, tol = 0: n eps; stats = true adds (sweeps, rounds)); :ql: Householder + implicit QL (dre_sym_eig)."
+function sym_eigh(A::AbstractMatrix; method::Symbol=:jacobi, tol::Float64=0.0, stats::Bool=false, ctx::Context=default_context())
+    size(A, 1) == size(A, 2) || throw(ArgumentError("sym_eigh: a square matrix is expected"))
+    method in (:jacobi, :ql) || throw(ArgumentError("sym_eigh: method must be :jacobi or :ql"))
+    Ad = upload(ctx, Matrix{Float64}(A))
+    w, V = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    ii = zeros(Int64, 2)
+    if method === :jacobi
+        chk(ctx, ccall((:dre_sym_eig_jacobi, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}, Ptr{Int64}), ctx.ptr, Ad.ptr, tol, w, V, ii))
+    else
+        chk(ctx, ccall((:dre_sym_eig, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}), ctx.ptr, Ad.ptr, 4.0, w, V))
+    end
+    vals, vecs = vec(download(ctx, w[])), download(ctx, V[])
+    stats ? (vals, vecs, (sweeps = ii[1], rounds = ii[2])) : (vals, vecs)
+end
+
 export Context, Pencil, LDLᵀ, lowrank, compress!, compress_fast!, concatenate!, residual, lyapunov_apply, ADI, Shifts, Callbacks, GALEProblem, GDREProblem, DRESolution, Ros1, Ros2,
-       Ros3, Ros4, MatrixSign, StepControl, FactoredSign, SignFactorization, solve_lr, solve_dense, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve
+       Ros3, Ros4, MatrixSign, StepControl, FactoredSign, SignFactorization, solve_lr, solve_dense, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve, sym_eigh
 
 end # module

@@ -97,7 +97,10 @@ int dre_ctx_info(dre_ctx* ctx, int64_t* info /* [0]=CUs [1]=pool bytes */);
  *                               X compressed every s-th step only
  *   "dense_gj_panel"            dense path: the pivoting panel of the Gauss-Jordan inversions.  0 (default) auto: the register panel for
  *                               n <= 4096, the tournament panel above; 1 the register panel only (n > 4096 is DRE_ERR_INVALID); 2 the
- *                               tournament panel at every n.  Other values are DRE_ERR_INVALID */
+ *                               tournament panel at every n.  Other values are DRE_ERR_INVALID
+ *   "sym_eig_method"            the symmetric eigensolver behind the rank-revealing compressions (FactoredSign, compress!, the projection's Gram
+ *                               eigenproblem).  0 (default) Householder tridiagonalisation + implicit QL (dre_sym_eig); 1 block Jacobi on the
+ *                               whole device (dre_sym_eig_jacobi).  Other values are DRE_ERR_INVALID */
 int dre_ctx_set_option(dre_ctx* ctx, const char* name, double value);
 /* the current value of an option of dre_ctx_set_option (tests snapshot and restore what they change; no reference counterpart: the reference's
  * tunables are keyword arguments) */
@@ -155,6 +158,12 @@ int dre_ctx_set_orthf(dre_ctx* ctx, dre_orthf_fn fn, void* user);
 /* eigen(Symmetric(S)) with early-terminating tridiagonalisation (src/LDLt.jl:214); returns the j computed
  * eigenpairs (all those above tolfac*eps*||S||_F in magnitude), values ascending */
 int dre_sym_eig(dre_ctx* ctx, const dre_dense* S, double tolfac, dre_dense** values, dre_dense** vectors);
+/* eigen(Symmetric(S)) by two-sided cyclic block Jacobi on the whole device (blocks of 16, round-robin ordering, both products of the update on
+ * v_mfma_f64_16x16x4_f64): all q eigenpairs, values ascending, S untouched (full symmetric storage; indefinite, rank-deficient and clustered
+ * spectra are fine).  Converged when off(A) <= tol ||A||_F; tol <= 0: q eps.  stats (may be NULL): [0] block sweeps, [1] rounds.
+ * DRE_ERR_INVALID for a non-finite S, DRE_ERR_INTERNAL after 30 sweeps.  The context option "sym_eig_method" = 1 puts this solver behind
+ * every rank-revealing compression of the library instead of the Householder + QL solver of dre_sym_eig. */
+int dre_sym_eig_jacobi(dre_ctx* ctx, const dre_dense* S, double tol, dre_dense** values, dre_dense** vectors, int64_t* stats);
 /* factorize(cA*A' + (cE_re + i cE_im)*E')  (src/blocklinear/backslash.jl:8-15); complex iff cE_im != 0.
  * The multifrontal LU does NOT pivot (the reference's UMFPACK / CHOLMOD do): it is exact-arithmetic safe for the pencils of the path
  * (-(A + pE) symmetric positive definite for real p < 0, complex symmetric with definite parts otherwise) and for diagonally dominant
