@@ -223,6 +223,7 @@ static OptionRef option_ref(Ctx& c, const std::string& key) {
     DRE_OPT_I("prefetch_batch", prefetch_batch)
     DRE_OPT_I("dense_x_max_n", dense_x_max_n)
     DRE_OPT_I("dense_x_max_k", dense_x_max_k)
+    DRE_OPT_I("final_x_lazy", final_x_lazy)
     DRE_OPT_I("adi_group", adi_group)
     DRE_OPT_I("adi_group_max_n", adi_group_max_n)
     DRE_OPT_I("adi_fan", adi_fan)
@@ -1049,7 +1050,15 @@ int dre_gdre_result_K_all(dre_ctx* ctx, const dre_gdre_result* r, double* K_host
 }
 int dre_gdre_result_X(const dre_gdre_result* r, int i, dre_ldlt** X) {
     if (r->dense || i < 0 || i >= (int)r->r.X.size()) return DRE_ERR_INVALID;
-    auto* h = new dre_ldlt(); h->x = r->r.X[i]; h->pen = r->pen; *X = h;
+    // a final X the solve left in dense form is factored here, once, on the stream of the solve's context (gdre.hip, gdre_result_x); the
+    // handle is const for the caller, the cache behind it is not
+    GdreResult& res = const_cast<dre_gdre_result*>(r)->r;
+    Ctx* const c = res.final_x ? res.final_x->ctx : nullptr;
+    LDLtP x;
+    try { x = gdre_result_x(res, i); }
+    catch (const Error& e) { if (c) c->last_error = e.what(); else g_noctx_error = e.what(); return e.code; }
+    catch (const std::exception& e) { if (c) c->last_error = e.what(); else g_noctx_error = e.what(); return DRE_ERR_INTERNAL; }
+    auto* h = new dre_ldlt(); h->x = x; h->pen = r->pen; *X = h;
     return DRE_OK;
 }
 int dre_gdre_result_gale(const dre_gdre_result* r, int j, int64_t* iinfo, double* dinfo) {

@@ -168,6 +168,9 @@ struct Ctx {
     // residual factors wider than this leave the dense-X loop for the factored path (0: the fast chain's own limit ADI_FAST_MAX_K); also the
     // switch the tests use to force that fallback in the middle of a run
     int dense_x_max_k = 0;
+    // a run that ends on the dense-X path hands its last X to the result as the dense matrix; the LDL' form (a band reduction of the full
+    // n x n matrix, nothing K(t) depends on) is produced when a caller asks for that X (gdre.hip, gdre_result_x); 0: inside the solve
+    int final_x_lazy = 1;
     // group chain of the dense-X loop (dense.hip k_adi_group, gdre.hip group_ops_prepare): g ADI iterations per launch.  1 = auto (largest
     // divisor of the cycle length up to 5), 0 = off (one launch per iteration), g >= 2 = that group size if it divides the cycle length
     int adi_group = 1;

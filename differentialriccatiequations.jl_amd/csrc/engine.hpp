@@ -4,6 +4,7 @@
 #include <complex>
 #include <functional>
 #include <map>
+#include <mutex>
 
 #include "common.hpp"
 #include "dense.hpp"
@@ -202,14 +203,27 @@ struct GdreProblem {
     LDLtP X0;
     double t0 = 0, tf = 0;
 };
+// Final X of a run that ended on the dense-X path (gdre.hip, ros1_dense_step) with the option final_x_lazy: the dense symmetric matrix as the
+// time loop left it.  The result shares ownership of the buffer (it cannot go back to the pool while the result lives); the LDL' form is
+// produced by the first gdre_result_x that asks for it, on the stream of the context the solve ran on, and kept.
+struct FinalXDense {
+    Ctx* ctx = nullptr;               // the context of the solve: the result must be freed before it
+    Mat Xd;                           // n x n; released once the factors exist
+    double ctf = 4.0;                 // compress_tolfac of the solve
+    long conversions = 0;
+    std::mutex mu;
+};
 struct GdreResult {
     std::vector<double> t;
     std::vector<Mat> Kt;              // K(t_i)' stored as n x m (solver ordering)
-    std::vector<LDLtP> X;             // first/last or all (save_state)
+    std::vector<LDLtP> X;             // first/last or all (save_state); the last entry is null while final_x holds it in dense form
     std::vector<AdiResult> gale;      // one per Lyapunov solve (Ros2: two per step), X/residual handles dropped
     long adi_iters = 0;
     long nfactor = 0;
+    std::shared_ptr<FinalXDense> final_x;
 };
 GdreResult gdre_solve(Ctx* ctx, const GdreProblem& prob, int order, double dt, bool save_state, const AdiOptions& adi);
+// X[i] of a result; converts a final X that is still dense (once: a second call returns the same factors without device work)
+LDLtP gdre_result_x(GdreResult& r, int i);
 
 }  // namespace dre

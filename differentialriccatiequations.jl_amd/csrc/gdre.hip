@@ -2033,7 +2033,21 @@ GdreResult gdre_solve(Ctx* ctx, const GdreProblem& prob, int order, double dt, b
         std::fprintf(stderr, "[pool] main: %ld misses, %.1f MB; side: %ld misses, %.1f MB\n", ctx->pool.misses(), ctx->pool.total_bytes() / 1048576.0,
                      side ? side->pool.misses() : 0L, side ? side->pool.total_bytes() / 1048576.0 : 0.0);
     sx.report();
-    if (x_is_dense) X = dense_to_ldlt(ctx, n, sx.X, ctf);
+    if (x_is_dense) {
+        // K(t) is complete and nothing downstream of the LDL' form of the last X feeds it: with final_x_lazy the result takes a handle of the
+        // dense matrix (shared with sx: the buffer stays out of the pool for as long as the result lives) and the band reduction — a host-paced
+        // chain of ~70 short kernels — runs when a caller asks for that X (gdre_result_x), if one ever does
+        if (steps_on) DRE_HIP(hipStreamSynchronize(ctx->stream));          // (the stamp below starts behind the last step's trailing kernels)
+        const auto f0 = std::chrono::steady_clock::now();
+        if (ctx->final_x_lazy) {
+            out.final_x = std::make_shared<FinalXDense>();
+            out.final_x->ctx = ctx; out.final_x->Xd = sx.X; out.final_x->ctf = ctf;
+            X = nullptr;
+        } else X = dense_to_ldlt(ctx, n, sx.X, ctf);
+        if (steps_on)
+            std::fprintf(stderr, "[final X, us] %.0f (%s)\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - f0).count(),
+                         ctx->final_x_lazy ? "kept dense: factored on demand" : "dense_to_ldlt");
+    }
     if (!save_state) out.X.push_back(X);
     out.nfactor = cache.nfactor;
     if (wall_on) {
@@ -2042,6 +2056,20 @@ GdreResult gdre_solve(Ctx* ctx, const GdreProblem& prob, int order, double dt, b
         std::fprintf(stderr, "[wall, ms] first step %.2f | steps 2..%d %.2f | final form %.2f\n", ms(w_begin, w_first), nsteps, ms(w_first, w_loop), ms(w_loop, w_end));
     }
     return out;
+}
+
+LDLtP gdre_result_x(GdreResult& r, int i) {
+    DRE_REQUIRE(i >= 0 && i < (int)r.X.size(), "X index out of range");
+    if (!r.final_x || i + 1 != (int)r.X.size()) return r.X[(size_t)i];
+    FinalXDense& f = *r.final_x;
+    std::lock_guard<std::mutex> lk(f.mu);
+    if (!r.X.back()) {
+        DRE_HIP(hipSetDevice(f.ctx->device));
+        r.X.back() = dense_to_ldlt(f.ctx, f.Xd.rows, f.Xd, f.ctf);
+        f.conversions++;
+        f.Xd = Mat();
+    }
+    return r.X.back();
 }
 
 

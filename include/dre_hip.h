@@ -362,7 +362,11 @@ int dre_gdre_result_K_device(dre_ctx* ctx, const dre_gdre_result* r, double* K_d
 /* the same nt blocks written to HOST memory (nt * m * n doubles): one export launch and one copy instead of nt calls of dre_gdre_result_K
  * (sol.K of DRESolution, src/riccati/lowrank_ros1.jl:65) */
 int dre_gdre_result_K_all(dre_ctx* ctx, const dre_gdre_result* r, double* K_host);
-int dre_gdre_result_X(const dre_gdre_result* r, int i, dre_ldlt** X);   /* shares the factors (sol.X[1] === prob.X0) */
+/* shares the factors (sol.X[1] === prob.X0).  A Ros1 run without save_state that ends on the dense-X path keeps its last X as a dense matrix
+ * (context option final_x_lazy, default 1): the first call for that X runs the conversion to LDL' on the stream of the context the solve ran
+ * on and caches the factors in the result; later calls return the same factors.  The result therefore refers to its context: free every
+ * result (dre_gdre_result_free) before the context it was made on (dre_ctx_destroy).  On failure the message goes to that context. */
+int dre_gdre_result_X(const dre_gdre_result* r, int i, dre_ldlt** X);
 /* per Lyapunov solve j: iinfo [0]=iters [1]=converged [2]=warnings [3]=rhs columns; dinfo [0]=res_norm [1]=abstol */
 int dre_gdre_result_gale(const dre_gdre_result* r, int j, int64_t* iinfo, double* dinfo);
 /* per-iteration record of Lyapunov solve j for the observer replay (observe_gale_step! / observe_gale_metadata!, src/lyapunov/adi.jl:65,103,119,192):
