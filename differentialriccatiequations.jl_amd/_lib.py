@@ -49,6 +49,30 @@ SHIFT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_
 BLOCK_SOLVER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
+class GemmViewC(C.Structure):
+    """dre_gemm_view: rows x cols, column-major with leading dimension ld, `offset` elements into the dre_dense `buf`."""
+    _fields_ = [("buf", C.c_void_p), ("offset", C.c_int64), ("ld", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
+class GemmProductC(C.Structure):
+    _fields_ = [("A", GemmViewC), ("B", GemmViewC), ("C", GemmViewC), ("copy_dst", GemmViewC), ("alpha", C.c_double)]
+
+
+class GemmProbeOptionsC(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32),
+        ("stride_a", C.c_int64), ("stride_b", C.c_int64), ("stride_c", C.c_int64),
+        ("member_on", C.POINTER(C.c_int32)),
+        ("coef", C.POINTER(C.c_double)), ("coef_stride", C.c_int64),
+        ("rowmap", C.POINTER(C.c_int32)),
+        ("cz", C.c_int64),
+        ("nprod", C.c_int32), ("prod", C.POINTER(GemmProductC)),
+        ("use_done", C.c_int32), ("done", C.c_int32),
+        ("use_count", C.c_int32), ("iters", C.c_int32), ("base", C.c_int32), ("nmax", C.c_int32), ("per", C.c_int32),
+        ("tile_sumsq", C.c_void_p),
+    ]
+
+
 _vp = C.c_void_p
 _pvp = C.POINTER(C.c_void_p)
 _pd = C.POINTER(C.c_double)
@@ -84,6 +108,8 @@ PROTOTYPES = {
     "dre_pencil_get_array": (C.c_int, [_vp, C.c_char_p, _pi64, C.c_int64, _pi64]),
     "dre_pencil_get_values": (C.c_int, [_vp, C.c_int, _pd, C.c_int64]),
     "dre_gemm": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, _vp, C.c_double, _vp]),
+    "dre_gemm_probe": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(GemmViewC), C.POINTER(GemmViewC), C.c_double, C.POINTER(GemmViewC),
+                                 C.POINTER(GemmProbeOptionsC), _pint]),
     "dre_spmm": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, C.c_double, _vp]),
     "dre_orthf": (C.c_int, [_vp, _vp, _pvp, _pvp]),
     "dre_sym_eig": (C.c_int, [_vp, _vp, C.c_double, _pvp, _pvp]),

@@ -15,6 +15,7 @@
 #include "dense_sign.hpp"
 #include "dense_sign_lr.hpp"
 #include "engine.hpp"
+#include "gemm_probe_check.hpp"
 #include "hostla.hpp"
 #include "profiling.hpp"
 #include "sym_jacobi.hpp"
@@ -79,10 +80,10 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 107; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 108; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
-                                        // dre_gdre_result_step_stats, DRE_ERR_STEP)
+                                        // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -452,6 +453,168 @@ static Mat to_user_order(Ctx* c, const dre_pencil* pen, const Mat& src) {
 // ---- kernels -----------------------------------------------------------------------------------
 int dre_gemm(dre_ctx* ctx, int tA, int tB, double alpha, const dre_dense* A, const dre_dense* B, double beta, dre_dense* C) {
     return guarded(ctx, [&] { gemm(&ctx->c, tA != 0, tB != 0, alpha, A->m, B->m, beta, C->m); });
+}
+// ---- dre_gemm_probe: the internal GEMM entry points one by one (test and diagnostic surface) ------------------------------------------
+namespace {
+int64_t probe_cap(const dre_dense* d) {          // elements of the buffer from the matrix's first element on
+    if (!d || !d->m.buf || !d->m.p) return -1;
+    const char* base = (const char*)d->m.buf->p;
+    const char* p = (const char*)d->m.p;
+    if (p < base || (size_t)(p - base) > d->m.buf->bytes) return -1;
+    return (int64_t)((d->m.buf->bytes - (size_t)(p - base)) / sizeof(double));
+}
+void probe_check(const dre_gemm_view* v, const char* what, int64_t count = 1, int64_t stride = 0) {
+    DRE_REQUIRE(v && v->buf, std::string("dre_gemm_probe: missing view ") + what);
+    DRE_REQUIRE(probe_view_fits(probe_cap(v->buf), v->offset, v->ld, v->rows, v->cols, count, stride),
+                std::string("dre_gemm_probe: view ") + what + " does not lie inside its buffer");
+}
+double* probe_ptr(const dre_gemm_view* v) { return v->buf->m.p + v->offset; }
+void probe_mat(const dre_gemm_view* v, Mat& m) { m.buf = v->buf->m.buf; m.p = probe_ptr(v); m.rows = v->rows; m.cols = v->cols; m.ld = v->ld; }
+}  // namespace
+
+int dre_gemm_probe(dre_ctx* ctx, int kind, int transA, int transB, double alpha, const dre_gemm_view* A, const dre_gemm_view* B, double beta,
+                   const dre_gemm_view* C, const dre_gemm_probe_options* opt, int* splits_out) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        const dre_gemm_probe_options none = {};
+        const dre_gemm_probe_options& o = opt ? *opt : none;
+        const bool tA = transA != 0, tB = transB != 0;
+        DRE_REQUIRE(kind >= DRE_PROBE_GEMM && kind <= DRE_PROBE_GEMM_SYM, "dre_gemm_probe: unknown kind");
+        const int batch = o.batch > 0 ? o.batch : 1;
+        DRE_REQUIRE(o.batch >= 0 && batch <= 65535, "dre_gemm_probe: batch");
+        const bool stacked = kind == DRE_PROBE_GEMM_STRIDED || kind == DRE_PROBE_GEMM_Z;
+        // what each kind can take
+        const bool takes_done = kind == DRE_PROBE_GEMM || kind == DRE_PROBE_GEMM_THIN || kind == DRE_PROBE_GEMM_ROWS || kind == DRE_PROBE_GEMM_Z;
+        const bool takes_count = kind == DRE_PROBE_GEMM_BATCHED || kind == DRE_PROBE_GEMM_ROWS || kind == DRE_PROBE_GEMM_SYM;
+        DRE_REQUIRE(!o.use_done || takes_done, "dre_gemm_probe: this kind takes no done flag");
+        DRE_REQUIRE(!o.use_count || takes_count, "dre_gemm_probe: this kind takes no device-side count");
+        DRE_REQUIRE(!o.tile_sumsq || kind == DRE_PROBE_GEMM, "dre_gemm_probe: tile_sumsq belongs to gemm");
+        DRE_REQUIRE((!o.member_on && !o.coef) || kind == DRE_PROBE_GEMM_STRIDED, "dre_gemm_probe: member_on and coef belong to gemm_strided");
+        DRE_REQUIRE(!o.rowmap || kind == DRE_PROBE_GEMM_ROWS || kind == DRE_PROBE_GEMM_Z, "dre_gemm_probe: rowmap belongs to the reduce kinds");
+        DRE_REQUIRE(stacked || o.batch <= 1, "dre_gemm_probe: this kind takes no batch");
+        DRE_REQUIRE((o.nprod == 0 && !o.prod) || kind == DRE_PROBE_GEMM_BATCHED, "dre_gemm_probe: products belong to gemm_batched");
+        DRE_REQUIRE(!o.use_count || (o.per >= 1 && o.nmax >= 0), "dre_gemm_probe: count needs per >= 1, nmax >= 0");
+
+        int M = 0, N = 0, K = 0;
+        if (kind != DRE_PROBE_GEMM_BATCHED) {
+            const int64_t sa = stacked ? o.stride_a : 0, sb = stacked ? o.stride_b : 0;
+            const int64_t sc = kind == DRE_PROBE_GEMM_STRIDED ? o.stride_c : (kind == DRE_PROBE_GEMM_Z ? o.cz : 0);
+            probe_check(A, "A", batch, sa);
+            probe_check(B, "B", batch, sb);
+            probe_check(C, "C", batch, sc);
+            if (kind == DRE_PROBE_GEMM_SYM) {
+                M = N = C->rows; K = A->cols;
+                DRE_REQUIRE(C->cols == M && A->rows == M && B->rows == M && B->cols == K && !tA && !tB, "dre_gemm_probe: gemm_sym_update takes A, B of n x K and C of n x n");
+            } else {
+                M = tA ? A->cols : A->rows; K = tA ? A->rows : A->cols; N = tB ? B->rows : B->cols;
+                DRE_REQUIRE((tB ? B->cols : B->rows) == K, "dre_gemm_probe: inner dimensions differ");
+                DRE_REQUIRE(C->cols == N, "dre_gemm_probe: C has the wrong number of columns");
+                const bool mapped = kind == DRE_PROBE_GEMM_ROWS || (kind == DRE_PROBE_GEMM_Z && o.rowmap);
+                DRE_REQUIRE(mapped ? C->rows >= M : C->rows == M, "dre_gemm_probe: C has the wrong number of rows");
+                DRE_REQUIRE(kind != DRE_PROBE_GEMM_ROWS || o.rowmap, "dre_gemm_probe: gemm_reduce_rows needs a rowmap");
+                DRE_REQUIRE(kind != DRE_PROBE_GEMM_THIN || !tB, "dre_gemm_probe: gemm_thin has no transposed B");
+            }
+            if (o.rowmap) for (int i = 0; i < M; ++i) DRE_REQUIRE(o.rowmap[i] >= 0 && o.rowmap[i] < C->rows, "dre_gemm_probe: rowmap entry outside C");
+        }
+
+        // device-side control blocks
+        DevArr<AdiState> st;
+        const AdiState* stp = nullptr;
+        if (o.use_done || o.use_count) {
+            std::vector<AdiState> h(1);
+            std::memset(h.data(), 0, sizeof(AdiState));
+            h[0].done = o.use_done ? o.done : 0; h[0].iters = o.iters;
+            st = DevArr<AdiState>(c, 1); st.upload(c, h);
+            stp = st.p;
+        }
+        const AdiState* done_st = o.use_done ? stp : nullptr;
+        DevCount dc;
+        if (o.use_count) { dc.st = stp; dc.base = o.base; dc.nmax = o.nmax; dc.per = o.per; }
+        DevArr<int> rowmap;
+        if (o.rowmap && M > 0) { rowmap = DevArr<int>(c, (size_t)M); rowmap.upload(c, o.rowmap, (size_t)M); }
+        int splits = 1;
+
+        switch (kind) {
+        case DRE_PROBE_GEMM: {
+            double* ss = nullptr;
+            if (o.tile_sumsq) {
+                DRE_REQUIRE(probe_cap(o.tile_sumsq) >= (int64_t)gemm_num_tiles(M, N), "dre_gemm_probe: tile_sumsq is too small");
+                ss = o.tile_sumsq->m.p;
+            }
+            if (M > 0 && N > 0 && !(ss && K > 64)) splits = gemm_split_plan(c, ceil_div(M, 64) * ceil_div(N, 64), K);
+            gemm(c, tA, tB, M, N, K, alpha, probe_ptr(A), A->ld, probe_ptr(B), B->ld, beta, probe_ptr(C), C->ld, done_st, "gemm_probe", ss);
+            break;
+        }
+        case DRE_PROBE_GEMM_THIN:
+            gemm_thin(c, tA, M, N, K, alpha, probe_ptr(A), A->ld, probe_ptr(B), B->ld, beta, probe_ptr(C), C->ld, done_st, "gemm_probe");
+            break;
+        case DRE_PROBE_GEMM_STRIDED: {
+            DevArr<BatchCtl> ctl;
+            BatchMask mask;
+            if (o.member_on) {
+                std::vector<BatchCtl> h((size_t)batch);
+                std::memset(h.data(), 0, h.size() * sizeof(BatchCtl));
+                for (int b = 0; b < batch; ++b) h[(size_t)b].fail = o.member_on[b] ? 0 : DRE_ERR_SINGULAR;
+                ctl = DevArr<BatchCtl>(c, (size_t)batch); ctl.upload(c, h);
+                mask.ctl = ctl.p;
+            }
+            DevArr<double> coef;
+            if (o.coef) {
+                DRE_REQUIRE(o.coef_stride >= 2 && o.coef_stride <= 4096, "dre_gemm_probe: coef_stride");
+                coef = DevArr<double>(c, (size_t)batch * (size_t)o.coef_stride);
+                coef.upload(c, o.coef, (size_t)batch * (size_t)o.coef_stride);
+            }
+            gemm_strided(c, batch, tA, tB, M, N, K, alpha, probe_ptr(A), A->ld, (size_t)o.stride_a, probe_ptr(B), B->ld, (size_t)o.stride_b, beta, probe_ptr(C),
+                         C->ld, (size_t)o.stride_c, mask, "gemm_probe", o.coef ? coef.p : nullptr, o.coef ? (size_t)o.coef_stride : 0);
+            c->sync();          // (the uploaded blocks live until here)
+            break;
+        }
+        case DRE_PROBE_GEMM_BATCHED: {
+            DRE_REQUIRE(o.nprod >= 0 && o.nprod <= 65535 && (o.nprod == 0 || o.prod), "dre_gemm_probe: product list");
+            std::vector<GemmBatchDesc> descs;
+            for (int i = 0; i < o.nprod; ++i) {
+                const dre_gemm_product& p = o.prod[i];
+                probe_check(&p.A, "A of a product"); probe_check(&p.B, "B of a product"); probe_check(&p.C, "C of a product");
+                DRE_REQUIRE(p.A.cols == p.B.rows && p.C.rows == p.A.rows && p.C.cols == p.B.cols, "dre_gemm_probe: shapes of a product");
+                GemmBatchDesc d;
+                d.A = probe_ptr(&p.A); d.B = probe_ptr(&p.B); d.C = probe_ptr(&p.C); d.copy_dst = nullptr; d.alpha = p.alpha;
+                d.M = p.A.rows; d.N = p.B.cols; d.K = p.A.cols; d.lda = p.A.ld; d.ldb = p.B.ld; d.ldc = p.C.ld; d.ldcopy = 0;
+                if (p.copy_dst.buf) {
+                    probe_check(&p.copy_dst, "copy_dst of a product");
+                    DRE_REQUIRE(p.copy_dst.rows == d.M && p.copy_dst.cols == d.K, "dre_gemm_probe: copy_dst has the shape of A");
+                    d.copy_dst = probe_ptr(&p.copy_dst); d.ldcopy = p.copy_dst.ld;
+                }
+                descs.push_back(d);
+            }
+            gemm_batched(c, descs, "gemm_probe", dc);
+            break;
+        }
+        case DRE_PROBE_GEMM_ROWS: {
+            BufP pb = gemm_partials(c, tA, tB, M, N, K, probe_ptr(A), A->ld, probe_ptr(B), B->ld, &splits, done_st, "gemm_probe", dc);
+            gemm_reduce_rows(c, M, N, splits, (const double*)pb->p, rowmap.p, probe_ptr(C), C->ld, done_st);
+            break;
+        }
+        case DRE_PROBE_GEMM_Z: {
+            GemmZ zb;
+            for (int z = 0; z < MF_ZMAX; ++z) {       // (a batch beyond MF_ZMAX is for gemm_partials_z to refuse)
+                const int zz = std::min(z, batch - 1);
+                zb.A[z] = probe_ptr(A) + (size_t)zz * (size_t)o.stride_a; zb.B[z] = probe_ptr(B) + (size_t)zz * (size_t)o.stride_b;
+            }
+            BufP pb = gemm_partials_z(c, tA, tB, M, N, K, zb, batch, A->ld, B->ld, &splits, done_st, "gemm_probe");
+            gemm_reduce_z(c, M, N, splits, batch, (const double*)pb->p, o.rowmap ? rowmap.p : nullptr, probe_ptr(C), C->ld, (long)o.cz, done_st);
+            break;
+        }
+        case DRE_PROBE_GEMM_SYM: {
+            Mat Am, Bm, Xm;
+            probe_mat(A, Am); probe_mat(B, Bm); probe_mat(C, Xm);
+            if (M > 0 && K > 0) splits = gemm_split_plan(c, ceil_div(M, 64) * ceil_div(M, 64), K);
+            gemm_sym_update(c, Am, Bm, Xm, "gemm_probe", dc);
+            break;
+        }
+        }
+        c->sync();
+        if (splits_out) *splits_out = splits;
+    });
 }
 int dre_spmm(dre_ctx* ctx, const dre_pencil* p, int which, double alpha, const dre_dense* X, double beta, dre_dense* Y) {
     return guarded(ctx, [&] {

@@ -38,6 +38,9 @@ void gemm(Ctx* ctx, bool transA, bool transB, int M, int N, int K, double alpha,
 // tile_sumsq (optional, K <= 64 only): receives one partial sum of squares of the updated C per 64 x 64 tile
 // (gemm_num_tiles(M, N) entries) — the band reduction's termination norm comes out of the update GEMM's epilogue.
 inline int gemm_num_tiles(int M, int N) { return ((M + 63) / 64) * ((N + 63) / 64); }
+// split-K plan of gemm / gemm_partials / gemm_partials_z for `tiles` 64 x 64 output tiles (times the z-batch) and inner dimension K: the number
+// of slabs; *kchunk_out (optional) the K range of one slab
+int gemm_split_plan(const Ctx* ctx, int tiles, int K, int* kchunk_out = nullptr);
 // C = alpha op(A) B + beta C for a SMALL C (a few dozen 16 x 16 tiles) and a long inner dimension, in one launch (no split-K slabs)
 void gemm_thin(Ctx* ctx, bool tA, int M, int N, int K, double alpha, const double* A, int lda, const double* B, int ldb, double beta, double* C, int ldc,
                const AdiState* st = nullptr, const char* tag = "gemm");

@@ -1,6 +1,7 @@
 // Dense f64 GEMM family for gfx950 (v_mfma_f64_16x16x4_f64): split-K GEMM, batched and z-batched products, the thin single-launch form.
 #include "dense_batch.hpp"
 #include "dense_device.hpp"
+#include "gemm_tilemap.hpp"
 #include <functional>
 #include "profiling.hpp"
 #include <atomic>
@@ -151,25 +152,15 @@ __device__ __forceinline__ void gemm_tile(int M, int N, int K, double alpha, con
 // 45.1 TFLOP/s at 4096^3 against 47.9 for this kernel, 22-30 against 29-34 on the skinny passes of the randomized compression
 // (tools/gemm_probe.py).  With one wave per SIMD its global round trips are not covered; the 64 x 64 tiles keep four workgroups per CU.
 // It was removed again.)
-// Workgroup -> output tile.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one; observed, a speed matter only), each
-// with its own L2: in launch order the tiles that share an operand panel sit on DIFFERENT L2s and every XCD streams the large operand for
-// itself (the 5 row tiles of a 304 x 6400 x 20209 sketch product: the 1 GB factor crosses the fabric five times).  swz != 0: every XCD takes
-// a CONTIGUOUS chunk of the tile list (bijective remap for any grid size), and the list runs fastest along the dimension with FEWER tiles,
-// so the tiles that are resident together on one XCD share the panels of the large operand; splits slowest (they share nothing).
+// Workgroup -> output tile: gemm_tile_map (gemm_tilemap.hpp, where the XCD-aware order is described) on this workgroup's grid and index.
 __device__ __forceinline__ void xcd_tile(int swz, int& bx, int& by, int& bz) {
-    if (!swz) { bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z; return; }
-    const unsigned gx = gridDim.x, gy = gridDim.y, per = gx * gy, T = per * gridDim.z;
-    unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const unsigned xcd = L & 7u, slot = L >> 3, q = T >> 3, r = T & 7u;
-    L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    const unsigned z = L / per, rem = L - z * per;
-    bz = (int)z;
-    if (gx <= gy) { const unsigned y = rem / gx; by = (int)y; bx = (int)(rem - y * gx); }
-    else { const unsigned x = rem / gy; bx = (int)x; by = (int)(rem - x * gy); }
+    gemm_tile_map(swz, gridDim.x, gridDim.y, gridDim.z, blockIdx.x, blockIdx.y, blockIdx.z, bx, by, bz);
 }
 // Used where the larger operand does not fit the 256 MB Infinity Cache (measured, tools/gemm_probe.py: 304 x 6400 x 20209 TN 39.1 -> 42.4 TFLOP/s,
 // 20209 x 304 x 6400 NT 35.8 -> 39.2, 20209 x 304 x 3500 NT 34.3 -> 38.1; cache-resident operands: within +-2 %, 2976 x 112 x 2976 7 % slower).
+// gemm_swizzle = 2 (diagnostic): every launch of k_gemm takes the swizzled order, whatever its size.
 static inline int gemm_swizzle(const Ctx* ctx, int M, int N, int K) {
+    if (ctx->gemm_swizzle == 2) return 1;
     return ctx->gemm_swizzle != 0 && 8.0 * (double)K * (double)std::max(M, N) > 256.0 * 1048576.0 ? 1 : 0;
 }
 template <bool TA, bool TB>
@@ -328,6 +319,19 @@ __global__ void k_gemm_reduce(int M, int N, int splits, double alpha, const doub
     *c = (beta == 0.0) ? alpha * s : alpha * s + beta * (*c);
 }
 
+// These GEMMs are latency bound (one memory round trip per K-tile), so K is split until the grid fills the chip or every block is down to
+// two K-tiles.  One plan for gemm, gemm_partials and gemm_partials_z: the number of slabs and the K range of each (a multiple of GB_K).
+int gemm_split_plan(const Ctx* ctx, int tiles, int K, int* kchunk_out) {
+    int splits = 1;
+    if (K > 2 * GB_K) {
+        int want = ceil_div(2 * ctx->num_cus, tiles);
+        splits = std::max(1, std::min(want, K / (2 * GB_K)));
+    }
+    const int kchunk = K > 0 ? ceil_div(ceil_div(K, splits), GB_K) * GB_K : GB_K;
+    if (kchunk_out) *kchunk_out = kchunk;
+    return K > 0 ? ceil_div(K, kchunk) : 1;
+}
+
 // (A tall-skinny  C = alpha A'B  kernel — every wave walks groups of 16 rows, up to 4 x 4 accumulator tiles, one partial per wave, no LDS — was
 // built in round 3 for the Gram matrices / U'W / V'Z products and measured NOT faster than the split-K GEMM below: Gram of a 5177 x 64 factor
 // 21 us with either.  Removed in round 4; CHANGELOG.)
@@ -336,16 +340,10 @@ void gemm(Ctx* ctx, bool tA, bool tB, int M, int N, int K, double alpha, const d
     if (M <= 0 || N <= 0) return;
     TimedScope ts(ctx, tag, 8.0 * ((double)M * K + (double)K * N + 2.0 * M * N), 2.0 * M * N * (double)K);
     const int tm = ceil_div(M, GB_M), tn = ceil_div(N, GB_N);
-    // These GEMMs are latency bound (one memory round trip per K-tile), so K is split until the grid fills the
-    // chip or every block is down to two K-tiles; partial slabs are reduced in a fixed order (deterministic).
+    // split-K (gemm_split_plan); the partial slabs are reduced in a fixed order (deterministic)
     DRE_REQUIRE(!tile_sumsq || K <= 2 * GB_K, "gemm: tile_sumsq needs an unsplit K");
-    int splits = 1;
-    if (K > 2 * GB_K) {
-        int want = ceil_div(2 * ctx->num_cus, tm * tn);
-        splits = std::max(1, std::min(want, K / (2 * GB_K)));
-    }
-    int kchunk = K > 0 ? ceil_div(ceil_div(K, splits), GB_K) * GB_K : GB_K;
-    splits = K > 0 ? ceil_div(K, kchunk) : 1;
+    int kchunk = GB_K;
+    const int splits = gemm_split_plan(ctx, tm * tn, K, &kchunk);
     dim3 grid(tm, tn, splits), block(256);
     BufP pb;
     double* partial = nullptr;
@@ -418,13 +416,8 @@ BufP gemm_partials(Ctx* ctx, bool tA, bool tB, int M, int N, int K, const double
                    int* splits_out, const AdiState* st, const char* tag, DevCount dc) {
     TimedScope ts(ctx, tag, 8.0 * ((double)M * K + (double)K * N + 2.0 * M * N), 2.0 * M * N * (double)K);
     const int tm = ceil_div(M, GB_M), tn = ceil_div(N, GB_N);
-    int splits = 1;
-    if (K > 2 * GB_K) {
-        int want = ceil_div(2 * ctx->num_cus, tm * tn);
-        splits = std::max(1, std::min(want, K / (2 * GB_K)));
-    }
-    int kchunk = K > 0 ? ceil_div(ceil_div(K, splits), GB_K) * GB_K : GB_K;
-    splits = K > 0 ? ceil_div(K, kchunk) : 1;
+    int kchunk = GB_K;
+    const int splits = gemm_split_plan(ctx, tm * tn, K, &kchunk);
     dim3 grid(tm, tn, splits), block(256);
     auto pb = std::make_shared<Buf>(ctx, (size_t)splits * M * N * sizeof(double));
     double* partial = (double*)pb->p;
@@ -456,13 +449,8 @@ BufP gemm_partials_z(Ctx* ctx, bool tA, bool tB, int M, int N, int K, const Gemm
     DRE_REQUIRE(nz >= 1 && nz <= MF_ZMAX, "gemm_partials_z: batch size");
     TimedScope ts(ctx, tag, 8.0 * nz * ((double)M * K + (double)K * N + 2.0 * M * N), 2.0 * nz * M * N * (double)K);
     const int tm = ceil_div(M, GB_M), tn = ceil_div(N, GB_N);
-    int splits = 1;
-    if (K > 2 * GB_K) {
-        int want = ceil_div(2 * ctx->num_cus, tm * tn * nz);
-        splits = std::max(1, std::min(want, K / (2 * GB_K)));
-    }
-    int kchunk = K > 0 ? ceil_div(ceil_div(K, splits), GB_K) * GB_K : GB_K;
-    splits = K > 0 ? ceil_div(K, kchunk) : 1;
+    int kchunk = GB_K;
+    const int splits = gemm_split_plan(ctx, tm * tn * nz, K, &kchunk);
     dim3 grid(tm, tn, splits * nz), block(256);
     auto pb = std::make_shared<Buf>(ctx, (size_t)splits * nz * M * N * sizeof(double));
     double* partial = (double*)pb->p;

@@ -100,7 +100,9 @@ int dre_ctx_info(dre_ctx* ctx, int64_t* info /* [0]=CUs [1]=pool bytes */);
  *                               tournament panel at every n.  Other values are DRE_ERR_INVALID
  *   "sym_eig_method"            the symmetric eigensolver behind the rank-revealing compressions (FactoredSign, compress!, the projection's Gram
  *                               eigenproblem).  0 (default) Householder tridiagonalisation + implicit QL (dre_sym_eig); 1 block Jacobi on the
- *                               whole device (dre_sym_eig_jacobi).  Other values are DRE_ERR_INVALID */
+ *                               whole device (dre_sym_eig_jacobi).  Other values are DRE_ERR_INVALID
+ *   "gemm_swizzle"              workgroup -> tile order of the split-K GEMM.  1 (default): XCD-aware where the larger operand does not fit the
+ *                               Infinity Cache; 0: launch order; 2 (diagnostic): XCD-aware in every launch, whatever its size.  Same results */
 int dre_ctx_set_option(dre_ctx* ctx, const char* name, double value);
 /* the current value of an option of dre_ctx_set_option (tests snapshot and restore what they change; no reference counterpart: the reference's
  * tunables are keyword arguments) */
@@ -510,6 +512,40 @@ int dre_sign_solve_lr(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_d
  * iinfo / dinfo as there.  The three n x n work matrices of this replay are allocated by the first call. */
 int dre_sign_solve_dense(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo);
 int dre_sign_free(dre_ctx* ctx, dre_sign* s);
+
+/* ---- test and diagnostic surface: the internal GEMM entry points one by one (dre_version >= 108) ----------------------------------------
+ * dre_gemm_probe calls ONE entry point of the f64 MFMA GEMM family with arguments a public caller cannot form: operands that are views into
+ * larger buffers, member masks, device-side counts, the `done` flag of an ADI control block.  It has no wrapper beyond the ctypes prototype
+ * and no counterpart in the reference; tests/test_gpu_gemm_family.py is its user.
+ * A view is rows x cols, column-major with leading dimension ld, beginning `offset` elements into the buffer `buf`.  Before any launch every
+ * view (every member of a stack, every product of a list) is checked to lie inside its buffer, every rowmap entry to lie inside C's rows, and
+ * the shapes to agree; DRE_ERR_INVALID otherwise, and for whatever the entry point itself refuses.  The call synchronises. */
+typedef struct dre_gemm_view { const dre_dense* buf; int64_t offset; int32_t ld, rows, cols; } dre_gemm_view;
+typedef struct dre_gemm_product { dre_gemm_view A, B, C, copy_dst; double alpha; } dre_gemm_product;   /* C = alpha A B; copy_dst.buf NULL: no copy, else
+                                                                                                          M x K with ld = ldcopy */
+#define DRE_PROBE_GEMM 0            /* gemm: C = alpha op(A) op(B) + beta C; done, tile_sumsq */
+#define DRE_PROBE_GEMM_THIN 1       /* gemm_thin: C = alpha op(A) B + beta C; done */
+#define DRE_PROBE_GEMM_STRIDED 2    /* gemm_strided: batch members at offset + b * stride_*; member_on, coef */
+#define DRE_PROBE_GEMM_BATCHED 3    /* gemm_batched on prod[0 .. nprod): the arguments A, B, C, alpha, beta are not read; count */
+#define DRE_PROBE_GEMM_ROWS 4       /* gemm_partials + gemm_reduce_rows: C[rowmap[i], :] = (op(A) op(B))[i, :]; rowmap needed; done, count */
+#define DRE_PROBE_GEMM_Z 5          /* gemm_partials_z + gemm_reduce_z: batch = nz products A_z, B_z at stride_a, stride_b into C + z * cz; rowmap optional; done */
+#define DRE_PROBE_GEMM_SYM 6        /* gemm_sym_update: C <- sym(C + A B') for A, B of n x K; count */
+typedef struct dre_gemm_probe_options {
+    int32_t batch;                          /* members (strided) or nz (z); 0 counts as 1 */
+    int64_t stride_a, stride_b, stride_c;   /* member strides in elements */
+    const int32_t* member_on;               /* strided: batch entries, 0 = the member is masked out (a device BatchCtl with `fail` set); NULL: all on */
+    const double* coef; int64_t coef_stride;/* strided: member b takes alpha = coef[b * coef_stride], beta = coef[b * coef_stride + 1] (uploaded); NULL: the arguments */
+    const int32_t* rowmap;                  /* rows, z: M entries in [0, C.rows) (uploaded) */
+    int64_t cz;                             /* z: member stride of C */
+    int32_t nprod; const dre_gemm_product* prod;   /* batched */
+    int32_t use_done, done;                 /* use_done != 0: a device AdiState with this `done` goes to every kernel that takes one */
+    int32_t use_count, iters, base, nmax, per;     /* use_count != 0: DevCount {AdiState with this `iters`, base, nmax, per} */
+    dre_dense* tile_sumsq;                  /* gemm: receives one sum of squares per 64 x 64 tile, entry bx + ceil(M / 64) * by (at least that many elements); NULL: none */
+} dre_gemm_probe_options;
+/* opt may be NULL (all zero).  *splits (may be NULL) receives the split-K count the host chose (1 for the kinds without one).  An option the
+ * selected kind cannot take is DRE_ERR_INVALID. */
+int dre_gemm_probe(dre_ctx* ctx, int kind, int transA, int transB, double alpha, const dre_gemm_view* A, const dre_gemm_view* B, double beta,
+                   const dre_gemm_view* C, const dre_gemm_probe_options* opt, int* splits);
 
 /* ---- host helpers exposed for CPU tests of the Projection shift pipeline ---------------------- */
 int dre_host_eigvals(int n, const double* A, double* wr, double* wi);

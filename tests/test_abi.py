@@ -68,3 +68,20 @@ def test_adi_options_struct_layout_matches_the_header(tmp_path):
     body = jl[jl.index("struct AdiOptionsC"):]
     body = body[:body.index("\nend")]
     assert re.findall(r"^\s+([a-z_]+)::", body, flags=re.M) == [f[0] for f in T._fields_]
+
+
+def test_gemm_probe_struct_layouts_match_the_header(tmp_path):
+    """`dre_gemm_view`, `dre_gemm_product` and `dre_gemm_probe_options` cross the boundary BY LAYOUT (ctypes `GemmViewC`, `GemmProductC`,
+    `GemmProbeOptionsC`): sizes and the offset of every field are compared with what the C compiler makes of include/dre_hip.h."""
+    import ctypes as C
+    import subprocess
+    import dre_amd as D
+    pairs = (("dre_gemm_view", D._lib.GemmViewC), ("dre_gemm_product", D._lib.GemmProductC), ("dre_gemm_probe_options", D._lib.GemmProbeOptionsC))
+    body = "".join(f'printf("%zu ", sizeof({c}));' + "".join(f'printf("%zu ", offsetof({c}, {f[0]}));' for f in T._fields_) for c, T in pairs)
+    src = tmp_path / "probe_layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dre_hip.h"\nint main(void) { ' + body + ' return 0; }\n')
+    exe = tmp_path / "probe_layout"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    want = [v for _, T in pairs for v in [C.sizeof(T)] + [getattr(T, f[0]).offset for f in T._fields_]]
+    assert got == want

@@ -18,7 +18,7 @@ def _prob(n=6, X0=None, tspan=(1.0, 0.0)):
 
 def test_abi_level_symbols_and_error_code():
     lib = D._lib.load()
-    assert lib.dre_version() == 107
+    assert lib.dre_version() >= 107          # the version that brought the adaptive entry points (include/dre_hip.h); later ones add to it
     for name, nargs in (("dre_dense_gdre_solve_adaptive", 22), ("dre_gdre_result_step_stats", 3)):
         assert hasattr(lib, name)
         assert len(D._lib.PROTOTYPES[name][1]) == nargs
