@@ -1662,9 +1662,16 @@ class SignFactorization:
     def close(self):
         self._fin()
 
-    def solve_lr(self, G, S, rtol=None, max_width=256, max_refine=1, download=True):
+    def _entry(self, name, transposed):
+        if not isinstance(transposed, (bool, np.bool_)):
+            raise TypeError(f"transposed must be a bool, not {type(transposed).__name__}; nothing was run on the device")
+        return getattr(self.ctx.lib, name + "_t" if transposed else name)
+
+    def solve_lr(self, G, S, rtol=None, max_width=256, max_refine=1, download=True, *, transposed=False):
         """F'XE + E'XF = -G S G'  ->  (L, D, info) with X = L D L', D diagonal.  G, S: ndarrays or `DenseMatrix` objects on the device;
-        download=False leaves L and D there (`DenseMatrix`)."""
+        download=False leaves L and D there (`DenseMatrix`).  transposed=True solves the dual equation F Y E' + E Y F' = -G S G' of the same
+        pencil from the same kept factorisation (`dre_sign_solve_lr_t`)."""
+        fn = self._entry("dre_sign_solve_lr", transposed)
         rtol = self.n * float(np.finfo(float).eps) if rtol is None else float(rtol)
         if isinstance(G, dev.DenseMatrix):
             Gd, Sd = G, S
@@ -1674,19 +1681,21 @@ class SignFactorization:
             Gd, Sd = self.ctx.upload(G), self.ctx.upload(np.asarray(S, dtype=float).reshape(r, r))
         lp, dp = C.c_void_p(), C.c_void_p()
         ii, dd = (C.c_int64 * 4)(), (C.c_double * 2)()
-        self.ctx.chk(self.ctx.lib.dre_sign_solve_lr(self.ctx.ptr, self.ptr, Gd.ptr, Sd.ptr, rtol, int(max_width), int(max_refine), C.byref(lp), C.byref(dp), ii, dd))
+        self.ctx.chk(fn(self.ctx.ptr, self.ptr, Gd.ptr, Sd.ptr, rtol, int(max_width), int(max_refine), C.byref(lp), C.byref(dp), ii, dd))
         L, Dm = dev.DenseMatrix(self.ctx, lp), dev.DenseMatrix(self.ctx, dp)
         if download:
             L, Dm = L.numpy(), Dm.numpy()
         return L, Dm, dict(iters=self.iters, rank=int(ii[0]), peak_width=int(ii[1]), compressions=int(ii[2]), refinements=int(ii[3]),
                            res0=float(dd[0]), res=float(dd[1]))
 
-    def solve_dense(self, R, max_refine=2, download=True):
-        """F'XE + E'XF = -R for a dense symmetric R (the `MatrixSign` replay on the kept factorisation) -> (X, info)"""
+    def solve_dense(self, R, max_refine=2, download=True, *, transposed=False):
+        """F'XE + E'XF = -R for a dense symmetric R (the `MatrixSign` replay on the kept factorisation) -> (X, info).  transposed=True solves
+        the dual equation F Y E' + E Y F' = -R of the same pencil from the same kept factorisation (`dre_sign_solve_dense_t`)."""
+        fn = self._entry("dre_sign_solve_dense", transposed)
         Rd = R if isinstance(R, dev.DenseMatrix) else self.ctx.upload(_dense_f64(R))
         xp = C.c_void_p()
         ii, dd = (C.c_int64 * 2)(), (C.c_double * 2)()
-        self.ctx.chk(self.ctx.lib.dre_sign_solve_dense(self.ctx.ptr, self.ptr, Rd.ptr, int(max_refine), C.byref(xp), ii, dd))
+        self.ctx.chk(fn(self.ctx.ptr, self.ptr, Rd.ptr, int(max_refine), C.byref(xp), ii, dd))
         X = dev.DenseMatrix(self.ctx, xp)
         return (X.numpy() if download else X), dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1]))
 
@@ -1716,6 +1725,47 @@ def solve_gale_factored_sign(prob: GALEProblem, alg: FactoredSign, ctx=None, ret
             sign.close()
     X = lowrank(L, Dm)
     return (X, info) if return_info else X
+
+
+def solve_gale_pair(E, A, C_obs, C_ctr, alg, ctx=None, return_info=False):
+    """Both Lyapunov equations of one pencil from ONE sign factorisation (`dre_sign_create`) and two replays:
+        A'XE + E'XA = -C_obs   (observability Gramian, regulator side)        A Y E' + E Y A' = -C_ctr   (controllability Gramian, filter side)
+    -> (X, Y).  alg = MatrixSign(): the right-hand sides are ndarrays or LDLᵀ objects (densified), X and Y ndarrays; alg = FactoredSign(): both are
+    LDLᵀ objects, and so are X and Y.  return_info=True adds dict(primal=..., dual=..., factorizations=1) with each replay's statistics."""
+    if isinstance(alg, MatrixSign):
+        for name, Cm in (("C_obs", C_obs), ("C_ctr", C_ctr)):
+            if not isinstance(Cm, (LDLt, np.ndarray)) and not sp.issparse(Cm):
+                raise TypeError(f"solve_gale_pair with MatrixSign() takes ndarray or LDLᵀ right-hand sides, {name} is a {type(Cm).__name__}; "
+                                "nothing was run on the device")
+    elif isinstance(alg, FactoredSign):
+        for name, Cm in (("C_obs", C_obs), ("C_ctr", C_ctr)):
+            if not isinstance(Cm, LDLt):
+                raise TypeError(f"solve_gale_pair with FactoredSign() takes low-rank right-hand sides (LDLᵀ objects), {name} is a "
+                                f"{type(Cm).__name__}; a dense right-hand side goes with MatrixSign(); nothing was run on the device")
+    else:
+        raise TypeError(f"solve_gale_pair takes alg = MatrixSign() or FactoredSign(), not {type(alg).__name__}; nothing was run on the device")
+    if isinstance(alg, MatrixSign):
+        maxiters, tol, max_refine = _sign_params(alg)
+        Rs = [_dense_f64(Cm.dense() if isinstance(Cm, LDLt) else Cm) for Cm in (C_obs, C_ctr)]
+        sign = SignFactorization(E, A, maxiters, tol if tol > 0 else None, ctx)
+        try:
+            X, ip = sign.solve_dense(Rs[0], max_refine)
+            Y, idual = sign.solve_dense(Rs[1], max_refine, transposed=True)
+        finally:
+            sign.close()
+    else:
+        n = C_obs.n
+        maxiters, tol, rtol, max_width, max_refine = _factored_sign_params(alg, n)
+        blocks = [(np.zeros((n, 0)), np.zeros((0, 0))) if Cm.rank() == 0 else _single_block(Cm) for Cm in (C_obs, C_ctr)]
+        sign = SignFactorization(E, A, maxiters, tol if tol > 0 else None, ctx)
+        try:
+            L, Dm, ip = sign.solve_lr(*blocks[0], rtol, max_width, max_refine)
+            X = lowrank(L, Dm)
+            L, Dm, idual = sign.solve_lr(*blocks[1], rtol, max_width, max_refine, transposed=True)
+            Y = lowrank(L, Dm)
+        finally:
+            sign.close()
+    return ((X, Y), dict(primal=ip, dual=idual, factorizations=1)) if return_info else (X, Y)
 
 
 def _solve_gdre_factored_sign(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats):

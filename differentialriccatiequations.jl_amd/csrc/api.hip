@@ -80,10 +80,11 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 108; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 109; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
-                                        // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2
+                                        // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
+                                        // 109: dual solves on a kept sign factorisation (dre_sign_solve_dense_t, dre_sign_solve_lr_t)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1640,6 +1641,35 @@ int dre_sign_solve_dense(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_
         if (iinfo) { iinfo[0] = st.iters; iinfo[1] = st.refinements; }
         if (dinfo) { dinfo[0] = st.res0; dinfo[1] = st.res; }
         *X = out.release();
+    });
+}
+// the dual equation F Y E' + E Y F' = -R / -G S G' on the same kept factorisation (109)
+int dre_sign_solve_dense_t(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** Y, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(s && R && Y && max_refine >= 0, "dre_sign_solve_dense_t: null argument or negative max_refine");
+        const int n = s->s->n();
+        auto out = std::make_unique<dre_dense>();
+        out->m = Mat(c, n, n);
+        s->s->set_max_refine(max_refine);
+        const SignStats st = s->s->solve_t(R->m, out->m);
+        c->sync();
+        if (iinfo) { iinfo[0] = st.iters; iinfo[1] = st.refinements; }
+        if (dinfo) { dinfo[0] = st.res0; dinfo[1] = st.res; }
+        *Y = out.release();
+    });
+}
+int dre_sign_solve_lr_t(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
+                        dre_dense** L, dre_dense** D, int64_t* ii, double* dd) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(s && G && S && L && D, "dre_sign_solve_lr_t: null argument");
+        auto Lo = std::make_unique<dre_dense>(), Do = std::make_unique<dre_dense>();
+        const SignLrStats st = s->s->solve_lr_t(G->m, S->m, rtol, max_width, max_refine, Lo->m, Do->m);
+        c->sync();
+        if (ii) { ii[0] = st.rank; ii[1] = st.peak_width; ii[2] = st.compressions; ii[3] = st.refinements; }
+        if (dd) { dd[0] = st.res0; dd[1] = st.res; }
+        *L = Lo.release(); *D = Do.release();
     });
 }
 int dre_sign_free(dre_ctx*, dre_sign* s) { delete s; return DRE_OK; }

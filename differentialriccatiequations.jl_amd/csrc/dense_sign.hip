@@ -212,6 +212,78 @@ SignStats SignLyap::solve(const Mat& R, Mat& X) {
     return s;
 }
 
+// ---- the dual equation F Y E' + E Y F' = -R on the same kept sequence (host model: tests/_sign_dual_model.py) ------------------
+// Res = R + G + G' (G = F Y E'), with the partial sums of squares of Res AND of R from the same pass: the dual solve needs no norm launch of its
+// own for the right-hand side, and a refinement step re-reads R anyway
+__global__ __launch_bounds__(256) void k_res_sym_norms(int n, const double* __restrict__ Rm, const double* __restrict__ G, double* __restrict__ Res,
+                                                       double* __restrict__ part) {
+    double s = 0.0, sr = 0.0;
+    const size_t tot = (size_t)n * n;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
+        const int i = idx % n, j = idx / n;
+        const double r = Rm[idx], v = r + G[idx] + G[j + (size_t)i * n];
+        Res[idx] = v;
+        s += v * v; sr += r * r;
+    }
+    store_partials(part, s, sr);
+}
+
+__global__ __launch_bounds__(256) void k_res_norms_finish(int nparts, const double* __restrict__ part, SignCtl* ctl) {
+    double s[2];
+    load_partials(nparts, part, s);
+    if (threadIdx.x == 0) ctl->res = s[1] > 0.0 ? sqrt(s[0] / s[1]) : sqrt(s[0]);
+}
+
+// V_0 = sym(E^-1 R E^-T), V_{k+1} = sym(V_k / (2 c_k) + (c_k / 2) P_k V_k P_k'), Y = V_inf / 2: two GEMMs and one combiner pass per iteration as in
+// replay(); the entry transform takes the place of replay()'s exit transform, and the last combiner pass carries the factor 1/2 and writes Y
+void SignLyap::replay_t(const Mat& R, Mat& Y) {
+    const int n = n_;
+    gemm(c_, false, false, 1.0, Einv_, R, 0.0, T_, nullptr, "sign_gemm");                      // E^-1 R
+    gemm(c_, false, true, 1.0, T_, Einv_, 0.0, Y_, nullptr, "sign_gemm");                      // E^-1 R E^-T
+    comb(c_, W_, 1.0, Y_, 0.0, nullptr, 0.0, nullptr, true);
+    for (int k = 0; k < iters_; ++k) {
+        const Mat P = Pstore_.colsview(k * n, n);
+        const double cf = cs_[(size_t)k];
+        gemm(c_, false, false, 1.0, P, W_, 0.0, T_, nullptr, "sign_gemm");                     // P V
+        gemm(c_, false, true, 0.5 * cf, T_, P, 1.0 / (2.0 * cf), W_, nullptr, "sign_gemm");    // V/(2c) + (c/2) P V P'
+        if (k + 1 == iters_) comb(c_, Y, 0.5, W_, 0.0, nullptr, 0.0, nullptr, true);
+        else {
+            comb(c_, Y_, 1.0, W_, 0.0, nullptr, 0.0, nullptr, true);
+            std::swap(W_, Y_);
+        }
+    }
+}
+
+double SignLyap::residual_t(const Mat& R, const Mat& Y) {
+    const int n = n_;
+    gemm(c_, false, true, 1.0, Y, E_, 0.0, T_, nullptr, "sign_gemm");        // Y E'
+    gemm(c_, false, false, 1.0, F_, T_, 0.0, Y_, nullptr, "sign_gemm");      // F Y E'
+    TimedScope ts(c_, "sign_residual", 24.0 * n * n, 0.0);
+    hipLaunchKernelGGL(k_res_sym_norms, dim3(NORM_PARTS), dim3(256), 0, c_->stream, n, (const double*)R.p, (const double*)Y_.p, Res_.p, part_.p);
+    hipLaunchKernelGGL(k_res_norms_finish, dim3(1), dim3(256), 0, c_->stream, NORM_PARTS, (const double*)part_.p, ctl_.p);
+    return read_back(c_, ctl_.p).res;
+}
+
+SignStats SignLyap::solve_t(const Mat& R, Mat& Y) {
+    const int n = n_;
+    DRE_REQUIRE(R.rows == n && R.cols == n && R.ld == n && Y.rows == n && Y.cols == n && Y.ld == n, "dense path: R and Y must be n x n");
+    DRE_REQUIRE(iters_ > 0, "dense path: factor() first");
+    ensure_dense_work();
+    SignStats s;
+    s.iters = iters_;
+    replay_t(R, Y);
+    s.res0 = s.res = residual_t(R, Y);
+    const double target = 100.0 * n * DBL_EPS;
+    Mat dY = square(c_, n);
+    while (s.res > target && s.refinements < max_refine_) {
+        replay_t(Res_, dY);
+        comb(c_, Y, 1.0, Y, 1.0, &dY);
+        s.res = residual_t(R, Y);
+        ++s.refinements;
+    }
+    return s;
+}
+
 // ---- Rosenbrock drivers (dense_ros{1,2,3,4}.jl of the reference) ------------------------------------------------
 DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X0, double t0, double tf, double dt,
                                  int order, bool save_state, int maxiters, double tol, int max_refine) {

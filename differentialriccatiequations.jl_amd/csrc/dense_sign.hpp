@@ -41,11 +41,19 @@ class SignLyap {
     // Factored replay (dense_sign_lr.hip): F'XE + E'XF = -G S G' (G n x r, S r x r symmetric, indefinite allowed) with the kept sequence applied
     // to the factor; X = L D L' with D diagonal (r = 0: L is n x 0).  Throws Error(ERR_INVALID) on rtol outside (0, 1) or max_width < max(r, 1).
     SignLrStats solve_lr(const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D);
+    // The dual equation of the same pencil, F Y E' + E Y F' = -R, from the same kept sequence: the sign iteration of (F', E') has the iterates
+    // Z_k' and the same c_k, and with V = E^-1 W E^-T its W recursion reads V <- sym(V/(2c) + (c/2) P_k V P_k'), V_0 = E^-1 R E^-T, Y = V/2.
+    // Same refinement rule as solve(); the kept state is not changed.  DESIGN.md §9.7.
+    SignStats solve_t(const Mat& R, Mat& Y);
+    // Factored dual replay: F Y E' + E Y F' = -G S G', L_0 = E^-1 G, L_{k+1} = [L_k, P_k L_k]; arguments, cap, compression and refinement as solve_lr
+    SignLrStats solve_lr_t(const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D);
 
   private:
     void ensure_dense_work();
     void replay(const Mat& R, Mat& X);
     double residual(const Mat& R, const Mat& X);
+    void replay_t(const Mat& R, Mat& Y);
+    double residual_t(const Mat& R, const Mat& Y);
     Ctx* c_;
     int n_, maxiters_, max_refine_, iters_ = 0;
     double tol_, logdetE_ = 0.0;

@@ -281,4 +281,137 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
     return st;
 }
 
+// The dual equation F Y E' + E Y F' = -G S G' on the same kept sequence (tests/_sign_dual_model.py):
+//     L_0 = E^-1 G,   L_{k+1} = [L_k, P_k L_k],   D_{k+1} = blkdiag(D_k / (2 c_k), (c_k / 2) D_k),   Y = L_inf (D_inf / 2) L_inf'
+// The transform with E^-1 sits at the entry instead of the exit and no operand is transposed; cap, compression, regrowth, refinement and the
+// statistics are solve_lr's, statement for statement (solve_lr itself is left untouched, hence a function of its own).
+SignLrStats SignLyap::solve_lr_t(const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D) {
+    Ctx* c = c_;
+    const int n = n_, r = G.cols;
+    DRE_REQUIRE(iters_ > 0, "solve_lr_t: factor() first");
+    DRE_REQUIRE(G.rows == n && S.rows == r && S.cols == r, "solve_lr_t: G must be n x r and S r x r");
+    DRE_REQUIRE(rtol > 0.0 && rtol < 1.0, "solve_lr_t: rtol must lie in (0, 1)");
+    DRE_REQUIRE(max_width >= 1 && max_width >= r && max_width <= SIGN_LR_MAX_WIDTH,
+                "solve_lr_t: max_width must be at least the width of G (and 1) and at most " + std::to_string(SIGN_LR_MAX_WIDTH));
+    DRE_REQUIRE(max_refine >= 0, "solve_lr_t: max_refine must be >= 0");
+    SignLrStats st;
+    st.iters = iters_;
+    if (r == 0) { L = Mat(c, n, 0); D = Mat(c, 0, 0); return st; }
+    require_memory(c, sign_lr_t_doubles(n, r, max_width));
+
+    // (L0, D0) of a right-hand side -> (L_inf, D_inf / 2) with D diagonal; E^-1 L0 is written straight into the left columns of the buffer and
+    // P_k L_k into the columns to its right
+    auto replay_lr = [&](const Mat& L0, const Mat& D0, Mat& LY, Mat& DY) {
+        int w = L0.cols;
+        const int cap = std::max(max_width, w);
+        if (cap > max_width) require_memory(c, sign_lr_t_doubles(n, r, cap));
+        Mat buf(c, n, 2 * cap);
+        Mat left0 = buf.colsview(0, w);
+        gemm(c, false, false, 1.0, Einv_, L0, 0.0, left0, nullptr, "signlr_gemm");           // E^-1 L0
+        Mat Dk = D0;
+        Compressor comp(c);
+        auto compress = [&]() -> std::vector<double> {
+            Mat Lv = buf.colsview(0, w);
+            comp.form(Lv, Dk);
+            std::vector<double> vals = comp.finish(buf, rtol);
+            ++st.compressions;
+            w = (int)vals.size();
+            return vals;
+        };
+        std::vector<double> vals;
+        bool fresh = false;          // Dk == diag(vals) of a compression that nothing has touched since
+        for (int k = 0; k < iters_ && w > 0; ++k) {
+            if (2 * w > buf.cols) {         // a rank above the cap survived the compression: the buffer follows it
+                require_memory(c, sign_lr_t_doubles(n, r, w));
+                Mat nb(c, n, 2 * w);
+                Mat dstv = nb.colsview(0, w), srcv = buf.colsview(0, w);
+                copy_mat(c, srcv, dstv);
+                buf = nb;
+            }
+            const Mat P = Pstore_.colsview(k * n, n);
+            const double cf = cs_[(size_t)k];
+            Mat left = buf.colsview(0, w), right = buf.colsview(w, w);
+            gemm(c, false, false, 1.0, P, left, 0.0, right, nullptr, "signlr_gemm");         // P_k L_k
+            Mat Dn(c, 2 * w, 2 * w);
+            blkdiag(c, Dk, 1.0 / (2.0 * cf), Dk, 0.5 * cf, Dn);
+            Dk = Dn;
+            w *= 2;
+            fresh = false;
+            st.peak_width = std::max<long>(st.peak_width, w);
+            if (w > max_width) { vals = compress(); Dk = diag_mat(c, vals, 1.0); fresh = true; }
+        }
+        if (!fresh && w > 0) vals = compress();
+        LY = Mat(c, n, w);
+        if (w > 0) {
+            Mat Lv = buf.colsview(0, w);
+            copy_mat(c, Lv, LY);
+        }
+        DY = diag_mat(c, vals, 0.5);
+    };
+
+    Compressor comp(c);
+    comp.form(G, S);
+    const double normR = comp.norm();
+    st.peak_width = r;
+    Mat LY, DY;
+    replay_lr(G, S, LY, DY);
+
+    // factored residual [G, F L, E L] blkdiag(S, [[0, D], [D, 0]]) [..]': its norm through the small matrix on the QR's basis
+    const double target = 100.0 * n * DBL_EPS + 10.0 * rtol;
+    Mat Rf, T;
+    auto residual = [&]() -> double {
+        const int p = LY.cols, w = r + 2 * p;
+        Rf = Mat(c, n, w);
+        Mat g = Rf.colsview(0, r);
+        copy_mat(c, G, g);
+        if (p > 0) {
+            Mat fl = Rf.colsview(r, p), el = Rf.colsview(r + p, p);
+            gemm(c, false, false, 1.0, F_, LY, 0.0, fl, nullptr, "signlr_gemm");
+            gemm(c, false, false, 1.0, E_, LY, 0.0, el, nullptr, "signlr_gemm");
+        }
+        T = Mat(c, w, w);
+        {
+            TimedScope ts(c, "signlr_small", 8.0 * w * w, 0.0);
+            hipLaunchKernelGGL(k_lr_res_t, dim3(grid_for((size_t)w * w)), dim3(256), 0, c->stream, r, (const double*)S.p, S.ld, p, (const double*)DY.p,
+                               DY.ld, T.p, T.ld);
+        }
+        comp.form(Rf, T);
+        const double nr = comp.norm();
+        return normR > 0.0 ? nr / normR : nr;
+    };
+    st.res0 = st.res = residual();
+    while (st.res > target && st.refinements < max_refine && std::isfinite(st.res)) {
+        std::vector<double> rv = comp.finish(Rf, rtol);          // the compressed residual factor, in the left columns of Rf
+        ++st.compressions;
+        const int pr = (int)rv.size();
+        if (pr == 0) break;
+        Mat Lr = Rf.colsview(0, pr), Dr = diag_mat(c, rv, 1.0), LdY, DdY;
+        replay_lr(Lr, Dr, LdY, DdY);
+        // Y <- Y + dY: append and compress
+        const int p = LY.cols, pd = LdY.cols, w = p + pd;
+        if (pd == 0) break;
+        Mat cat(c, n, w), Dc(c, w, w);
+        Mat a = cat.colsview(0, p), b = cat.colsview(p, pd);
+        copy_mat(c, LY, a);
+        copy_mat(c, LdY, b);
+        blkdiag(c, DY, 1.0, DdY, 1.0, Dc);
+        st.peak_width = std::max<long>(st.peak_width, w);
+        Compressor cx(c);
+        cx.form(cat, Dc);
+        std::vector<double> yv = cx.finish(cat, rtol);
+        ++st.compressions;
+        const int py = (int)yv.size();
+        LY = Mat(c, n, py);
+        if (py > 0) { Mat src = cat.colsview(0, py); copy_mat(c, src, LY); }
+        DY = diag_mat(c, yv, 1.0);
+        ++st.refinements;
+        st.res = residual();
+    }
+    DRE_HIP(hipGetLastError());
+    st.rank = LY.cols;
+    L = LY;
+    D = DY;
+    return st;
+}
+
 }  // namespace dre

@@ -25,4 +25,8 @@ inline size_t sign_lr_doubles(int n, int max_width) {
     return 5 * (size_t)n * w2 + 6 * w2 * w2;
 }
 
+// what solve_lr_t checks on top of that: the entry block E^-1 G (n x r) and the residual's F L_Y and E L_Y blocks (n x max_width each; the
+// dual has no exit transform, so these are the only products with F, E and E^-1 outside the recursion)
+inline size_t sign_lr_t_doubles(int n, int r, int max_width) { return sign_lr_doubles(n, max_width) + (size_t)n * ((size_t)r + 2 * (size_t)max_width); }
+
 }  // namespace dre

@@ -560,8 +560,9 @@ function SignFactorization(ctx::Context, E, F; maxiters::Int=50, tol::Float64=0.
     finalizer(x -> ccall((:dre_sign_free, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ctx.ptr, x.ptr), s)
 end
 
-"F'XE + E'XF = -G S G' on a kept factorisation: (L, D, info) with X = L D L', D diagonal"
-function solve_lr(s::SignFactorization, G::AbstractMatrix, S::AbstractMatrix; rtol::Float64=0.0, max_width::Int=256, max_refine::Int=1)
+"F'XE + E'XF = -G S G' on a kept factorisation: (L, D, info) with X = L D L', D diagonal; transposed = true: the dual equation F Y E' + E Y F' = -G S G' from the same factorisation"
+function solve_lr(s::SignFactorization, G::AbstractMatrix, S::AbstractMatrix; rtol::Float64=0.0, max_width::Int=256, max_refine::Int=1, transposed::Bool=false)
+    transposed && return solve_lr_t(s, G, S; rtol = rtol, max_width = max_width, max_refine = max_refine)
     ctx = s.ctx
     Gd, Sd = upload(ctx, Matrix{Float64}(G)), upload(ctx, Matrix{Float64}(S))
     L, D = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
@@ -572,8 +573,9 @@ function solve_lr(s::SignFactorization, G::AbstractMatrix, S::AbstractMatrix; rt
     download(ctx, L[]), download(ctx, D[]), (iters = s.iters, rank = ii[1], peak_width = ii[2], compressions = ii[3], refinements = ii[4], res0 = dd[1], res = dd[2])
 end
 
-"F'XE + E'XF = -R for a dense symmetric R on a kept factorisation (the MatrixSign replay): (X, info)"
-function solve_dense(s::SignFactorization, R::AbstractMatrix; max_refine::Int=2)
+"F'XE + E'XF = -R for a dense symmetric R on a kept factorisation (the MatrixSign replay): (X, info); transposed = true: the dual equation F Y E' + E Y F' = -R from the same factorisation"
+function solve_dense(s::SignFactorization, R::AbstractMatrix; max_refine::Int=2, transposed::Bool=false)
+    transposed && return solve_dense_t(s, R; max_refine = max_refine)
     ctx = s.ctx
     Rd = upload(ctx, Matrix{Float64}(R))
     X = Ref{Ptr{Cvoid}}(C_NULL)
@@ -599,6 +601,8 @@ function CommonSolve.solve(prob::GALEProblem, alg::FactoredSign; ctx::Context=de
     finalize(s)
     LDLᵀ([1.0], [L], [D], C_NULL, nothing)
 end
+
+include("DREHipSignDual.jl")          # solve_dense_t, solve_lr_t: the dual equation on a kept factorisation (dre_version >= 109)
 
 """Dense GARE: Q + A'XE + E'XA - E'XGXE = 0 with G = β B R⁻¹ Bᵀ, Q = γ Cᵀ S C (riccati/types.jl:41-52), all dense.  `solve(prob, MatrixSign())`
 returns the stabilizing X from the sign function of the Hamiltonian pencil plus Newton-Kleinman refinement (DREError(-7) when the

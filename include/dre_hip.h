@@ -511,6 +511,15 @@ int dre_sign_solve_lr(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_d
 /* F'XE + E'XF = -R for a dense symmetric R on the kept factorisation (what dre_dense_gale_solve does after its own sign iteration);
  * iinfo / dinfo as there.  The three n x n work matrices of this replay are allocated by the first call. */
 int dre_sign_solve_dense(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo);
+/* The dual equation of the kept pencil (dre_version >= 109):  F Y E' + E Y F' = -R  (the controllability Gramian next to the observability
+ * Gramian, the filter equation next to the regulator equation) from the SAME factorisation: no second dre_sign_create on (F', E').
+ * Arguments, info arrays, refinement rule and errors as dre_sign_solve_dense; the kept state is not changed. */
+int dre_sign_solve_dense_t(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** Y, int64_t* iinfo, double* dinfo);
+/* The factored dual (dre_version >= 109):  F Y E' + E Y F' = -G S G',  Y = L D L', with L_0 = E^-1 G and L_{k+1} = [L_k, P_k L_k].  Arguments,
+ * info arrays, cap, compression, refinement threshold and errors as dre_sign_solve_lr; the memory check adds n (r + 2 max_width) doubles
+ * (the E^-1 G block and the residual's F L and E L blocks). */
+int dre_sign_solve_lr_t(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
+                        dre_dense** L, dre_dense** D, int64_t* ii, double* dd);
 int dre_sign_free(dre_ctx* ctx, dre_sign* s);
 
 /* ---- test and diagnostic surface: the internal GEMM entry points one by one (dre_version >= 108) ----------------------------------------
