@@ -1768,6 +1768,120 @@ def solve_gale_pair(E, A, C_obs, C_ctr, alg, ctx=None, return_info=False):
     return ((X, Y), dict(primal=ip, dual=idual, factorizations=1)) if return_info else (X, Y)
 
 
+# ------------------------------------------------------------------------------------------------
+# Device SVD and square-root balanced truncation                           csrc/svd_jacobi.hip, csrc/balance.hip
+# ------------------------------------------------------------------------------------------------
+def svd_jacobi(A, tol=None, ctx=None, return_stats=False):
+    """svd(A) on the device by one-sided block Jacobi (`dre_svd_jacobi`): (U, s, V) with A ≈ U diag(s) Vᵀ, U m x k, s descending, V w x k,
+    k = min(m, w).  Norm-wise accuracy (errors of order eps s[0]); no high relative accuracy for tiny singular values.  tol None:
+    sqrt(max(m, w)) eps.  The columns of U (of V for a wide A) that belong to s <= tol ||A||_F are zero columns.  return_stats adds dict(sweeps, rounds, rank).
+    A that is not a matrix and a tol that is not positive are errors before anything runs on the device; a non-finite entry is the device
+    solver's DREError(-1)."""
+    A = np.asarray(A, dtype=float)
+    if A.ndim != 2:
+        raise ValueError(f"svd_jacobi: a matrix is expected, got shape {A.shape}; nothing was run on the device")
+    if tol is not None and not (float(tol) > 0.0 and math.isfinite(float(tol))):
+        raise ValueError("svd_jacobi: tol must be positive and finite; nothing was run on the device")
+    ctx = ctx or dev.default_context()
+    Ad = ctx.upload(np.asfortranarray(A))
+    up, sp_, vp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    ii = (C.c_int64 * 3)()
+    ctx.chk(ctx.lib.dre_svd_jacobi(ctx.ptr, Ad.ptr, float(tol) if tol is not None else 0.0, C.byref(up), C.byref(sp_), C.byref(vp), ii))
+    U, s, V = dev.DenseMatrix(ctx, up).numpy(), dev.DenseMatrix(ctx, sp_).numpy().ravel(), dev.DenseMatrix(ctx, vp).numpy()
+    return (U, s, V, dict(sweeps=int(ii[0]), rounds=int(ii[1]), rank=int(ii[2]))) if return_stats else (U, s, V)
+
+
+@dataclass
+class ReducedModel:
+    """ẋ_r = Ar x_r + Br u, y = Cr x_r (Er is the identity): the balanced truncation of E ẋ = A x + B u, y = C x to order len(Ar).  hsv: the
+    Hankel singular values; T, W: the right and left projection (x ≈ T x_r, Wᵀ E T = I)."""
+    Er: np.ndarray
+    Ar: np.ndarray
+    Br: np.ndarray
+    Cr: np.ndarray
+    hsv: np.ndarray
+    T: np.ndarray
+    W: np.ndarray
+
+    @property
+    def order(self):
+        return self.Ar.shape[0]
+
+
+def _balance_check(name, E, A, B, C, alg, order, tol):
+    if not isinstance(alg, (FactoredSign, MatrixSign)):
+        raise TypeError(f"{name} takes alg = FactoredSign() or MatrixSign(), not {type(alg).__name__}; nothing was run on the device")
+    if order is not None and (isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer))):
+        raise TypeError(f"{name}: order must be None or an int, not {type(order).__name__}; nothing was run on the device")
+    if order is not None and order < 1:
+        raise ValueError(f"{name}: order must be at least 1 (None: chosen by tol); nothing was run on the device")
+    if not (isinstance(tol, (int, float, np.floating)) and math.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"{name}: tol must be a finite non-negative number; nothing was run on the device")
+    mats = []
+    for nm, M in (("E", E), ("A", A), ("B", B), ("C", C)):
+        if not isinstance(M, (np.ndarray, LowRankUpdate, ScaledPencil)) and not sp.issparse(M):
+            raise TypeError(f"{name}: {nm} must be a matrix, not {type(M).__name__}; nothing was run on the device")
+        mats.append(_dense_operator(M))
+    Ed, Am, Bm, Cm = mats
+    n = Ed.shape[0]
+    if Ed.ndim != 2 or Ed.shape != (n, n) or Am.shape != (n, n) or Bm.ndim != 2 or Bm.shape[0] != n or Cm.ndim != 2 or Cm.shape[1] != n:
+        raise ValueError(f"{name}: E and A must be n x n, B n x m and C q x n; got {Ed.shape}, {Am.shape}, {Bm.shape}, {Cm.shape}; "
+                         "nothing was run on the device")
+    return Ed, Am, Bm, Cm
+
+
+def _balance(name, E, A, B, Cout, alg, order, tol, ctx):
+    Eh, Ah, Bh, Ch = _balance_check(name, E, A, B, Cout, alg, order, tol)
+    n = Eh.shape[0]
+    ctx = ctx or dev.default_context()
+    Ed, Ad, Bd, Cd = (ctx.upload(M) for M in (Eh, Ah, Bh, Ch))
+    if isinstance(alg, FactoredSign):
+        maxiters, stol, rtol, max_width, max_refine = _factored_sign_params(alg, n)
+    else:
+        maxiters, stol, max_refine = _sign_params(alg)
+    sign = SignFactorization(Ed, Ad, maxiters, stol if stol > 0 else None, ctx)
+    try:
+        if isinstance(alg, FactoredSign):
+            Lo, Do, ip = sign.solve_lr(ctx.upload(np.asfortranarray(Ch.T)), ctx.upload(np.eye(Ch.shape[0])), rtol, max_width, max_refine, download=False)
+            Lc, Dc, idual = sign.solve_lr(Bd, ctx.upload(np.eye(Bh.shape[1])), rtol, max_width, max_refine, download=False, transposed=True)
+        else:
+            Q, ip = sign.solve_dense(ctx.gemm(True, False, 1.0, Cd, Cd), max_refine, download=False)
+            P, idual = sign.solve_dense(ctx.gemm(False, True, 1.0, Bd, Bd), max_refine, download=False, transposed=True)
+            fac = []
+            for X in (Q, P):
+                wp, vp = C.c_void_p(), C.c_void_p()
+                ctx.chk(ctx.lib.dre_sym_eig(ctx.ptr, X.ptr, 4.0, C.byref(wp), C.byref(vp)))
+                fac.append((dev.DenseMatrix(ctx, vp), dev.DenseMatrix(ctx, wp)))
+            (Lo, Do), (Lc, Dc) = fac
+    finally:
+        sign.close()
+    out = [C.c_void_p() for _ in range(6)]
+    ii, dd = (C.c_int64 * 6)(), (C.c_double * 3)()
+    ctx.chk(ctx.lib.dre_balance_lr(ctx.ptr, Ed.ptr, Ad.ptr, Bd.ptr, Cd.ptr, Lc.ptr, Dc.ptr, Lo.ptr, Do.ptr, int(order or 0), float(tol),
+                                   *(C.byref(p) for p in out), ii, dd))
+    hsv, T, W, Ar, Br, Cr = (dev.DenseMatrix(ctx, p).numpy() for p in out)
+    info = dict(primal=ip, dual=idual, factorizations=1, order=int(ii[0]), rank=int(ii[1]), r_c=int(ii[2]), r_o=int(ii[3]), dropped=int(ii[4]),
+                svd_sweeps=int(ii[5]), eye_err=float(dd[0]), bound=float(dd[1]), neg_max=float(dd[2]))
+    return ReducedModel(np.eye(Ar.shape[0]), Ar, Br, Cr, hsv.ravel(), T, W), info
+
+
+def balanced_truncation(E, A, B, C, alg=FactoredSign(), order=None, tol=1e-8, ctx=None, return_info=False):
+    """Square-root balanced truncation of E ẋ = A x + B u, y = C x (c-stable pencil (A, E)) on the device -> ReducedModel.
+    ONE sign factorisation of (A, E) (`dre_sign_create`) and two replays give the Gramians: alg = FactoredSign() keeps them in factored form on
+    the device, alg = MatrixSign() runs the two dense replays and factors each Gramian with `dre_sym_eig`.  `dre_balance_lr` does the rest: the
+    SVD of Z_oᵀ E Z_c by `dre_svd_jacobi`, the order, the projections and the reduced matrices.
+    order: the reduced order (above the numerical rank of Z_oᵀ E Z_c: DREError(-1)); None: the smallest r with 2 Σ_{i>r} σ_i <= tol σ_1.
+    return_info=True adds dict(primal, dual, factorizations=1, order, rank, r_c, r_o, dropped, svd_sweeps, eye_err = ||WᵀET - I||_F,
+    bound = 2 Σ_{i>r} σ_i, neg_max).  Wrong types and shapes are errors before anything runs on the device."""
+    red, info = _balance("balanced_truncation", E, A, B, C, alg, order, tol, ctx)
+    return (red, info) if return_info else red
+
+
+def hankel_singular_values(E, A, B, C, alg=FactoredSign(), ctx=None):
+    """The Hankel singular values of E ẋ = A x + B u, y = C x, descending (the `hsv` of `balanced_truncation`)."""
+    return _balance("hankel_singular_values", E, A, B, C, alg, None, 0.0, ctx)[0].hsv
+
+
 def _solve_gdre_factored_sign(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats):
     """solve(::GDREProblem{<:LDLᵀ}, ::Ros1/Ros2(FactoredSign()); dt, save_state, observer): the host-driven Rosenbrock loop with one kept sign
     factorisation per time step and one factored replay per stage.  The observe_gdre_* hooks fire as on the other paths; there are no ADI

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstring>
 
+#include "balance.hpp"
 #include "comm.hpp"
 #include "dense_adaptive.hpp"
 #include "dense_are.hpp"
@@ -18,6 +19,7 @@
 #include "gemm_probe_check.hpp"
 #include "hostla.hpp"
 #include "profiling.hpp"
+#include "svd_jacobi.hpp"
 #include "sym_jacobi.hpp"
 
 using namespace dre;
@@ -80,11 +82,12 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 109; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 110; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
-                                        // 109: dual solves on a kept sign factorisation (dre_sign_solve_dense_t, dre_sign_solve_lr_t)
+                                        // 109: dual solves on a kept sign factorisation (dre_sign_solve_dense_t, dre_sign_solve_lr_t);
+                                        // 110: device SVD and balanced truncation (dre_svd_jacobi, dre_balance_lr)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1673,6 +1676,37 @@ int dre_sign_solve_lr_t(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre
     });
 }
 int dre_sign_free(dre_ctx*, dre_sign* s) { delete s; return DRE_OK; }
+
+// device SVD and balanced truncation (110)
+int dre_svd_jacobi(dre_ctx* ctx, const dre_dense* A, double tol, dre_dense** U, dre_dense** S, dre_dense** V, int64_t* stats) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(A && U && S && V, "dre_svd_jacobi: null argument");
+        SvjStats st;
+        SvdResult r = svd_jacobi(c, A->m, tol, &st);
+        c->sync();
+        auto Uo = std::make_unique<dre_dense>(), So = std::make_unique<dre_dense>(), Vo = std::make_unique<dre_dense>();
+        Uo->m = r.U; So->m = r.S; Vo->m = r.V;
+        if (stats) { stats[0] = st.sweeps; stats[1] = st.rounds; stats[2] = st.rank; }
+        *U = Uo.release(); *S = So.release(); *V = Vo.release();
+    });
+}
+int dre_balance_lr(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* Lc, const dre_dense* Dc,
+                   const dre_dense* Lo, const dre_dense* Do, int order, double tol, dre_dense** hsv, dre_dense** T, dre_dense** W, dre_dense** Ar,
+                   dre_dense** Br, dre_dense** Cr, int64_t* ii, double* dd) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && A && B && C && Lc && Dc && Lo && Do && hsv && T && W && Ar && Br && Cr, "dre_balance_lr: null argument");
+        BalanceResult r = balance_lr(c, E->m, A->m, B->m, C->m, Lc->m, Dc->m, Lo->m, Do->m, order, tol);
+        c->sync();
+        std::unique_ptr<dre_dense> o[6];
+        const Mat* src[6] = {&r.hsv, &r.T, &r.W, &r.Ar, &r.Br, &r.Cr};
+        for (int i = 0; i < 6; ++i) { o[i] = std::make_unique<dre_dense>(); o[i]->m = *src[i]; }
+        if (ii) { ii[0] = r.order; ii[1] = r.rank; ii[2] = r.r_c; ii[3] = r.r_o; ii[4] = r.dropped; ii[5] = r.sweeps; }
+        if (dd) { dd[0] = r.eye_err; dd[1] = r.bound; dd[2] = r.neg_max; }
+        *hsv = o[0].release(); *T = o[1].release(); *W = o[2].release(); *Ar = o[3].release(); *Br = o[4].release(); *Cr = o[5].release();
+    });
+}
 
 int dre_host_eigvals(int n, const double* A, double* wr, double* wi) {
     return guarded(nullptr, [&] {

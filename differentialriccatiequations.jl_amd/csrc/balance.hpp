@@ -1,0 +1,29 @@
+// Square-root balanced truncation of a descriptor system  E x' = A x + B u,  y = C x  from its Gramians in factored form (balance.hip).
+// See DESIGN.md §9.8; the host restatement is tests/_svd_jacobi_model.py (balance).
+#pragma once
+#include "dense.hpp"
+
+namespace dre {
+
+struct BalanceResult {
+    Mat hsv;           // k x 1: the Hankel singular values, k = min(r_o, r_c)
+    Mat T, W;          // n x r: right and left projection, W'E T = I
+    Mat Ar, Br, Cr;    // W'A T (r x r), W'B (r x m), C T (q x r)
+    int order = 0;     // r
+    long rank = 0;     // numerical rank of Z_o'E Z_c
+    int r_c = 0, r_o = 0;   // columns of Z_c and Z_o
+    long dropped = 0;       // non-positive entries of D_c and D_o, left out
+    long sweeps = 0;        // block sweeps of the SVD
+    double eye_err = 0.0;   // ||W'E T - I||_F
+    double bound = 0.0;     // 2 sum_{i > r} sigma_i
+    double neg_max = 0.0;   // largest |d| among the dropped entries
+};
+
+// P = Lc Dc Lc' from A P E' + E P A' = -B B' and Q = Lo Do Lo' from A'Q E + E'Q A = -C'C, in the form dre_sign_solve_lr_t / dre_sign_solve_lr
+// return them; Dc, Do: a diagonal matrix (its diagonal is read) or a vector.  order > 0: that order (above the numerical rank: DRE_ERR_INVALID);
+// order = 0: the smallest r with 2 sum_{i > r} sigma_i <= tol sigma_1, at most the numerical rank.  Shape errors are DRE_ERR_INVALID before any
+// launch.
+BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do,
+                         int order, double tol);
+
+}  // namespace dre

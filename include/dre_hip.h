@@ -522,6 +522,29 @@ int dre_sign_solve_lr_t(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre
                         dre_dense** L, dre_dense** D, int64_t* ii, double* dd);
 int dre_sign_free(dre_ctx* ctx, dre_sign* s);
 
+/* ---- device SVD and balanced truncation (dre_version >= 110) ---------------------------------------------------------------------------
+ * svd(A) by one-sided (Hestenes) cyclic block Jacobi on the device (column blocks of 16, round-robin ordering, one launch per round, the Gram
+ * and update products on v_mfma_f64_16x16x4_f64): A (m x w, untouched) ~ U diag(S) V' with k = min(m, w), *U m x k, *S k x 1 descending and
+ * non-negative, *V w x k.  Accuracy is norm-wise, like a LAPACK driver: errors of order eps sigma_1; there is NO claim of high relative
+ * accuracy for tiny singular values (the Gram matrices are formed explicitly).  tol <= 0: sqrt(max(m, w)) eps; two columns count as orthogonal
+ * when |g_r'g_c| <= tol ||g_r|| ||g_c||.  The columns of U (of V for a wide input, m < w) that belong to sigma <= tol ||A||_F are zero columns; their number
+ * defines the numerical rank.  stats (may be NULL): [0] block sweeps, [1] rounds, [2] numerical rank.
+ * DRE_ERR_INVALID for a non-finite A, min(m, w) > 4096 or max(m, w) > 46340 (before any launch); DRE_ERR_ALLOC from the memory check (before
+ * any launch); DRE_ERR_INTERNAL after 60 sweeps. */
+int dre_svd_jacobi(dre_ctx* ctx, const dre_dense* A, double tol, dre_dense** U, dre_dense** S, dre_dense** V, int64_t* stats /* 3, may be NULL */);
+/* Square-root balanced truncation of  E x' = A x + B u,  y = C x  from its Gramians in the form dre_sign_solve_lr_t and dre_sign_solve_lr return
+ * them:  P = Lc Dc Lc' from A P E' + E P A' = -B B'  and  Q = Lo Do Lo' from A'Q E + E'Q A = -C'C  (Dc, Do: a diagonal matrix or a vector; entries
+ * that are not positive are left out with their columns).  With Z = L sqrt(D) and Zo'E Zc = U Sigma V' (dre_svd_jacobi):  *hsv the Hankel singular
+ * values (min(r_o, r_c) x 1),  *W = Zo U_r Sigma_r^-1/2 and *T = Zc V_r Sigma_r^-1/2 (n x r, W'E T = I),  *Ar = W'A T, *Br = W'B, *Cr = C T.
+ * order > 0: r = order (above the numerical rank of Zo'E Zc: DRE_ERR_INVALID); order = 0: the smallest r with 2 sum_{i > r} sigma_i <= tol sigma_1,
+ * at most the numerical rank.
+ * ii (6, may be NULL): [0] r [1] numerical rank [2] r_c [3] r_o [4] entries of Dc and Do left out [5] sweeps of the SVD;
+ * dd (3, may be NULL): [0] ||W'E T - I||_F [1] the a-priori bound 2 sum_{i > r} sigma_i on max_w ||H(iw) - H_r(iw)||_2 [2] largest |d| left out.
+ * Shape and argument errors are DRE_ERR_INVALID before any launch; the context stays usable after every error. */
+int dre_balance_lr(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* Lc, const dre_dense* Dc,
+                   const dre_dense* Lo, const dre_dense* Do, int order, double tol, dre_dense** hsv, dre_dense** T, dre_dense** W, dre_dense** Ar,
+                   dre_dense** Br, dre_dense** Cr, int64_t* ii /* 6 */, double* dd /* 3 */);
+
 /* ---- test and diagnostic surface: the internal GEMM entry points one by one (dre_version >= 108) ----------------------------------------
  * dre_gemm_probe calls ONE entry point of the f64 MFMA GEMM family with arguments a public caller cannot form: operands that are views into
  * larger buffers, member masks, device-side counts, the `done` flag of an ADI control block.  It has no wrapper beyond the ctypes prototype
