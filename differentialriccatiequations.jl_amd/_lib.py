@@ -202,6 +202,9 @@ PROTOTYPES = {
                                                 C.c_int, C.c_double, C.c_int, _pvp, _pi32]),
     "dre_dense_gare_solve_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pvp, _pvp, _pvp, _pvp, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd, _pi32]),
     "dre_batch_member_error": (C.c_char_p, [_vp, C.c_int]),
+    "dre_sym_eig_jacobi_batched": (C.c_int, [_vp, C.c_int, _pvp, C.c_double, _pvp, _pvp, _pi64, _pi32]),
+    "dre_svd_jacobi_batched": (C.c_int, [_vp, C.c_int, _pvp, C.c_double, _pvp, _pvp, _pvp, _pi64, _pi32]),
+    "dre_balance_lr_batched": (C.c_int, [_vp, C.c_int] + [_pvp] * 8 + [C.c_int, C.c_double] + [_pvp] * 6 + [_pi64, _pd, _pi32]),
 }
 
 _lib = None

@@ -1882,6 +1882,241 @@ def hankel_singular_values(E, A, B, C, alg=FactoredSign(), ctx=None):
     return _balance("hankel_singular_values", E, A, B, C, alg, None, 0.0, ctx)[0].hsv
 
 
+# ------------------------------------------------------------------------------------------------
+# Ensembles: batched block Jacobi and ensemble balanced truncation          csrc/jacobi_batch.hip, csrc/balance.hip
+# ------------------------------------------------------------------------------------------------
+def _batch_members(name, As, what="matrices"):
+    if isinstance(As, np.ndarray) and As.ndim == 3:
+        As = list(As)
+    if not isinstance(As, (list, tuple)):
+        raise TypeError(f"{name}: a list of {what} is expected, not {type(As).__name__}; nothing was run on the device")
+    if len(As) == 0:
+        raise ValueError(f"{name}: empty list of {what}; nothing was run on the device")
+    if len(As) > 65535:
+        raise ValueError(f"{name}: a batch has at most 65535 members, got {len(As)}; nothing was run on the device")
+    return list(As)
+
+
+def _batch_errors_arg(name, errors):
+    if errors not in ("raise", "return"):
+        raise ValueError(f'{name}: errors must be "raise" or "return"; nothing was run on the device')
+
+
+def _raise_first(out, errors):
+    if errors == "raise":
+        for e in out:
+            if isinstance(e, DREError):
+                raise e
+    return out
+
+
+def sym_eigh_batch(As, tol=None, errors="raise", ctx=None, return_stats=False):
+    """eigh(A_b) of a list of dense symmetric matrices of one order in shared launches (`dre_sym_eig_jacobi_batched`, the block Jacobi solver of
+    sym_eigh(method="jacobi") with the member on a grid axis): the list of (w, V), w ascending; with return_stats (w, V, dict(sweeps, rounds)).
+    Every member's result is bit for bit what sym_eigh returns for it alone.  A member with a non-finite entry fails alone (DREError(-1));
+    errors="raise" raises the first failed member's error, errors="return" puts the DREError in that member's slot.  The shape and symmetry
+    checks of sym_eigh are made for every member before anything runs on the device."""
+    name = "sym_eigh_batch"
+    As = [np.asarray(A, dtype=float) for A in _batch_members(name, As)]
+    _batch_errors_arg(name, errors)
+    if tol is not None and not float(tol) > 0.0:
+        raise ValueError(f"{name}: tol must be positive; nothing was run on the device")
+    for b, A in enumerate(As):
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError(f"{name}: member {b}: a square matrix is expected, got shape {A.shape}; nothing was run on the device")
+        if A.shape != As[0].shape:
+            raise ValueError(f"{name}: member {b} has shape {A.shape}, member 0 has {As[0].shape}: the members of a batch share one order; "
+                             "nothing was run on the device")
+        if A.size and np.isfinite(A).all():           # (a non-finite entry is the device solver's DRE_ERR_INVALID of that member)
+            asym = np.abs(A - A.T).max()
+            if asym > 100 * np.finfo(float).eps * np.abs(A).max():
+                raise ValueError(f"{name}: member {b} is not symmetric (max |A - A'| = {asym:.3e}); nothing was run on the device")
+    nb, n = len(As), As[0].shape[0]
+    if n == 0:
+        return [(np.zeros(0), np.zeros((0, 0)), dict(sweeps=0, rounds=0)) if return_stats else (np.zeros(0), np.zeros((0, 0))) for _ in As]
+    ctx = ctx or dev.default_context()
+    Ad = [ctx.upload(np.asfortranarray(A)) for A in As]
+    ws, vs = (C.c_void_p * nb)(), (C.c_void_p * nb)()
+    ii, status = np.zeros(2 * nb, dtype=np.int64), np.zeros(nb, dtype=np.int32)
+    ctx.chk(ctx.lib.dre_sym_eig_jacobi_batched(ctx.ptr, nb, _handle_array(Ad), float(tol) if tol is not None else 0.0, ws, vs,
+                                               ii.ctypes.data_as(C.POINTER(C.c_int64)), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    errs = _batch_errors(ctx, status)
+    out = []
+    for b in range(nb):
+        if errs[b] is not None:
+            out.append(errs[b])
+            continue
+        w, V = dev.DenseMatrix(ctx, C.c_void_p(ws[b])).numpy().ravel(), dev.DenseMatrix(ctx, C.c_void_p(vs[b])).numpy()
+        out.append((w, V, dict(sweeps=int(ii[2 * b]), rounds=int(ii[2 * b + 1]))) if return_stats else (w, V))
+    return _raise_first(out, errors)
+
+
+def svd_jacobi_batch(As, tol=None, errors="raise", ctx=None, return_stats=False):
+    """svd(A_b) of a list of matrices of one shape in shared launches (`dre_svd_jacobi_batched`, the one-sided block Jacobi of svd_jacobi with
+    the member on a grid axis): the list of (U, s, V); with return_stats (U, s, V, dict(sweeps, rounds, rank)).  Every member's result is bit
+    for bit what svd_jacobi returns for it alone.  A member with a non-finite entry fails alone (DREError(-1)); errors as in sym_eigh_batch.
+    A member that is not a matrix, two shapes in one batch and a tol that is not positive are errors before anything runs on the device."""
+    name = "svd_jacobi_batch"
+    As = [np.asarray(A, dtype=float) for A in _batch_members(name, As)]
+    _batch_errors_arg(name, errors)
+    if tol is not None and not (float(tol) > 0.0 and math.isfinite(float(tol))):
+        raise ValueError(f"{name}: tol must be positive and finite; nothing was run on the device")
+    for b, A in enumerate(As):
+        if A.ndim != 2:
+            raise ValueError(f"{name}: member {b}: a matrix is expected, got shape {A.shape}; nothing was run on the device")
+        if A.shape != As[0].shape:
+            raise ValueError(f"{name}: member {b} has shape {A.shape}, member 0 has {As[0].shape}: the members of a batch share one shape; "
+                             "nothing was run on the device")
+    nb = len(As)
+    ctx = ctx or dev.default_context()
+    Ad = [ctx.upload(np.asfortranarray(A)) for A in As]
+    us, ss, vs = (C.c_void_p * nb)(), (C.c_void_p * nb)(), (C.c_void_p * nb)()
+    ii, status = np.zeros(3 * nb, dtype=np.int64), np.zeros(nb, dtype=np.int32)
+    ctx.chk(ctx.lib.dre_svd_jacobi_batched(ctx.ptr, nb, _handle_array(Ad), float(tol) if tol is not None else 0.0, us, ss, vs,
+                                           ii.ctypes.data_as(C.POINTER(C.c_int64)), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    errs = _batch_errors(ctx, status)
+    out = []
+    for b in range(nb):
+        if errs[b] is not None:
+            out.append(errs[b])
+            continue
+        U, s, V = (dev.DenseMatrix(ctx, C.c_void_p(h[b])).numpy() for h in (us, ss, vs))
+        st = dict(sweeps=int(ii[3 * b]), rounds=int(ii[3 * b + 1]), rank=int(ii[3 * b + 2]))
+        out.append((U, s.ravel(), V, st) if return_stats else (U, s.ravel(), V))
+    return _raise_first(out, errors)
+
+
+BALANCE_BATCH_MAX_N = 4096      # the batched dense Lyapunov solver's order limit (dre_dense_gale_solve_batched)
+
+
+def _balance_batch_check(systems, alg, order, tol, errors):
+    name = "balanced_truncation_batch"
+    systems = _batch_members(name, systems, "(E, A, B, C) systems")
+    _batch_errors_arg(name, errors)
+    if isinstance(alg, FactoredSign):
+        raise TypeError(f"{name}: the batched route is the dense one, alg = MatrixSign(); FactoredSign() Gramians are not batched "
+                        "(balanced_truncation takes them one system at a time); nothing was run on the device")
+    if not isinstance(alg, MatrixSign):
+        raise TypeError(f"{name} takes alg = MatrixSign(), not {type(alg).__name__}; nothing was run on the device")
+    mats = []
+    for b, sys_ in enumerate(systems):
+        if not isinstance(sys_, (tuple, list)) or len(sys_) != 4:
+            raise TypeError(f"{name}: member {b} must be a tuple (E, A, B, C); nothing was run on the device")
+        mats.append(_balance_check(f"{name}: member {b}", *sys_, alg, order, tol))
+    shape = lambda m: (m[0].shape[0], m[2].shape[1], m[3].shape[0])
+    for b, m in enumerate(mats):
+        if shape(m) != shape(mats[0]):
+            raise ValueError(f"{name}: member {b} has (n, m, q) = {shape(m)}, member 0 has {shape(mats[0])}: the members of a batch share n, m "
+                             "and q; nothing was run on the device")
+    n = shape(mats[0])[0]
+    if not 1 <= n <= BALANCE_BATCH_MAX_N:
+        raise ValueError(f"{name}: the batched dense Lyapunov solver takes orders 1 .. {BALANCE_BATCH_MAX_N}, got n = {n}; nothing was run on the device")
+    if 2 * len(mats) > 65535:
+        raise ValueError(f"{name}: at most 32767 systems (two Lyapunov equations each in one batch), got {len(mats)}; nothing was run on the device")
+    return mats
+
+
+def balanced_truncation_batch(systems, alg=MatrixSign(), order=None, tol=1e-8, errors="raise", ctx=None, return_info=False):
+    """Square-root balanced truncation of an ensemble: a list of (E, A, B, C) of one (n, m, q), n <= 4096 -> the list of ReducedModel, in three
+    batched calls:  (1) ONE `dre_dense_gale_solve_batched` of 2B members gives both Gramians of every system (member b: A'QE + E'QA = -C'C, member
+    B + b: the transposed pencil, A P E' + E P A' = -B B');  (2) ONE `dre_sym_eig_jacobi_batched` factors the 2B Gramians, and eigenvalues at or
+    below n eps lambda_max are set to zero;  (3) ONE `dre_balance_lr_batched`: every Z_o'E Z_c in a zero-padded stack of the common shape
+    (max r_o) x (max r_c), one batched SVD, then the order rule, projections and reduced matrices per member.
+    A member's result is a bitwise function of its own data and of the padded shape only.  A member whose pencil is not c-stable
+    (DREError(-7)), or whose `order` is above its numerical rank (DREError(-1)), fails alone: errors="raise" raises the first failed member's
+    error, errors="return" puts the DREError in its slot.  return_info=True gives (ReducedModel, info) per member, info with the keys of
+    balanced_truncation's (primal, dual: the two Lyapunov solves; factorizations = 2, one per Gramian) plus padded_shape.
+    FactoredSign() is a TypeError (the batched route is the dense one); wrong types and shapes are errors before anything runs on the device."""
+    mats = _balance_batch_check(systems, alg, order, tol, errors)
+    nb, n = len(mats), mats[0][0].shape[0]
+    ctx = ctx or dev.default_context()
+    lib = ctx.lib
+    pi32, pi64, pd = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    ups = [[ctx.upload(M) for M in m] for m in mats]                                    # (E, A, B, C) handles per member
+    # (1) the Gramians: members 0 .. B-1 (E, A, C'C), members B .. 2B-1 (E', A', B B')
+    maxiters, stol, max_refine = _sign_params(alg)
+    Es = [u[0] for u in ups] + [ctx.upload(np.asfortranarray(m[0].T)) for m in mats]
+    Fs = [u[1] for u in ups] + [ctx.upload(np.asfortranarray(m[1].T)) for m in mats]
+    Rs = [ctx.gemm(True, False, 1.0, u[3], u[3]) for u in ups] + [ctx.gemm(False, True, 1.0, u[2], u[2]) for u in ups]
+    xs = (C.c_void_p * (2 * nb))()
+    gi, gd, gst = np.zeros(4 * nb, dtype=np.int64), np.zeros(4 * nb), np.zeros(2 * nb, dtype=np.int32)
+    ctx.chk(lib.dre_dense_gale_solve_batched(ctx.ptr, 2 * nb, _handle_array(Es), _handle_array(Fs), _handle_array(Rs), maxiters, stol, max_refine, xs,
+                                             gi.ctypes.data_as(pi64), gd.ctypes.data_as(pd), gst.ctypes.data_as(pi32)))
+    def member_error(b, e, stage):
+        """a batched call's error of one of its members, renumbered to the system it belongs to"""
+        msg = str(e).split(": ", 1)[1] if ": " in str(e) else str(e)
+        return DREError(e.code, f"balanced_truncation_batch, member {b} ({stage}): {msg}")
+
+    gerr = _batch_errors(ctx, gst)
+    X = [dev.DenseMatrix(ctx, C.c_void_p(xs[j])) if gerr[j] is None else None for j in range(2 * nb)]
+    gstat = [dict(iters=int(gi[2 * j]), refinements=int(gi[2 * j + 1]), res0=float(gd[2 * j]), res=float(gd[2 * j + 1])) for j in range(2 * nb)]
+    out = [None] * nb                                                                   # None: still alive
+    for b in range(nb):
+        for j, stage in ((b, "observability Gramian"), (nb + b, "controllability Gramian")):
+            if gerr[j] is not None and out[b] is None:
+                out[b] = member_error(b, gerr[j], stage)
+    del Es, Fs, Rs
+
+    def alive():
+        return [b for b in range(nb) if out[b] is None]
+
+    # (2) the eigen-decompositions of the Gramians of the members still alive: Q_b then P_b
+    live = alive()
+    fac = {}
+    if live:
+        G = [X[b] for b in live] + [X[nb + b] for b in live]
+        k = len(G)
+        ws, vs = (C.c_void_p * k)(), (C.c_void_p * k)()
+        est = np.zeros(k, dtype=np.int32)
+        ctx.chk(lib.dre_sym_eig_jacobi_batched(ctx.ptr, k, _handle_array(G), 0.0, ws, vs, None, est.ctypes.data_as(pi32)))
+        eerr = _batch_errors(ctx, est)
+        for i, b in enumerate(live):
+            for j, stage in ((i, "observability Gramian's eigen-decomposition"), (len(live) + i, "controllability Gramian's eigen-decomposition")):
+                if eerr[j] is not None and out[b] is None:
+                    out[b] = member_error(b, eerr[j], stage)
+        for i, b in enumerate(live):
+            pair = []
+            for j in (i, len(live) + i):                                                # observability, controllability
+                if eerr[j] is not None:
+                    continue
+                w, V = dev.DenseMatrix(ctx, C.c_void_p(ws[j])), dev.DenseMatrix(ctx, C.c_void_p(vs[j]))
+                lam = w.numpy().ravel()
+                lam[lam <= n * np.finfo(float).eps * lam.max()] = 0.0                   # the reference's rule (tests/_balance_cases.py, rank_rtol)
+                pair.append((V, ctx.upload(lam.reshape(-1, 1)), int((lam > 0).sum())))
+            if out[b] is None:
+                fac[b] = pair
+    del X
+
+    # (3) the SVD of the stack and the reduced models
+    live = alive()
+    res = {}
+    if live:
+        k = len(live)
+        padded = (max(fac[b][0][2] for b in live), max(fac[b][1][2] for b in live))
+        arrs = [_handle_array([ups[b][j] for b in live]) for j in range(4)]
+        arrs += [_handle_array([fac[b][1][0] for b in live]), _handle_array([fac[b][1][1] for b in live]),
+                 _handle_array([fac[b][0][0] for b in live]), _handle_array([fac[b][0][1] for b in live])]
+        outs = [(C.c_void_p * k)() for _ in range(6)]
+        ii, dd, bst = np.zeros(6 * k, dtype=np.int64), np.zeros(3 * k), np.zeros(k, dtype=np.int32)
+        ctx.chk(lib.dre_balance_lr_batched(ctx.ptr, k, *arrs, int(order or 0), float(tol), *outs, ii.ctypes.data_as(pi64), dd.ctypes.data_as(pd),
+                                           bst.ctypes.data_as(pi32)))
+        berr = _batch_errors(ctx, bst)
+        for i, b in enumerate(live):
+            if berr[i] is not None:
+                out[b] = member_error(b, berr[i], "balancing")
+                continue
+            hsv, T, W, Ar, Br, Cr = (dev.DenseMatrix(ctx, C.c_void_p(o[i])).numpy() for o in outs)
+            j, d = ii[6 * i:6 * i + 6], dd[3 * i:3 * i + 3]
+            info = dict(primal=gstat[b], dual=gstat[nb + b], factorizations=2, order=int(j[0]), rank=int(j[1]), r_c=int(j[2]), r_o=int(j[3]),
+                        dropped=int(j[4]), svd_sweeps=int(j[5]), eye_err=float(d[0]), bound=float(d[1]), neg_max=float(d[2]), padded_shape=padded)
+            red = ReducedModel(np.eye(Ar.shape[0]), Ar, Br, Cr, hsv.ravel(), T, W)
+            res[b] = (red, info) if return_info else red
+    for b in range(nb):
+        if out[b] is None:
+            out[b] = res[b]
+    return _raise_first(out, errors)
+
+
 def _solve_gdre_factored_sign(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats):
     """solve(::GDREProblem{<:LDLᵀ}, ::Ros1/Ros2(FactoredSign()); dt, save_state, observer): the host-driven Rosenbrock loop with one kept sign
     factorisation per time step and one factored replay per stage.  The observe_gdre_* hooks fire as on the other paths; there are no ADI

@@ -18,6 +18,7 @@
 #include "engine.hpp"
 #include "gemm_probe_check.hpp"
 #include "hostla.hpp"
+#include "jacobi_batch.hpp"
 #include "profiling.hpp"
 #include "svd_jacobi.hpp"
 #include "sym_jacobi.hpp"
@@ -82,12 +83,14 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 110; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 111; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
                                         // 109: dual solves on a kept sign factorisation (dre_sign_solve_dense_t, dre_sign_solve_lr_t);
                                         // 110: device SVD and balanced truncation (dre_svd_jacobi, dre_balance_lr)
+                                        // 111: batched block Jacobi and ensemble balanced truncation (dre_sym_eig_jacobi_batched, dre_svd_jacobi_batched,
+                                        //      dre_balance_lr_batched)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1705,6 +1708,106 @@ int dre_balance_lr(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const d
         if (ii) { ii[0] = r.order; ii[1] = r.rank; ii[2] = r.r_c; ii[3] = r.r_o; ii[4] = r.dropped; ii[5] = r.sweeps; }
         if (dd) { dd[0] = r.eye_err; dd[1] = r.bound; dd[2] = r.neg_max; }
         *hsv = o[0].release(); *T = o[1].release(); *W = o[2].release(); *Ar = o[3].release(); *Br = o[4].release(); *Cr = o[5].release();
+    });
+}
+
+// batched block Jacobi and ensemble balanced truncation (111)
+static std::vector<Mat> member_mats(int batch, const dre_dense* const* h, const char* who, const char* what) {
+    std::vector<Mat> v((size_t)batch);
+    for (int b = 0; b < batch; ++b) {
+        DRE_REQUIRE(h[b], std::string(who) + ": " + what + " of member " + std::to_string(b) + " is null");
+        v[(size_t)b] = h[b]->m;
+    }
+    return v;
+}
+int dre_sym_eig_jacobi_batched(dre_ctx* ctx, int batch, const dre_dense* const* S, double tol, dre_dense** values, dre_dense** vectors, int64_t* stats,
+                               int32_t* status) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        const char* who = "dre_sym_eig_jacobi_batched";
+        DRE_REQUIRE(S && values && vectors && status && batch >= 1, std::string(who) + ": null argument or batch < 1");
+        for (int b = 0; b < batch; ++b) values[b] = vectors[b] = nullptr;
+        SymEigBatch r = sym_eig_jacobi_batch(c, member_mats(batch, S, who, "S"), tol, who);
+        // ascending order and the output format of dre_sym_eig_jacobi, per member; the eigenvalues of all members go up in one copy
+        const int q = r.eig[0].q;
+        std::vector<double> w((size_t)batch * q);
+        DevArr<double> dw(c, w.size());
+        std::vector<std::unique_ptr<dre_dense>> Vo((size_t)batch), Wo((size_t)batch);
+        for (int b = 0; b < batch; ++b) {
+            if (r.status[(size_t)b].code) continue;
+            const SymEig& e = r.eig[(size_t)b];
+            std::vector<int> ids(e.j);
+            for (int i = 0; i < e.j; ++i) ids[i] = i;
+            std::sort(ids.begin(), ids.end(), [&](int a, int d) { return e.w[a] < e.w[d]; });
+            for (int i = 0; i < e.j; ++i) w[(size_t)b * q + i] = e.w[ids[i]];
+            Vo[(size_t)b] = std::make_unique<dre_dense>();
+            Vo[(size_t)b]->m = sym_eig_backtransform(c, e, ids);
+        }
+        dw.upload(c, w);
+        for (int b = 0; b < batch; ++b) {
+            if (r.status[(size_t)b].code) continue;
+            Wo[(size_t)b] = std::make_unique<dre_dense>();
+            Wo[(size_t)b]->m.buf = dw.buf; Wo[(size_t)b]->m.p = dw.p + (size_t)b * q;
+            Wo[(size_t)b]->m.rows = q; Wo[(size_t)b]->m.cols = 1; Wo[(size_t)b]->m.ld = q > 0 ? q : 1;
+            if (stats) { stats[2 * b] = r.stats[(size_t)b].sweeps; stats[2 * b + 1] = r.stats[(size_t)b].rounds; }
+        }
+        c->sync();
+        for (int b = 0; b < batch; ++b) { values[b] = Wo[(size_t)b].release(); vectors[b] = Vo[(size_t)b].release(); }
+        report_members(ctx, r.status, status);
+    });
+}
+int dre_svd_jacobi_batched(dre_ctx* ctx, int batch, const dre_dense* const* A, double tol, dre_dense** U, dre_dense** S, dre_dense** V, int64_t* stats,
+                           int32_t* status) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        const char* who = "dre_svd_jacobi_batched";
+        DRE_REQUIRE(A && U && S && V && status && batch >= 1, std::string(who) + ": null argument or batch < 1");
+        for (int b = 0; b < batch; ++b) U[b] = S[b] = V[b] = nullptr;
+        SvdBatch r = svd_jacobi_batch(c, member_mats(batch, A, who, "A"), tol, who);
+        c->sync();
+        std::vector<std::unique_ptr<dre_dense>> o((size_t)3 * batch);
+        for (int b = 0; b < batch; ++b) {
+            if (r.status[(size_t)b].code) continue;
+            const Mat* src[3] = {&r.svd[(size_t)b].U, &r.svd[(size_t)b].S, &r.svd[(size_t)b].V};
+            for (int i = 0; i < 3; ++i) { o[(size_t)3 * b + i] = std::make_unique<dre_dense>(); o[(size_t)3 * b + i]->m = *src[i]; }
+            if (stats) { stats[3 * b] = r.stats[(size_t)b].sweeps; stats[3 * b + 1] = r.stats[(size_t)b].rounds; stats[3 * b + 2] = r.stats[(size_t)b].rank; }
+        }
+        for (int b = 0; b < batch; ++b) { U[b] = o[(size_t)3 * b].release(); S[b] = o[(size_t)3 * b + 1].release(); V[b] = o[(size_t)3 * b + 2].release(); }
+        report_members(ctx, r.status, status);
+    });
+}
+int dre_balance_lr_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                           const dre_dense* const* C, const dre_dense* const* Lc, const dre_dense* const* Dc, const dre_dense* const* Lo,
+                           const dre_dense* const* Do, int order, double tol, dre_dense** hsv, dre_dense** T, dre_dense** W, dre_dense** Ar,
+                           dre_dense** Br, dre_dense** Cr, int64_t* ii, double* dd, int32_t* status) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        const char* who = "dre_balance_lr_batched";
+        DRE_REQUIRE(E && A && B && C && Lc && Dc && Lo && Do && hsv && T && W && Ar && Br && Cr && status && batch >= 1,
+                    std::string(who) + ": null argument or batch < 1");
+        dre_dense** outs[6] = {hsv, T, W, Ar, Br, Cr};
+        for (int b = 0; b < batch; ++b)
+            for (auto* o : outs) o[b] = nullptr;
+        const dre_dense* const* ins[8] = {E, A, B, C, Lc, Dc, Lo, Do};
+        std::vector<BalanceMember> mem((size_t)batch);
+        for (int b = 0; b < batch; ++b) {
+            for (auto* in : ins) DRE_REQUIRE(in[b], std::string(who) + ": a handle of member " + std::to_string(b) + " is null");
+            mem[(size_t)b] = BalanceMember{&E[b]->m, &A[b]->m, &B[b]->m, &C[b]->m, &Lc[b]->m, &Dc[b]->m, &Lo[b]->m, &Do[b]->m};
+        }
+        BalanceBatch r = balance_lr_batch(c, mem, order, tol, who);
+        c->sync();
+        std::vector<std::unique_ptr<dre_dense>> o((size_t)6 * batch);
+        for (int b = 0; b < batch; ++b) {
+            if (r.status[(size_t)b].code) continue;
+            const BalanceResult& m = r.res[(size_t)b];
+            const Mat* src[6] = {&m.hsv, &m.T, &m.W, &m.Ar, &m.Br, &m.Cr};
+            for (int i = 0; i < 6; ++i) { o[(size_t)6 * b + i] = std::make_unique<dre_dense>(); o[(size_t)6 * b + i]->m = *src[i]; }
+            if (ii) { int64_t* p = ii + 6 * (size_t)b; p[0] = m.order; p[1] = m.rank; p[2] = m.r_c; p[3] = m.r_o; p[4] = m.dropped; p[5] = m.sweeps; }
+            if (dd) { double* p = dd + 3 * (size_t)b; p[0] = m.eye_err; p[1] = m.bound; p[2] = m.neg_max; }
+        }
+        for (int b = 0; b < batch; ++b)
+            for (int i = 0; i < 6; ++i) outs[i][b] = o[(size_t)6 * b + i].release();
+        report_members(ctx, r.status, status);
     });
 }
 

@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "dense_gj.hpp"
+#include "jacobi_batch.hpp"
 #include "profiling.hpp"
 #include "svd_jacobi.hpp"
 
@@ -150,6 +151,158 @@ BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, con
     set_identity(ctx, I, 1.0);
     gemm(ctx, true, false, 1.0, out.W, XT, -1.0, I, nullptr, "bal_gemm");
     out.eye_err = frob_norm_host(ctx, I);
+    return out;
+}
+
+// ---- ensemble form ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// steps (4)-(7) of balance_lr for one member after the shared SVD: U, V are the member's blocks of the padded factors (r_o x k' and r_c x k'),
+// s the singular values on the host (the member's first k = min(r_o, r_c)), S_dev the same on the device
+void balance_member_finish(Ctx* ctx, const BalanceMember& mb, const Mat& Zc, const Mat& Zo, const Mat& U, const Mat& V, const std::vector<double>& s,
+                           const double* S_dev, long rank, int order, double tol, BalanceResult& out) {
+    const Mat &E = *mb.E, &A = *mb.A, &B = *mb.B, &C = *mb.C;
+    const int n = E.rows, k = std::min(out.r_c, out.r_o);
+    int r = order;
+    if (order > 0) {
+        if (order > rank)
+            throw Error(ERR_INVALID, "balance_lr: the requested order " + std::to_string(order) + " is above the numerical rank " + std::to_string(rank));
+    } else {
+        r = k;
+        double tail = 0.0;
+        while (r > 0 && 2.0 * (tail + s[r - 1]) <= tol * s[0]) { tail += s[r - 1]; --r; }
+        r = (int)std::min<long>(r, rank);
+    }
+    out.order = r;
+    { double tail = 0.0; for (int i = k - 1; i >= r; --i) tail += s[i]; out.bound = 2.0 * tail; }
+
+    out.W = Mat(ctx, n, r); out.T = Mat(ctx, n, r);
+    out.Ar = Mat(ctx, r, r); out.Br = Mat(ctx, r, B.cols); out.Cr = Mat(ctx, C.rows, r);
+    if (r == 0) return;
+    const Mat Ur = U.colsview(0, r), Vr = V.colsview(0, r);
+    gemm(ctx, false, false, 1.0, Zo, Ur, 0.0, out.W, nullptr, "bal_gemm");
+    gemm(ctx, false, false, 1.0, Zc, Vr, 0.0, out.T, nullptr, "bal_gemm");
+    scale_cols(ctx, out.W, S_dev);
+    scale_cols(ctx, out.T, S_dev);
+    Mat XT(ctx, n, r), I(ctx, r, r);
+    gemm(ctx, false, false, 1.0, A, out.T, 0.0, XT, nullptr, "bal_gemm");
+    gemm(ctx, true, false, 1.0, out.W, XT, 0.0, out.Ar, nullptr, "bal_gemm");
+    if (B.cols) gemm(ctx, true, false, 1.0, out.W, B, 0.0, out.Br, nullptr, "bal_gemm");
+    if (C.rows) gemm(ctx, false, false, 1.0, C, out.T, 0.0, out.Cr, nullptr, "bal_gemm");
+    gemm(ctx, false, false, 1.0, E, out.T, 0.0, XT, nullptr, "bal_gemm");
+    set_identity(ctx, I, 1.0);
+    gemm(ctx, true, false, 1.0, out.W, XT, -1.0, I, nullptr, "bal_gemm");
+    out.eye_err = frob_norm_host(ctx, I);
+}
+
+}  // namespace
+
+BalanceBatch balance_lr_batch(Ctx* ctx, const std::vector<BalanceMember>& mem, int order, double tol, const char* who) {
+    const std::string w_ = std::string(who) + ": ";
+    DRE_REQUIRE(!mem.empty() && mem.size() <= (size_t)JACOBI_BATCH_MAX, w_ + "batch must be in 1 .. 65535");
+    const int nb = (int)mem.size();
+    const int n = mem[0].E->rows, mB = mem[0].B->cols, qC = mem[0].C->rows;
+    DRE_REQUIRE(n >= 1 && n <= DENSE_MAX_N, w_ + "order beyond the device's 32-bit index limit, or empty");
+    DRE_REQUIRE(order >= 0, w_ + "negative order");
+    DRE_REQUIRE(order > 0 || (tol >= 0.0 && std::isfinite(tol)), w_ + "tol must be finite and non-negative");
+    size_t need = 0, ro_cap = 0, rc_cap = 0;
+    for (int b = 0; b < nb; ++b) {
+        const BalanceMember& m = mem[(size_t)b];
+        const std::string mb_ = w_ + "member " + std::to_string(b) + ": ";
+        DRE_REQUIRE(m.E->rows == n && m.E->cols == n && m.A->rows == n && m.A->cols == n, mb_ + "E and A must be n x n with the n of member 0");
+        DRE_REQUIRE(m.B->rows == n && m.B->cols == mB && m.C->cols == n && m.C->rows == qC, mb_ + "B must be n x m and C q x n with the (n, m, q) of member 0");
+        DRE_REQUIRE(m.Lc->rows == n && m.Lo->rows == n, mb_ + "the Gramian factors must have n rows");
+        DRE_REQUIRE(diag_stride(*m.Dc, m.Lc->cols) > 0 && diag_stride(*m.Do, m.Lo->cols) > 0, mb_ + "D must be a diagonal matrix or a vector matching its factor's columns");
+        const size_t rc0 = m.Lc->cols, ro0 = m.Lo->cols, k0 = std::min(rc0, ro0);
+        need += (size_t)n * (2 * rc0 + ro0) + 4 * (size_t)n * k0 + ((size_t)mB + qC + k0) * k0;
+        ro_cap = std::max(ro_cap, ro0); rc_cap = std::max(rc_cap, rc0);
+    }
+    DRE_REQUIRE(std::min(ro_cap, rc_cap) <= (size_t)SVJ_MAX_W, w_ + "more than 4096 columns in both Gramian factors");
+    // the members' factors, projections and reduced matrices, the stack of M and its SVD (svd_jacobi_batch checks its own share again)
+    require_memory(ctx, need + (size_t)nb * 6 * ro_cap * rc_cap);
+
+    BalanceBatch out;
+    out.res.resize((size_t)nb); out.status.resize((size_t)nb);
+    auto fail = [&](int b, const Error& e) {
+        std::string msg = e.what();
+        if (msg.rfind("balance_lr: ", 0) == 0) msg = msg.substr(12);
+        out.status[(size_t)b] = {e.code, std::string(who) + ", member " + std::to_string(b) + ": " + msg};
+        out.res[(size_t)b] = BalanceResult{};
+    };
+    std::vector<SqrtFactor> fc((size_t)nb), fo((size_t)nb);
+    int ro_max = 0, rc_max = 0;
+    for (int b = 0; b < nb; ++b) {
+        try {
+            fc[(size_t)b] = sqrt_factor(ctx, *mem[(size_t)b].Lc, *mem[(size_t)b].Dc);
+            fo[(size_t)b] = sqrt_factor(ctx, *mem[(size_t)b].Lo, *mem[(size_t)b].Do);
+        } catch (const Error& e) {
+            if (e.code != ERR_INVALID) throw;
+            fail(b, e);
+            continue;
+        }
+        BalanceResult& r = out.res[(size_t)b];
+        r.r_c = fc[(size_t)b].Z.cols; r.r_o = fo[(size_t)b].Z.cols;
+        r.dropped = fc[(size_t)b].dropped + fo[(size_t)b].dropped;
+        r.neg_max = std::max(fc[(size_t)b].neg_max, fo[(size_t)b].neg_max);
+        ro_max = std::max(ro_max, r.r_o); rc_max = std::max(rc_max, r.r_c);
+    }
+    out.padded_rows = ro_max; out.padded_cols = rc_max;
+
+    // the members that reach the SVD: M_b into the top left corner of its zero-filled slot
+    std::vector<int> ids;
+    std::vector<Mat> Ms;
+    Mat stack;
+    const size_t slot = (size_t)ro_max * rc_max;
+    for (int b = 0; b < nb; ++b) {
+        if (out.status[(size_t)b].code) continue;
+        BalanceResult& r = out.res[(size_t)b];
+        if (std::min(r.r_c, r.r_o) == 0) {
+            if (order != 0) { fail(b, Error(ERR_INVALID, "the requested order is above the numerical rank 0")); continue; }
+            r.hsv = Mat(ctx, 0, 1);
+            r.T = Mat(ctx, n, 0); r.W = Mat(ctx, n, 0);
+            r.Ar = Mat(ctx, 0, 0); r.Br = Mat(ctx, 0, mB); r.Cr = Mat(ctx, qC, 0);
+            continue;
+        }
+        ids.push_back(b);
+    }
+    if (!ids.empty()) {
+        DevArr<double> st(ctx, slot * ids.size());
+        DRE_HIP(hipMemsetAsync(st.p, 0, slot * ids.size() * sizeof(double), ctx->stream));
+        for (size_t i = 0; i < ids.size(); ++i) {
+            const int b = ids[i];
+            const BalanceResult& r = out.res[(size_t)b];
+            Mat slotm;
+            slotm.buf = st.buf; slotm.p = st.p + i * slot; slotm.rows = ro_max; slotm.cols = rc_max; slotm.ld = ro_max;
+            Mat EZ(ctx, n, r.r_c), M = slotm.view(0, 0, r.r_o, r.r_c);
+            gemm(ctx, false, false, 1.0, *mem[(size_t)b].E, fc[(size_t)b].Z, 0.0, EZ, nullptr, "bal_gemm");
+            gemm(ctx, true, false, 1.0, fo[(size_t)b].Z, EZ, 0.0, M, nullptr, "bal_gemm");
+            Ms.push_back(slotm);
+        }
+        SvdBatch sv = svd_jacobi_batch(ctx, Ms, 0.0, who);
+        for (size_t i = 0; i < ids.size(); ++i) {
+            const int b = ids[i];
+            BalanceResult& r = out.res[(size_t)b];
+            if (sv.status[i].code) {
+                // (the SVD numbered the member inside its own batch)
+                const std::string& m0 = sv.status[i].msg;
+                const size_t at = m0.find(": ");
+                fail(b, Error(sv.status[i].code, at == std::string::npos ? m0 : m0.substr(at + 2)));
+                continue;
+            }
+            const int k = std::min(r.r_c, r.r_o);
+            const SvdResult& s = sv.svd[i];
+            r.hsv = s.S.view(0, 0, k, 1);
+            r.rank = std::min<long>(sv.stats[i].rank, k); r.sweeps = sv.stats[i].sweeps;
+            try {
+                balance_member_finish(ctx, mem[(size_t)b], fc[(size_t)b].Z, fo[(size_t)b].Z, s.U.view(0, 0, r.r_o, s.U.cols), s.V.view(0, 0, r.r_c, s.V.cols), s.s,
+                                      s.S.p, r.rank, order, tol, r);
+            } catch (const Error& e) {
+                if (e.code != ERR_INVALID) throw;
+                fail(b, e);
+            }
+        }
+    }
+    ctx->sync();
     return out;
 }
 

@@ -2,6 +2,7 @@
 // See DESIGN.md §9.8; the host restatement is tests/_svd_jacobi_model.py (balance).
 #pragma once
 #include "dense.hpp"
+#include "dense_batch.hpp"
 
 namespace dre {
 
@@ -25,5 +26,25 @@ struct BalanceResult {
 // launch.
 BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do,
                          int order, double tol);
+
+// Ensemble form: the members share (n, m, q); each has its own E, A, B, C and factored Gramians, whose ranks may differ.  Every
+// M_b = Z_o'(E Z_c) is written into a zero-filled stack of the common shape (max_b r_o) x (max_b r_c) and ONE svd_jacobi_batch diagonalises the
+// stack; the order rule, the projections and the reduced matrices then run per member with balance_lr's steps, the member's own r_o and r_c
+// bounding its numerical rank.
+//
+// Contract: a member's result is a bitwise function of its own data and of the padded shape only; it depends on the other members only
+// through that shape.  (Zero rows add nothing to a Gram matrix and zero columns are never rotated, so a member's non-zero singular triplets are
+// those of its own M_b up to rounding, and the padding's singular values are zeros at the tail.)  A batch of one member, whose padded shape is
+// its own, is bitwise balance_lr.
+//
+// Shape errors, batch < 1 and a D that matches no factor are the call's DRE_ERR_INVALID before any launch.  A member's own failure (an order
+// above its numerical rank, a non-finite Gramian factor, an SVD that does not converge) is recorded in status[b]; the others go on.
+struct BalanceBatch {
+    std::vector<BalanceResult> res;              // per member (empty for a failed member)
+    std::vector<BatchMemberStatus> status;
+    int padded_rows = 0, padded_cols = 0;        // the stack's shape: max_b r_o, max_b r_c
+};
+struct BalanceMember { const Mat *E, *A, *B, *C, *Lc, *Dc, *Lo, *Do; };
+BalanceBatch balance_lr_batch(Ctx* ctx, const std::vector<BalanceMember>& mem, int order, double tol, const char* who = "balance_lr_batch");
 
 }  // namespace dre

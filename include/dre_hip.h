@@ -545,6 +545,33 @@ int dre_balance_lr(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const d
                    const dre_dense* Lo, const dre_dense* Do, int order, double tol, dre_dense** hsv, dre_dense** T, dre_dense** W, dre_dense** Ar,
                    dre_dense** Br, dre_dense** Cr, int64_t* ii /* 6 */, double* dd /* 3 */);
 
+/* ---- batched block Jacobi and ensemble balanced truncation (dre_version >= 111) -----------------------------------------------------------
+ * The eigensolver of dre_sym_eig_jacobi, the SVD of dre_svd_jacobi and dre_balance_lr for `batch` members of one shape in shared launches
+ * (member b on a grid axis, one control block per member).  Every output of a member is bit for bit what the single call returns for that
+ * member alone, whatever the other members are; a member that is finished, non-finite or out of sweeps drops out of the following launches
+ * and the others go on.  Conventions of the other *_batched entries: the return value is DRE_OK when the batch was processed; status[b] is 0
+ * or the member's error code (DRE_ERR_INVALID for a non-finite member, DRE_ERR_INTERNAL without convergence), the outputs of a failed member
+ * are NULL, dre_last_error names the first failed member and dre_batch_member_error(ctx, b) gives member b's message.  DRE_ERR_INVALID of the
+ * call itself, before any launch: batch < 1 or > 65535, a NULL array or member, members of different shapes, a shape beyond the single call's
+ * limits; DRE_ERR_ALLOC from the memory check, before any launch.
+ * values[b] (q x 1, ascending), vectors[b] (q x q) in the output format of dre_sym_eig_jacobi; stats (2 * batch, may be NULL): [2b] block
+ * sweeps, [2b + 1] rounds. */
+int dre_sym_eig_jacobi_batched(dre_ctx* ctx, int batch, const dre_dense* const* S, double tol, dre_dense** values, dre_dense** vectors,
+                               int64_t* stats /* 2 * batch */, int32_t* status);
+/* U[b], S[b], V[b] as dre_svd_jacobi returns them (handles into stacks shared by the batch: the memory goes back when the last of them is
+ * freed); stats (3 * batch, may be NULL): [3b] block sweeps, [3b + 1] rounds, [3b + 2] numerical rank. */
+int dre_svd_jacobi_batched(dre_ctx* ctx, int batch, const dre_dense* const* A, double tol, dre_dense** U, dre_dense** S, dre_dense** V,
+                           int64_t* stats /* 3 * batch */, int32_t* status);
+/* dre_balance_lr for members that share (n, m, q); the Gramian factors' ranks may differ.  Every Zo'E Zc is written into a zero-filled stack
+ * of the common shape (max_b r_o) x (max_b r_c) and one batched SVD diagonalises the stack.  Contract: a member's result is a bitwise function
+ * of its own data and of that padded shape only (a batch of one member is bitwise dre_balance_lr).  An order above a member's numerical rank
+ * is that member's DRE_ERR_INVALID in status[b], not the call's.  ii (6 * batch, may be NULL) and dd (3 * batch, may be NULL): per member the
+ * entries of dre_balance_lr. */
+int dre_balance_lr_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                           const dre_dense* const* C, const dre_dense* const* Lc, const dre_dense* const* Dc, const dre_dense* const* Lo,
+                           const dre_dense* const* Do, int order, double tol, dre_dense** hsv, dre_dense** T, dre_dense** W, dre_dense** Ar,
+                           dre_dense** Br, dre_dense** Cr, int64_t* ii /* 6 * batch */, double* dd /* 3 * batch */, int32_t* status);
+
 /* ---- test and diagnostic surface: the internal GEMM entry points one by one (dre_version >= 108) ----------------------------------------
  * dre_gemm_probe calls ONE entry point of the f64 MFMA GEMM family with arguments a public caller cannot form: operands that are views into
  * larger buffers, member masks, device-side counts, the `done` flag of an ADI control block.  It has no wrapper beyond the ctypes prototype
