@@ -1807,6 +1807,11 @@ class ReducedModel:
     def order(self):
         return self.Ar.shape[0]
 
+    def freq_response(self, omega, D=None, **kw):
+        """H_r(iω) = Cr (iω I - Ar)⁻¹ Br (+ D) of the reduced model at every frequency of omega, on the device: `freq_response` with E_r = I
+        and its keyword arguments."""
+        return freq_response(self.Er, self.Ar, self.Br, self.Cr, omega, D=D, **kw)
+
 
 def _balance_check(name, E, A, B, C, alg, order, tol):
     if not isinstance(alg, (FactoredSign, MatrixSign)):
@@ -2115,6 +2120,144 @@ def balanced_truncation_batch(systems, alg=MatrixSign(), order=None, tol=1e-8, e
         if out[b] is None:
             out[b] = res[b]
     return _raise_first(out, errors)
+
+
+# ------------------------------------------------------------------------------------------------
+# Frequency response, batched by frequency                                  csrc/freq_response.hip
+# ------------------------------------------------------------------------------------------------
+FREQ_RESPONSE_MAX_N = 2048      # the real form of iωE - A has order 2n and is inverted with the register panel (2n <= 4096)
+
+
+def _freq_check(name, systems, omega, D, errors, chunk):
+    """the argument errors of the frequency-response calls, before anything runs on the device -> (list of (E, A, B, C), omega, D)"""
+    _batch_errors_arg(name, errors)
+    if chunk is not None and (isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= 65535):
+        raise ValueError(f"{name}: chunk must be None (as many frequencies as fit) or an int in 1 .. 65535; nothing was run on the device")
+    w = np.asarray(omega, dtype=float)
+    if w.ndim != 1:
+        raise ValueError(f"{name}: omega must be a one-dimensional array of frequencies, got shape {w.shape}; nothing was run on the device")
+    if w.size < 1:
+        raise ValueError(f"{name}: at least one frequency is needed; nothing was run on the device")
+    if not np.isfinite(w).all():
+        raise ValueError(f"{name}: omega has a non-finite entry; nothing was run on the device")
+    mats = []
+    for b, sys_ in enumerate(systems):
+        ms = []
+        for nm, M in zip("EABC", sys_):
+            if not isinstance(M, (np.ndarray, LowRankUpdate, ScaledPencil)) and not sp.issparse(M):
+                raise TypeError(f"{name}: {nm} must be a matrix, not {type(M).__name__}; nothing was run on the device")
+            ms.append(_dense_f64(_dense_operator(M)))
+        Ed, Am, Bm, Cm = ms
+        n = Ed.shape[0]
+        if Ed.ndim != 2 or Ed.shape != (n, n) or Am.shape != (n, n) or Bm.ndim != 2 or Bm.shape[0] != n or Cm.ndim != 2 or Cm.shape[1] != n \
+                or n < 1 or Bm.shape[1] < 1 or Cm.shape[0] < 1:
+            raise ValueError(f"{name}: E and A must be n x n, B n x m and C q x n (n, m, q >= 1); got {Ed.shape}, {Am.shape}, {Bm.shape}, {Cm.shape}; "
+                             "nothing was run on the device")
+        mats.append((Ed, Am, Bm, Cm))
+    shape = lambda t: (t[0].shape[0], t[2].shape[1], t[3].shape[0])
+    for b, t in enumerate(mats):
+        if shape(t) != shape(mats[0]):
+            raise ValueError(f"{name}: member {b} has (n, m, q) = {shape(t)}, member 0 has {shape(mats[0])}: the systems of a batch share n, m "
+                             "and q; nothing was run on the device")
+    n, m, q = shape(mats[0])
+    if n > FREQ_RESPONSE_MAX_N:
+        raise ValueError(f"{name}: the real form of i omega E - A has order 2n and goes through the register panel, n <= {FREQ_RESPONSE_MAX_N}; "
+                         f"got n = {n}; nothing was run on the device")
+    if D is not None:
+        D = np.asarray(D)
+        if D.shape != (q, m):
+            raise ValueError(f"{name}: D must be q x m = {(q, m)}, got {D.shape}; nothing was run on the device")
+    return mats, w, D
+
+
+def _freq_run(name, mats, w, chunk, ctx):
+    """-> (H (nsys, K, q, m) complex, list of DREError / None per member s K + k, info)"""
+    ctx = ctx or dev.default_context()
+    nsys, K = len(mats), w.size
+    n, m, q = mats[0][0].shape[0], mats[0][2].shape[1], mats[0][3].shape[0]
+    ups = [[ctx.upload(M) for M in t] for t in mats]
+    re, im = np.zeros(nsys * K * q * m), np.zeros(nsys * K * q * m)
+    status, info = np.zeros(nsys * K, dtype=np.int32), (C.c_int64 * 2)()
+    pd, pi32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    wc = np.ascontiguousarray(w)
+    tail = (K, wc.ctypes.data_as(pd), int(chunk or 0), re.ctypes.data_as(pd), im.ctypes.data_as(pd), status.ctypes.data_as(pi32), info)
+    if nsys == 1:
+        ctx.chk(ctx.lib.dre_freq_response(ctx.ptr, *(u.ptr for u in ups[0]), *tail))
+    else:
+        ctx.chk(ctx.lib.dre_freq_response_batched(ctx.ptr, nsys, *(_handle_array([u[j] for u in ups]) for j in range(4)), *tail))
+    H = (re + 1j * im).reshape(nsys, K, m, q).transpose(0, 1, 3, 2)         # members hold q x m column-major
+    return H, _batch_errors(ctx, status), dict(chunk=int(info[0]), chunks=int(info[1]), members=nsys * K, order=2 * n)
+
+
+def _freq_out(H, errs, info, errors, return_info):
+    if errors == "raise":
+        _raise_first(errs, errors)
+        return (H, info) if return_info else H
+    return (H, errs, info) if return_info else (H, errs)
+
+
+def freq_response(E, A, B, C, omega, D=None, errors="raise", chunk=None, ctx=None, return_info=False):
+    """H(iω_k) = C (iω_k E - A)⁻¹ B + D of the dense descriptor system E ẋ = A x + B u, y = C x + D u at every frequency of omega, in shared
+    launches with the frequency on the member axis (`dre_freq_response`): a complex array (K, q, m).  Per frequency the real form
+    [[-A, -ωE], [ωE, -A]] of iωE - A is inverted with the register panel, so n <= 2048; 16 n³ flops per frequency.  E may be singular; D
+    (q x m) is added on the host.  The sweep runs in chunks of `chunk` frequencies (None: as many as fit the device memory); a frequency's
+    result is bit for bit the same whatever the others are and whatever chunk it falls in.
+    A frequency at which iωE - A is exactly singular (ω on a pole, a NaN in the system) fails alone: its H is NaN.  errors="raise" raises that
+    DREError(-4); errors="return" returns (H, errs) with errs[k] None or the DREError of frequency k.  return_info=True appends
+    dict(chunk, chunks, members, order = 2n).  Wrong types, shapes, a non-finite ω and an empty omega are errors before anything runs on the
+    device."""
+    name = "freq_response"
+    mats, w, D = _freq_check(name, [(E, A, B, C)], omega, D, errors, chunk)
+    H, errs, info = _freq_run(name, mats, w, chunk, ctx)
+    H = H[0] if D is None else H[0] + D
+    return _freq_out(H, errs, info, errors, return_info)
+
+
+def freq_response_batch(systems, omega, errors="raise", chunk=None, ctx=None, return_info=False):
+    """`freq_response` for an ensemble: systems is the list of (E, A, B, C) of one (n, m, q) that `balanced_truncation_batch` takes -> a
+    complex array (nsys, K, q, m) from one `dre_freq_response_batched` call, member s K + k = system s at ω_k.  Entry (s, k) is bit for bit
+    what freq_response gives for system s at ω_k.  errors="return": (H, errs) with errs[s][k]."""
+    name = "freq_response_batch"
+    systems = _batch_members(name, systems, "(E, A, B, C) systems")
+    for b, sys_ in enumerate(systems):
+        if not isinstance(sys_, (tuple, list)) or len(sys_) != 4:
+            raise TypeError(f"{name}: member {b} must be a tuple (E, A, B, C); nothing was run on the device")
+    mats, w, _ = _freq_check(name, systems, omega, None, errors, chunk)
+    H, errs, info = _freq_run(name, mats, w, chunk, ctx)
+    if errors == "raise":
+        return _freq_out(H, errs, info, errors, return_info)
+    K = w.size
+    return _freq_out(H, [errs[s * K:(s + 1) * K] for s in range(len(mats))], info, errors, return_info)
+
+
+def sigma_response(E, A, B, C, omega, D=None, errors="raise", chunk=None, ctx=None, return_info=False):
+    """The singular values of H(iω_k), descending: a real array (K, min(q, m)), the data of a sigma plot.  H comes from `freq_response` (same
+    arguments and returns); the K tiny SVDs run on the host on purpose (numpy.linalg.svd).  A failed frequency's row is NaN."""
+    out = freq_response(E, A, B, C, omega, D=D, errors=errors, chunk=chunk, ctx=ctx, return_info=return_info)
+    H = out[0] if isinstance(out, tuple) else out
+    S = np.full((H.shape[0], min(H.shape[1:])), np.nan)
+    ok = np.isfinite(H).all(axis=(1, 2))
+    if ok.any():
+        S[ok] = np.linalg.svd(H[ok], compute_uv=False)
+    return (S,) + out[1:] if isinstance(out, tuple) else S
+
+
+def bt_error(E, A, B, C, rom, omega, chunk=None, ctx=None):
+    """Balanced truncation's guarantee, measured: max_k ‖H(iω_k) - H_r(iω_k)‖₂ of the full system against the ReducedModel `rom`, both
+    frequency responses from the device -> dict(max_error, omega_at_max, bound = 2 Σ_{i>r} hsv_i, ratio = bound / max_error)."""
+    if not isinstance(rom, ReducedModel):
+        raise TypeError(f"bt_error: rom must be a ReducedModel, not {type(rom).__name__}; nothing was run on the device")
+    name = "bt_error"
+    mats, w, _ = _freq_check(name, [(E, A, B, C)], omega, None, "raise", chunk)
+    if (rom.Br.shape[1], rom.Cr.shape[0]) != (mats[0][2].shape[1], mats[0][3].shape[0]):
+        raise ValueError(f"{name}: the reduced model has (m, q) = {(rom.Br.shape[1], rom.Cr.shape[0])}, the system "
+                         f"{(mats[0][2].shape[1], mats[0][3].shape[0])}; nothing was run on the device")
+    H = freq_response(E, A, B, C, w, chunk=chunk, ctx=ctx)
+    Hr = rom.freq_response(w, chunk=chunk, ctx=ctx)
+    err = np.linalg.svd(H - Hr, compute_uv=False)[:, 0]
+    k = int(np.argmax(err))
+    bound = 2.0 * float(np.sum(np.asarray(rom.hsv, dtype=float)[rom.order:][::-1]))
+    return dict(max_error=float(err[k]), omega_at_max=float(w[k]), bound=bound, ratio=bound / float(err[k]) if err[k] > 0 else math.inf)
 
 
 def _solve_gdre_factored_sign(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats):

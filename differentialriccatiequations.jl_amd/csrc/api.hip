@@ -16,6 +16,7 @@
 #include "dense_sign.hpp"
 #include "dense_sign_lr.hpp"
 #include "engine.hpp"
+#include "freq_response.hpp"
 #include "gemm_probe_check.hpp"
 #include "hostla.hpp"
 #include "jacobi_batch.hpp"
@@ -83,7 +84,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 111; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 112; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -91,6 +92,7 @@ int dre_version(void) { return 111; }   // 101: dense path (dre_dense_gale_solve
                                         // 110: device SVD and balanced truncation (dre_svd_jacobi, dre_balance_lr)
                                         // 111: batched block Jacobi and ensemble balanced truncation (dre_sym_eig_jacobi_batched, dre_svd_jacobi_batched,
                                         //      dre_balance_lr_batched)
+                                        // 112: frequency response batched by frequency (dre_freq_response, dre_freq_response_batched)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1456,6 +1458,32 @@ int dre_dense_invert_batched(dre_ctx* ctx, int batch, dre_dense* const* A, int32
         report_members(ctx, st, status);
     });
 }
+// ---- frequency response (freq_response.hip) --------------------------------------------------------------------------------------------
+int dre_freq_response_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                              const dre_dense* const* C, int K, const double* omega, int chunk, double* H_re, double* H_im, int32_t* status,
+                              int64_t* info) {
+    return guarded(ctx, [&] {
+        const char* who = "dre_freq_response_batched";
+        DRE_REQUIRE(nsys >= 1, std::string(who) + ": no systems (nsys < 1)");
+        DRE_REQUIRE(K >= 1, std::string(who) + ": at least one frequency is needed (K >= 1)");
+        DRE_REQUIRE(E && A && B && C && omega && H_re && H_im && status, std::string(who) + ": null argument");
+        std::vector<FreqSystem> sys((size_t)nsys);
+        for (int s = 0; s < nsys; ++s) {
+            DRE_REQUIRE(E[s] && A[s] && B[s] && C[s], std::string(who) + ": null operand in system " + std::to_string(s));
+            sys[(size_t)s] = FreqSystem{E[s]->m, A[s]->m, B[s]->m, C[s]->m};
+        }
+        const FreqResponse r = freq_response(&ctx->c, sys, std::vector<double>(omega, omega + K), chunk);
+        std::memcpy(H_re, r.re.data(), r.re.size() * sizeof(double));
+        std::memcpy(H_im, r.im.data(), r.im.size() * sizeof(double));
+        if (info) { info[0] = r.chunk; info[1] = r.chunks; }
+        report_members(ctx, r.status, status);
+    });
+}
+int dre_freq_response(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* omega,
+                      int chunk, double* H_re, double* H_im, int32_t* status, int64_t* info) {
+    return dre_freq_response_batched(ctx, 1, &E, &A, &B, &C, K, omega, chunk, H_re, H_im, status, info);
+}
+
 int dre_dense_gale_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* F, const dre_dense* const* R,
                                  int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo, int32_t* status) {
     return guarded(ctx, [&] {

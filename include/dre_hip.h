@@ -572,6 +572,26 @@ int dre_balance_lr_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, c
                            const dre_dense* const* Do, int order, double tol, dre_dense** hsv, dre_dense** T, dre_dense** W, dre_dense** Ar,
                            dre_dense** Br, dre_dense** Cr, int64_t* ii /* 6 * batch */, double* dd /* 3 * batch */, int32_t* status);
 
+/* ---- frequency response of dense descriptor systems, batched by frequency (dre_version >= 112) -------------------------------------------
+ * H(i w_k) = C (i w_k E - A)^-1 B for K frequencies in shared launches, the frequency on the member axis of the batched dense path.  Per
+ * member the real form [[-A, -w E], [w E, -A]] of i w E - A (order 2n) is assembled, inverted in place with the register panel (so
+ * 2n <= 4096) and multiplied out, with one refinement step whose residual is formed from E and A (the real form is not kept): 16 n^3 flops
+ * per frequency; the result is as accurate as a complex LU solve.  The n x n Schur form A + w^2 E A^-1 E would be 8 x cheaper, but it squares the condition number and needs a regular A.  E may be
+ * singular (descriptor systems): nothing here inverts E.
+ * H_re, H_im: q*m*K doubles each, member k at k*q*m, q x m column-major.  status[k]: 0, or DRE_ERR_SINGULAR for a frequency at which
+ * i w E - A has an exactly zero or non-finite pivot (w on a pole, a NaN in the system): its H is NaN, the other frequencies go on.  The sweep
+ * runs in chunks of `chunk` members (0: as many as fit the free device memory, at most 65535); a member's result is bit for bit the same
+ * whatever the other members are and whatever chunk it falls in.  info (2, may be NULL): [0] members per chunk, [1] chunks.
+ * Conventions of the other *_batched entries: DRE_OK when the sweep was processed, dre_last_error names the first failed member and
+ * dre_batch_member_error(ctx, k) gives member k's message.  The call's own DRE_ERR_INVALID, before any launch: a NULL argument, K < 1, a
+ * non-finite frequency, mismatched shapes, 2n > 4096, chunk < 0 or > 65535; DRE_ERR_ALLOC, before any launch: the chunk does not fit. */
+int dre_freq_response(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* omega,
+                      int chunk, double* H_re /* q*m*K */, double* H_im /* q*m*K */, int32_t* status /* K */, int64_t* info /* 2, may be NULL */);
+/* the same for nsys systems of one (n, m, q) at the same K frequencies: member s*K + k is system s at w_k */
+int dre_freq_response_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                              const dre_dense* const* C, int K, const double* omega, int chunk, double* H_re /* q*m*K*nsys */,
+                              double* H_im /* q*m*K*nsys */, int32_t* status /* K*nsys */, int64_t* info /* 2, may be NULL */);
+
 /* ---- test and diagnostic surface: the internal GEMM entry points one by one (dre_version >= 108) ----------------------------------------
  * dre_gemm_probe calls ONE entry point of the f64 MFMA GEMM family with arguments a public caller cannot form: operands that are views into
  * larger buffers, member masks, device-side counts, the `done` flag of an ADI control block.  It has no wrapper beyond the ctypes prototype
