@@ -1888,7 +1888,7 @@ def hankel_singular_values(E, A, B, C, alg=FactoredSign(), ctx=None):
 
 
 # ------------------------------------------------------------------------------------------------
-# Ensembles: batched block Jacobi and ensemble balanced truncation          csrc/jacobi_batch.hip, csrc/balance.hip
+# Ensembles: batched block Jacobi and ensemble balanced truncation          csrc/sym_jacobi.hip, csrc/svd_jacobi.hip, csrc/balance.hip
 # ------------------------------------------------------------------------------------------------
 def _batch_members(name, As, what="matrices"):
     if isinstance(As, np.ndarray) and As.ndim == 3:

@@ -80,6 +80,44 @@ void scale_cols(Ctx* ctx, Mat& X, const double* s_dev) {
     hipLaunchKernelGGL(k_bal_scale_cols, dim3(grid_for((size_t)X.rows * X.cols)), dim3(256), 0, ctx->stream, X.rows, X.cols, X.p, (size_t)X.ld, s_dev);
 }
 
+// steps (4)-(7) for one system after the SVD: U, V are the factors of M (r_o x k' and r_c x k'; in a batch the member's blocks of the padded
+// factors), s the singular values on the host (the first k = min(r_o, r_c) count), S_dev the same on the device
+void balance_member_finish(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Zc, const Mat& Zo, const Mat& U, const Mat& V,
+                           const std::vector<double>& s, const double* S_dev, long rank, int order, double tol, BalanceResult& out) {
+    const int n = E.rows, k = std::min(out.r_c, out.r_o);
+    int r = order;
+    if (order > 0) {
+        if (order > rank)
+            throw Error(ERR_INVALID, "balance_lr: the requested order " + std::to_string(order) + " is above the numerical rank " + std::to_string(rank));
+    } else {
+        // the smallest r with 2 sum_{i > r} sigma_i <= tol sigma_1, the tail summed from the smallest sigma upward
+        r = k;
+        double tail = 0.0;
+        while (r > 0 && 2.0 * (tail + s[r - 1]) <= tol * s[0]) { tail += s[r - 1]; --r; }
+        r = (int)std::min<long>(r, rank);
+    }
+    out.order = r;
+    { double tail = 0.0; for (int i = k - 1; i >= r; --i) tail += s[i]; out.bound = 2.0 * tail; }
+
+    out.W = Mat(ctx, n, r); out.T = Mat(ctx, n, r);
+    out.Ar = Mat(ctx, r, r); out.Br = Mat(ctx, r, B.cols); out.Cr = Mat(ctx, C.rows, r);
+    if (r == 0) return;
+    const Mat Ur = U.colsview(0, r), Vr = V.colsview(0, r);
+    gemm(ctx, false, false, 1.0, Zo, Ur, 0.0, out.W, nullptr, "bal_gemm");
+    gemm(ctx, false, false, 1.0, Zc, Vr, 0.0, out.T, nullptr, "bal_gemm");
+    scale_cols(ctx, out.W, S_dev);
+    scale_cols(ctx, out.T, S_dev);
+    Mat XT(ctx, n, r), I(ctx, r, r);
+    gemm(ctx, false, false, 1.0, A, out.T, 0.0, XT, nullptr, "bal_gemm");
+    gemm(ctx, true, false, 1.0, out.W, XT, 0.0, out.Ar, nullptr, "bal_gemm");
+    if (B.cols) gemm(ctx, true, false, 1.0, out.W, B, 0.0, out.Br, nullptr, "bal_gemm");
+    if (C.rows) gemm(ctx, false, false, 1.0, C, out.T, 0.0, out.Cr, nullptr, "bal_gemm");
+    gemm(ctx, false, false, 1.0, E, out.T, 0.0, XT, nullptr, "bal_gemm");
+    set_identity(ctx, I, 1.0);
+    gemm(ctx, true, false, 1.0, out.W, XT, -1.0, I, nullptr, "bal_gemm");
+    out.eye_err = frob_norm_host(ctx, I);
+}
+
 }  // namespace
 
 BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do,
@@ -119,84 +157,11 @@ BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, con
     SvdResult sv = svd_jacobi(ctx, M, 0.0, &st);
     out.hsv = sv.S;
     out.rank = st.rank; out.sweeps = st.sweeps;
-
-    int r = order;
-    if (order > 0) {
-        if (order > st.rank)
-            throw Error(ERR_INVALID, "balance_lr: the requested order " + std::to_string(order) + " is above the numerical rank " + std::to_string(st.rank));
-    } else {
-        // the smallest r with 2 sum_{i > r} sigma_i <= tol sigma_1, the tail summed from the smallest sigma upward
-        r = k;
-        double tail = 0.0;
-        while (r > 0 && 2.0 * (tail + sv.s[r - 1]) <= tol * sv.s[0]) { tail += sv.s[r - 1]; --r; }
-        r = (int)std::min<long>(r, st.rank);
-    }
-    out.order = r;
-    { double tail = 0.0; for (int i = k - 1; i >= r; --i) tail += sv.s[i]; out.bound = 2.0 * tail; }
-
-    out.W = Mat(ctx, n, r); out.T = Mat(ctx, n, r);
-    out.Ar = Mat(ctx, r, r); out.Br = Mat(ctx, r, B.cols); out.Cr = Mat(ctx, C.rows, r);
-    if (r == 0) return out;
-    const Mat Ur = sv.U.colsview(0, r), Vr = sv.V.colsview(0, r);
-    gemm(ctx, false, false, 1.0, Zo, Ur, 0.0, out.W, nullptr, "bal_gemm");
-    gemm(ctx, false, false, 1.0, Zc, Vr, 0.0, out.T, nullptr, "bal_gemm");
-    scale_cols(ctx, out.W, sv.S.p);
-    scale_cols(ctx, out.T, sv.S.p);
-    Mat XT(ctx, n, r), I(ctx, r, r);
-    gemm(ctx, false, false, 1.0, A, out.T, 0.0, XT, nullptr, "bal_gemm");
-    gemm(ctx, true, false, 1.0, out.W, XT, 0.0, out.Ar, nullptr, "bal_gemm");
-    if (B.cols) gemm(ctx, true, false, 1.0, out.W, B, 0.0, out.Br, nullptr, "bal_gemm");
-    if (C.rows) gemm(ctx, false, false, 1.0, C, out.T, 0.0, out.Cr, nullptr, "bal_gemm");
-    gemm(ctx, false, false, 1.0, E, out.T, 0.0, XT, nullptr, "bal_gemm");
-    set_identity(ctx, I, 1.0);
-    gemm(ctx, true, false, 1.0, out.W, XT, -1.0, I, nullptr, "bal_gemm");
-    out.eye_err = frob_norm_host(ctx, I);
+    balance_member_finish(ctx, E, A, B, C, Zc, Zo, sv.U, sv.V, sv.s, sv.S.p, st.rank, order, tol, out);
     return out;
 }
 
 // ---- ensemble form ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// steps (4)-(7) of balance_lr for one member after the shared SVD: U, V are the member's blocks of the padded factors (r_o x k' and r_c x k'),
-// s the singular values on the host (the member's first k = min(r_o, r_c)), S_dev the same on the device
-void balance_member_finish(Ctx* ctx, const BalanceMember& mb, const Mat& Zc, const Mat& Zo, const Mat& U, const Mat& V, const std::vector<double>& s,
-                           const double* S_dev, long rank, int order, double tol, BalanceResult& out) {
-    const Mat &E = *mb.E, &A = *mb.A, &B = *mb.B, &C = *mb.C;
-    const int n = E.rows, k = std::min(out.r_c, out.r_o);
-    int r = order;
-    if (order > 0) {
-        if (order > rank)
-            throw Error(ERR_INVALID, "balance_lr: the requested order " + std::to_string(order) + " is above the numerical rank " + std::to_string(rank));
-    } else {
-        r = k;
-        double tail = 0.0;
-        while (r > 0 && 2.0 * (tail + s[r - 1]) <= tol * s[0]) { tail += s[r - 1]; --r; }
-        r = (int)std::min<long>(r, rank);
-    }
-    out.order = r;
-    { double tail = 0.0; for (int i = k - 1; i >= r; --i) tail += s[i]; out.bound = 2.0 * tail; }
-
-    out.W = Mat(ctx, n, r); out.T = Mat(ctx, n, r);
-    out.Ar = Mat(ctx, r, r); out.Br = Mat(ctx, r, B.cols); out.Cr = Mat(ctx, C.rows, r);
-    if (r == 0) return;
-    const Mat Ur = U.colsview(0, r), Vr = V.colsview(0, r);
-    gemm(ctx, false, false, 1.0, Zo, Ur, 0.0, out.W, nullptr, "bal_gemm");
-    gemm(ctx, false, false, 1.0, Zc, Vr, 0.0, out.T, nullptr, "bal_gemm");
-    scale_cols(ctx, out.W, S_dev);
-    scale_cols(ctx, out.T, S_dev);
-    Mat XT(ctx, n, r), I(ctx, r, r);
-    gemm(ctx, false, false, 1.0, A, out.T, 0.0, XT, nullptr, "bal_gemm");
-    gemm(ctx, true, false, 1.0, out.W, XT, 0.0, out.Ar, nullptr, "bal_gemm");
-    if (B.cols) gemm(ctx, true, false, 1.0, out.W, B, 0.0, out.Br, nullptr, "bal_gemm");
-    if (C.rows) gemm(ctx, false, false, 1.0, C, out.T, 0.0, out.Cr, nullptr, "bal_gemm");
-    gemm(ctx, false, false, 1.0, E, out.T, 0.0, XT, nullptr, "bal_gemm");
-    set_identity(ctx, I, 1.0);
-    gemm(ctx, true, false, 1.0, out.W, XT, -1.0, I, nullptr, "bal_gemm");
-    out.eye_err = frob_norm_host(ctx, I);
-}
-
-}  // namespace
-
 BalanceBatch balance_lr_batch(Ctx* ctx, const std::vector<BalanceMember>& mem, int order, double tol, const char* who) {
     const std::string w_ = std::string(who) + ": ";
     DRE_REQUIRE(!mem.empty() && mem.size() <= (size_t)JACOBI_BATCH_MAX, w_ + "batch must be in 1 .. 65535");
@@ -278,24 +243,19 @@ BalanceBatch balance_lr_batch(Ctx* ctx, const std::vector<BalanceMember>& mem, i
             gemm(ctx, true, false, 1.0, fo[(size_t)b].Z, EZ, 0.0, M, nullptr, "bal_gemm");
             Ms.push_back(slotm);
         }
-        SvdBatch sv = svd_jacobi_batch(ctx, Ms, 0.0, who);
+        SvdBatch sv = svd_jacobi_run(ctx, Ms, 0.0, who, false);
         for (size_t i = 0; i < ids.size(); ++i) {
             const int b = ids[i];
             BalanceResult& r = out.res[(size_t)b];
-            if (sv.status[i].code) {
-                // (the SVD numbered the member inside its own batch)
-                const std::string& m0 = sv.status[i].msg;
-                const size_t at = m0.find(": ");
-                fail(b, Error(sv.status[i].code, at == std::string::npos ? m0 : m0.substr(at + 2)));
-                continue;
-            }
+            if (sv.status[i].code) { fail(b, Error(sv.status[i].code, sv.status[i].msg)); continue; }
             const int k = std::min(r.r_c, r.r_o);
             const SvdResult& s = sv.svd[i];
             r.hsv = s.S.view(0, 0, k, 1);
             r.rank = std::min<long>(sv.stats[i].rank, k); r.sweeps = sv.stats[i].sweeps;
             try {
-                balance_member_finish(ctx, mem[(size_t)b], fc[(size_t)b].Z, fo[(size_t)b].Z, s.U.view(0, 0, r.r_o, s.U.cols), s.V.view(0, 0, r.r_c, s.V.cols), s.s,
-                                      s.S.p, r.rank, order, tol, r);
+                const BalanceMember& mb = mem[(size_t)b];
+                balance_member_finish(ctx, *mb.E, *mb.A, *mb.B, *mb.C, fc[(size_t)b].Z, fo[(size_t)b].Z, s.U.view(0, 0, r.r_o, s.U.cols),
+                                      s.V.view(0, 0, r.r_c, s.V.cols), s.s, s.S.p, r.rank, order, tol, r);
             } catch (const Error& e) {
                 if (e.code != ERR_INVALID) throw;
                 fail(b, e);

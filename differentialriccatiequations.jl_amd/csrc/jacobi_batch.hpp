@@ -1,7 +1,7 @@
-// Member-indexed block Jacobi: the symmetric eigensolver of sym_jacobi.hip and the SVD of svd_jacobi.hip for an ensemble of same-size problems in
-// shared launches (jacobi_batch.hip).  See DESIGN.md §9.9.  Member b sits on the grid's y axis; a workgroup of member b does that member's
-// arithmetic of the single solver in the same order, so every output of a member is bit for bit what the single call returns for it, whatever
-// the other members are.  A member that is finished, non-finite or out of sweeps is skipped by every later launch (its workgroups return at
+// Block Jacobi for an ensemble of same-size problems in shared launches: the batch types and entry points of the symmetric eigensolver
+// (sym_jacobi.hip) and of the SVD (svd_jacobi.hip).  See DESIGN.md §9.9.  There is one kernel set: member b sits on the grid's y axis, and
+// sym_eig_jacobi / svd_jacobi are batches of one, so every output of a member is bit for bit what the single call returns for it, whatever the
+// other members are.  A member that is finished, non-finite or out of sweeps is skipped by every later launch (its workgroups return at
 // entry); the others go on.
 #pragma once
 #include <string>
@@ -14,17 +14,6 @@
 namespace dre {
 
 constexpr int JACOBI_BATCH_MAX = 65535;      // members at most (the grid's y axis)
-
-// Device-side control blocks, one per member: BjCtl / SvjCtl with the padding word used for "out of sweeps".  ctl[b] is written only by the
-// one-workgroup-per-member decide / init / fold kernels and read by the kernels enqueued after them on the same stream.
-struct BjbCtl {
-    double off, norm;
-    int sweeps, done, nonfinite, failed;     // failed: BJ_MAX_SWEEPS sweeps without convergence
-};
-struct SvjbCtl {
-    double norm, pad0_;
-    int sweeps, done, nonfinite, failed;     // failed: SVJ_MAX_SWEEPS sweeps with rotations
-};
 
 struct SymEigBatch {
     std::vector<SymEig> eig;                 // per member what sym_eig_jacobi returns (empty for a failed member)
@@ -45,5 +34,9 @@ SymEigBatch sym_eig_jacobi_batch(Ctx* ctx, const std::vector<Mat>& S, double tol
 // A[b]: one shape for all members (left untouched), the limits of svd_jacobi.  tol <= 0: sqrt(max(m, w)) eps.  The rotation rule, floor, sweep
 // caps, zero-column rule and numerical rank are per member, exactly those of svd_jacobi.
 SvdBatch svd_jacobi_batch(Ctx* ctx, const std::vector<Mat>& A, double tol = 0.0, const char* who = "svd_jacobi_batch");
+
+// The driver behind svd_jacobi (single) and svd_jacobi_batch, for a caller that words the failures itself: status[b].msg is only the "what"
+// of a member's failure, without "who" and the member's number.  single: the kernel-timer tags and the trace line of svd_jacobi.
+SvdBatch svd_jacobi_run(Ctx* ctx, const std::vector<Mat>& A, double tol, const char* who, bool single);
 
 }  // namespace dre

@@ -1,42 +1,31 @@
-// Device SVD: one-sided (Hestenes) cyclic block Jacobi (DESIGN.md §9.8; host model: tests/_svd_jacobi_model.py).
+// Device SVD: one-sided (Hestenes) cyclic block Jacobi (DESIGN.md §9.8, §9.9; host model: tests/_svd_jacobi_model.py).
 //
-// The m x w matrix (m >= w; a wide input is transposed once at the entry, U and V are swapped at the exit) is padded with zero columns to
+// The m x w matrix (m >= w; a wide input is transposed on the way in, U and V are swapped at the exit) is padded with zero columns to
 // W = 16 p (p >= 2) and cut into p column blocks of 16: the working copy G (m x W), V = I (W x W).  A sweep is the p - 1 (p even) or p (p odd:
-// one block sits out per round) rounds of the round-robin tournament of the blocks.  ONE launch per round (k_svj_round): one workgroup of 256
+// one block sits out per round) rounds of the round-robin tournament of the blocks.  ONE launch per round (k_svjb_round): one workgroup of 256
 // per block pair (i, j) forms H = [G_i G_j]'[G_i G_j] (32 x 32, v_mfma_f64_16x16x4_f64, row slabs of 64 through LDS), diagonalises it by cyclic
 // Jacobi in LDS (J accumulated) and, if anything was rotated, applies [G_i G_j] <- [G_i G_j] J and [V_i V_j] <- [V_i V_j] J on MFMA.  The pairs
 // of a round own disjoint columns, so G and V are updated in place; kernel boundaries are the only synchronisation between workgroups.  After
 // every sweep a one-workgroup kernel folds the `rotated` flags into the control block, which the host reads once per sweep; a sweep without a
 // rotation ends the iteration.
 //
-// Index arithmetic: row and column indices are ints below max(m, W) <= DENSE_MAX_N; every element offset is formed in size_t.
-#include "svd_jacobi.hpp"
-
-#include <algorithm>
+// Every launch carries the member b = blockIdx.y of an ensemble of same-shape matrices (jacobi_common.hpp); svd_jacobi is a batch of one.
+// Every member has its own control block, `rotated` flags and partial sums; nothing is summed across members and there are no atomics, so a
+// member's result does not depend on the others.  The host reads the B control blocks in one copy per sweep.
+//
+// Index arithmetic: row and column indices are ints below max(m, W) <= DENSE_MAX_N; every element offset and every member stride is a size_t.
 #include <cmath>
 #include <numeric>
 
-#include "dense_device.hpp"
 #include "dense_gj.hpp"
+#include "jacobi_common.hpp"
 #include "profiling.hpp"
 
 namespace dre {
 
 namespace {
 
-constexpr int SB = 16;                // column block
-constexpr int PB = 2 * SB;            // columns of a block pair, order of its Gram matrix
-constexpr int LDP = PB + 1;           // leading dimension of a 32 x 32 block in LDS (odd: rows and columns both walk over all banks)
 constexpr int LDX = SVJ_SLAB + 1;     // leading dimension of a 64 x 32 row slab in LDS
-constexpr int SVJ_INNER_MAX = 10;     // cyclic sweeps of a Gram block at most (ended by the first sweep without a rotation)
-
-// pair k (0 <= k < players / 2) of round `step` (0 <= step < players - 1) of the round-robin tournament of an even number of players
-// (the tournament of sym_jacobi.hip)
-__host__ __device__ inline void rr_pair(int players, int step, int k, int& a, int& b) {
-    const int m = players - 1;
-    if (k == 0) { a = m; b = step; }
-    else { a = (step + k) % m; b = (step - k + m) % m; }
-}
 
 // rows [r0, r0 + 64) of the column blocks c0 and c1 (first columns) of M (rows x ., leading dimension ld) into Xs; rows beyond `rows` are zero
 __device__ inline void svj_load_slab(const double* __restrict__ M, int rows, size_t ld, int c0, int c1, int r0, double* Xs) {
@@ -78,13 +67,20 @@ __device__ inline void svj_apply(double* __restrict__ M, int rows, size_t ld, in
 }
 
 // ---- one round -------------------------------------------------------------------------------------------------------------------------------
-// G: m x W (leading dimension ldg), V: W x W (leading dimension W); pairs: the round's block pairs (bi < bj); rotated: one flag per pair.
+// grid (np pairs of the round, B).  Gs: m x W per member (leading dimension ldg, member stride sg), Vs: W x W per member (stride sv); pairs: the
+// round's block pairs (bi < bj); rotateds: this round's np flags of member b at rotateds + b * rstride.
 // A rotation (r, c) is done when h_rc != 0, h_rr h_cc > 0, |h_rc| > tol sqrt(h_rr h_cc) and sqrt(h_rr h_cc) > (tol ||A||_F)^2; a skipped rotation is
 // the exact identity, so a zero padding column stays a zero column of G and a unit column of V.
-__global__ __launch_bounds__(256) void k_svj_round(int m, int W, double* __restrict__ G, size_t ldg, double* __restrict__ V, const int* __restrict__ pairs,
-                                                   const SvjCtl* __restrict__ ctl, double tol, int* __restrict__ rotated) {
+__global__ __launch_bounds__(256) void k_svjb_round(int m, int W, double* __restrict__ Gs, size_t ldg, size_t sg, double* __restrict__ Vs, size_t sv,
+                                                    const int* __restrict__ pairs, const SvjCtl* __restrict__ ctls, double tol,
+                                                    int* __restrict__ rotateds, size_t rstride) {
     __shared__ double Xs[LDX * PB], H[PB * LDP], J[PB * LDP], cs[2 * SB];
     __shared__ int flag;
+    const SvjCtl* ctl = ctls + blockIdx.y;
+    if (member_off(*ctl)) return;          // (uniform in the workgroup)
+    double* G = Gs + (size_t)blockIdx.y * sg;
+    double* V = Vs + (size_t)blockIdx.y * sv;
+    int* rotated = rotateds + (size_t)blockIdx.y * rstride;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4;
     const int c0 = pairs[2 * blockIdx.x] * SB, c1 = pairs[2 * blockIdx.x + 1] * SB;
     const double floor_ = (tol * ctl->norm) * (tol * ctl->norm);
@@ -105,67 +101,13 @@ __global__ __launch_bounds__(256) void k_svj_round(int m, int W, double* __restr
     if (tid == 0) flag = 0;
     __syncthreads();
 
-    // 2. cyclic Jacobi on H (16 disjoint rotations per step, 31 steps per sweep, round-robin order), J accumulated
-    int any = 0;
-    for (int sw = 0; sw < SVJ_INNER_MAX; ++sw) {
-        for (int step = 0; step < PB - 1; ++step) {
-            if (tid < SB) {
-                int a, b;
-                rr_pair(PB, step, tid, a, b);
-                const int p = a < b ? a : b, q = a < b ? b : a;
-                const double app = H[p + LDP * p], aqq = H[q + LDP * q], apq = H[p + LDP * q];
-                const double prod = app * aqq;
-                double c = 1.0, s = 0.0;
-                if (apq != 0.0 && prod > 0.0) {
-                    const double g = sqrt(prod);
-                    if (fabs(apq) > tol * g && g > floor_) {
-                        const double tau = (aqq - app) / (2.0 * apq);
-                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        c = 1.0 / sqrt(1.0 + t * t);
-                        s = t * c;
-                        flag = 1;
-                    }
-                }
-                cs[2 * tid] = c; cs[2 * tid + 1] = s;
-            }
-            __syncthreads();
-            // columns of H and of J: (H or J, pair k, row i)
-            for (int e = tid; e < 2 * SB * PB; e += 256) {
-                const int i = e & (PB - 1), k = (e >> 5) & (SB - 1);
-                double* M = e >= SB * PB ? J : H;
-                const double c = cs[2 * k], s = cs[2 * k + 1];
-                if (s != 0.0) {
-                    int a, b;
-                    rr_pair(PB, step, k, a, b);
-                    const int p = a < b ? a : b, q = a < b ? b : a;
-                    const double x = M[i + LDP * p], y = M[i + LDP * q];
-                    M[i + LDP * p] = c * x - s * y;
-                    M[i + LDP * q] = s * x + c * y;
-                }
-            }
-            __syncthreads();
-            // rows of H: (pair k, column j); the annihilated entries are set to zero exactly
-            for (int e = tid; e < SB * PB; e += 256) {
-                const int j = e & (PB - 1), k = e >> 5;
-                const double c = cs[2 * k], s = cs[2 * k + 1];
-                if (s != 0.0) {
-                    int a, b;
-                    rr_pair(PB, step, k, a, b);
-                    const int p = a < b ? a : b, q = a < b ? b : a;
-                    const double x = H[p + LDP * j], y = H[q + LDP * j];
-                    H[p + LDP * j] = j == q ? 0.0 : c * x - s * y;
-                    H[q + LDP * j] = j == p ? 0.0 : s * x + c * y;
-                }
-            }
-            __syncthreads();
-        }
-        const int f = flag;          // (uniform: every write of this sweep is behind a barrier)
-        __syncthreads();
-        if (tid == 0) flag = 0;
-        __syncthreads();
-        if (!f) break;
-        any = 1;
-    }
+    // 2. cyclic Jacobi on H, J accumulated
+    const int any = cyclic_jacobi_32(H, J, cs, &flag, INNER_MAX, [tol, floor_](double app, double aqq, double apq) {
+        const double prod = app * aqq;
+        if (!(apq != 0.0 && prod > 0.0)) return false;
+        const double g = sqrt(prod);
+        return fabs(apq) > tol * g && g > floor_;
+    });
     if (tid == 0) rotated[blockIdx.x] = any;
     if (!any) return;                // (uniform in the workgroup)
 
@@ -175,50 +117,72 @@ __global__ __launch_bounds__(256) void k_svj_round(int m, int W, double* __restr
 }
 
 // ---- control -------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_svj_sumsq(int rows, int cols, const double* __restrict__ A, size_t ld, double* __restrict__ part) {
+// grid (NORM_PARTS, B): the partial sums of member b in parts + NORM_PARTS b
+__global__ __launch_bounds__(256) void k_svjb_sumsq(int rows, int cols, const double* __restrict__ As, size_t ld, size_t stride, double* __restrict__ parts) {
+    const double* A = As + (size_t)blockIdx.y * stride;
     double s = 0.0;
     const size_t tot = (size_t)rows * (size_t)cols;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
         const double x = A[idx % (size_t)rows + (idx / (size_t)rows) * ld];
         s += x * x;
     }
-    store_partials(part, s);
+    store_partials(parts + (size_t)blockIdx.y * gridDim.x, s);
 }
 
-__global__ __launch_bounds__(256) void k_svj_init(int nparts, const double* __restrict__ part, SvjCtl* ctl) {
+// grid (B)
+__global__ __launch_bounds__(256) void k_svjb_init(int nparts, const double* __restrict__ parts, SvjCtl* ctls) {
+    SvjCtl* ctl = ctls + blockIdx.x;
     double s[1];
-    load_partials(nparts, part, s);
+    load_partials(nparts, parts + (size_t)blockIdx.x * nparts, s);
     if (threadIdx.x == 0) {
         const double norm = sqrt(s[0]);
         ctl->norm = norm; ctl->pad0_ = 0.0;
-        ctl->sweeps = 0; ctl->done = 0; ctl->pad_ = 0;
+        ctl->sweeps = 0; ctl->done = 0; ctl->failed = 0;
         ctl->nonfinite = isfinite(norm) ? 0 : 1;
     }
 }
 
-__global__ __launch_bounds__(256) void k_svj_fold(int n, const int* __restrict__ rotated, SvjCtl* ctl) {
+// grid (B): n flags per member at rotateds + b * n; a member still rotating after SVJ_MAX_SWEEPS sweeps is dropped here
+__global__ __launch_bounds__(256) void k_svjb_fold(int n, const int* __restrict__ rotateds, SvjCtl* ctls) {
+    SvjCtl* ctl = ctls + blockIdx.x;
+    if (member_off(*ctl)) return;          // (uniform in the workgroup)
+    const int* rotated = rotateds + (size_t)blockIdx.x * n;
     int any = 0;
     for (int i = threadIdx.x; i < n; i += 256) any |= rotated[i];
     any = __syncthreads_or(any);
-    if (threadIdx.x == 0) { ctl->sweeps += 1; ctl->done = any ? 0 : 1; }
+    if (threadIdx.x == 0) {
+        ctl->sweeps += 1; ctl->done = any ? 0 : 1;
+        ctl->failed = any && ctl->sweeps >= SVJ_MAX_SWEEPS ? 1 : 0;
+    }
 }
 
 // ---- exit ----------------------------------------------------------------------------------------------------------------------------------
-// one workgroup per column: sig[c] = ||G(:, c)||
-__global__ __launch_bounds__(256) void k_svj_colnorm(int m, const double* __restrict__ G, size_t ldg, double* __restrict__ sig) {
+// grid (w, B), one workgroup per column: sig[b w + c] = ||G_b(:, c)||
+__global__ __launch_bounds__(256) void k_svjb_colnorm(int m, const double* __restrict__ Gs, size_t ldg, size_t sg, double* __restrict__ sig) {
     __shared__ double red[17];
-    const double* g = G + (size_t)blockIdx.x * ldg;
+    const double* g = Gs + (size_t)blockIdx.y * sg + (size_t)blockIdx.x * ldg;
     double s = 0.0;
     for (int i = threadIdx.x; i < m; i += 256) s += g[i] * g[i];
     s = block_sum(s, red);
-    if (threadIdx.x == 0) sig[blockIdx.x] = sqrt(s);
+    if (threadIdx.x == 0) sig[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sqrt(s);
 }
 
-// U(:, j) = G(:, perm[j]) / sig[j] where sig[j] > thr, a zero column otherwise;  Vout(:, j) = V(0 .. w, perm[j])
-__global__ __launch_bounds__(256) void k_svj_gather(int m, int w, int k, const double* __restrict__ G, size_t ldg, const double* __restrict__ V, size_t ldv,
-                                                    const int* __restrict__ perm, const double* __restrict__ sig, double thr, double* __restrict__ U,
-                                                    size_t ldu, double* __restrict__ Vout, size_t ldvo) {
-    const size_t h = (size_t)m + (size_t)w, tot = h * (size_t)k;
+// grid (., B): U(:, j) = G(:, perm[j]) / sig[j] where sig[j] > thr = tol ||A_b||_F, a zero column otherwise;  Vout(:, j) = V(0 .. w, perm[j]).
+// perm and sig are w per member, U m x w, Vout w x w per member (contiguous)
+__global__ __launch_bounds__(256) void k_svjb_gather(int m, int w, const double* __restrict__ Gs, size_t ldg, size_t sg, const double* __restrict__ Vs, size_t ldv,
+                                                     size_t sv, const int* __restrict__ perms, const double* __restrict__ sigs, double tol,
+                                                     const SvjCtl* __restrict__ ctls, double* __restrict__ Us, double* __restrict__ Vouts) {
+    const SvjCtl* ctl = ctls + blockIdx.y;
+    if (ctl->nonfinite | ctl->failed) return;
+    const double thr = tol * ctl->norm;
+    const double* G = Gs + (size_t)blockIdx.y * sg;
+    const double* V = Vs + (size_t)blockIdx.y * sv;
+    const int* perm = perms + (size_t)blockIdx.y * w;
+    const double* sig = sigs + (size_t)blockIdx.y * w;
+    double* U = Us + (size_t)blockIdx.y * (size_t)m * (size_t)w;
+    double* Vout = Vouts + (size_t)blockIdx.y * (size_t)w * (size_t)w;
+    const size_t ldu = (size_t)m, ldvo = (size_t)w;
+    const size_t h = (size_t)m + (size_t)w, tot = h * (size_t)w;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
         const int j = (int)(idx / h), i = (int)(idx % h);
         const size_t src = (size_t)perm[j];
@@ -227,111 +191,142 @@ __global__ __launch_bounds__(256) void k_svj_gather(int m, int w, int k, const d
     }
 }
 
-// the tall case: A is m x w with m >= w >= 1
-SvdResult svd_tall(Ctx* ctx, const Mat& A, double tol, SvjStats* stats) {
-    const int m = A.rows, w = A.cols;
-    const int p = std::max(2, ceil_div(w, SB)), W = p * SB, players = p + (p & 1), nrounds = players - 1, np = p / 2;
-    SvdResult out;
-
-    // the schedule: per round the np block pairs (i < j)
-    std::vector<int> tab((size_t)nrounds * 2 * np);
-    for (int r = 0; r < nrounds; ++r) {
-        int* t = tab.data() + (size_t)r * 2 * np;
-        int cnt = 0;
-        for (int k = 0; k < players / 2; ++k) {
-            int a, b;
-            rr_pair(players, r, k, a, b);
-            if (a >= p || b >= p) continue;          // (the pair of the block that sits out)
-            t[2 * cnt] = std::min(a, b); t[2 * cnt + 1] = std::max(a, b); ++cnt;
-        }
-    }
-    DevArr<int> dtab(ctx, tab.size());
-    dtab.upload(ctx, tab);
-
-    Mat G(ctx, m, W), V(ctx, W, W);
-    if (W != w) fill_mat(ctx, G, 0.0);
-    { Mat left = G.view(0, 0, m, w); copy_mat(ctx, A, left); }
-    set_identity(ctx, V, 1.0);
-    DevArr<double> part(ctx, NORM_PARTS), dsig(ctx, w);
-    DevArr<int> rotated(ctx, (size_t)nrounds * np), dperm(ctx, w);
-    DevArr<SvjCtl> ctl(ctx, 1);
-    {
-        TimedScope ts(ctx, "svj_norm", 8.0 * m * w, 0.0, 2);
-        hipLaunchKernelGGL(k_svj_sumsq, dim3(NORM_PARTS), dim3(256), 0, ctx->stream, m, w, (const double*)A.p, (size_t)A.ld, part.p);
-        hipLaunchKernelGGL(k_svj_init, dim3(1), dim3(256), 0, ctx->stream, NORM_PARTS, (const double*)part.p, ctl.p);
-    }
-    SvjCtl h = read_back(ctx, ctl.p);
-    if (h.nonfinite) throw Error(ERR_INVALID, "svd_jacobi: the matrix has non-finite entries");
-    if (!(tol > 0.0)) tol = std::sqrt((double)m) * DBL_EPS;
-
-    long rounds = 0;
-    while (!h.done) {
-        if (h.sweeps >= SVJ_MAX_SWEEPS) throw Error(ERR_INTERNAL, "svd_jacobi: no convergence in " + std::to_string(h.sweeps) + " sweeps");
-        {
-            TimedScope ts(ctx, "svj_round", 16.0 * nrounds * ((double)m + W) * W, 2.0 * nrounds * np * (3.0 * m + 2.0 * W) * PB * PB, nrounds);
-            for (int r = 0; r < nrounds; ++r)
-                hipLaunchKernelGGL(k_svj_round, dim3(np), dim3(256), 0, ctx->stream, m, W, G.p, (size_t)G.ld, V.p, (const int*)(dtab.p + (size_t)r * 2 * np),
-                                   (const SvjCtl*)ctl.p, tol, rotated.p + (size_t)r * np);
-        }
-        rounds += nrounds;
-        hipLaunchKernelGGL(k_svj_fold, dim3(1), dim3(256), 0, ctx->stream, nrounds * np, (const int*)rotated.p, ctl.p);
-        h = read_back(ctx, ctl.p);
-    }
-    DRE_HIP(hipGetLastError());
-
-    // sigma = column norms, sorted on the host (stable, descending)
-    hipLaunchKernelGGL(k_svj_colnorm, dim3(w), dim3(256), 0, ctx->stream, m, (const double*)G.p, (size_t)G.ld, dsig.p);
-    std::vector<double> sig(w);
-    DRE_HIP(hipMemcpyAsync(sig.data(), dsig.p, (size_t)w * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sync();
-    std::vector<int> perm(w);
-    std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return sig[a] > sig[b]; });
-    out.s.resize(w);
-    for (int j = 0; j < w; ++j) out.s[j] = sig[perm[j]];
-    const double thr = tol * h.norm;
-    long rank = 0;
-    for (int j = 0; j < w; ++j) rank += out.s[j] > thr ? 1 : 0;
-    dperm.upload(ctx, perm);
-    out.S = Mat(ctx, w, 1);
-    DRE_HIP(hipMemcpyAsync(out.S.p, out.s.data(), (size_t)w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ctx->sync();
-    out.U = Mat(ctx, m, w);
-    out.V = Mat(ctx, w, w);
-    hipLaunchKernelGGL(k_svj_gather, dim3(grid_for(((size_t)m + w) * w)), dim3(256), 0, ctx->stream, m, w, w, (const double*)G.p, (size_t)G.ld,
-                       (const double*)V.p, (size_t)V.ld, (const int*)dperm.p, (const double*)out.S.p, thr, out.U.p, (size_t)out.U.ld, out.V.p,
-                       (size_t)out.V.ld);
-    DRE_HIP(hipGetLastError());
-    ctx->sync();
-    out.norm = h.norm;
-    if (env_trace("compress")) std::fprintf(stderr, "[svd_jacobi] %d x %d: %d sweeps, %ld rounds, rank %ld\n", m, w, h.sweeps, rounds, rank);
-    if (stats) { stats->sweeps = h.sweeps; stats->rounds = rounds; stats->rank = rank; }
-    return out;
+// a rows x cols view (contiguous columns) at `off` doubles into a stack
+Mat stack_view(const DevArr<double>& st, size_t off, int rows, int cols) {
+    Mat m;
+    m.buf = st.buf; m.p = st.p + off; m.rows = rows; m.cols = cols; m.ld = rows > 0 ? rows : 1;
+    return m;
 }
 
 }  // namespace
 
-SvdResult svd_jacobi(Ctx* ctx, const Mat& A, double tol, SvjStats* stats) {
-    if (stats) *stats = SvjStats{};
-    const int m = std::max(A.rows, A.cols), w = std::min(A.rows, A.cols);
-    DRE_REQUIRE(A.rows >= 0 && A.cols >= 0, "svd_jacobi: negative shape");
-    DRE_REQUIRE(w <= SVJ_MAX_W, "svd_jacobi: the shorter dimension is limited to 4096");
-    DRE_REQUIRE(m <= DENSE_MAX_N, "svd_jacobi: the longer dimension is beyond the device's 32-bit index limit");
-    DRE_REQUIRE(std::isfinite(tol), "svd_jacobi: tol is not finite");
+SvdBatch svd_jacobi_run(Ctx* ctx, const std::vector<Mat>& A, double tol, const char* who, bool single) {
+    check_batch(A, who);
+    const int B = (int)A.size(), rows = A[0].rows, cols = A[0].cols;
+    const int m = std::max(rows, cols), w = std::min(rows, cols);
+    const bool wide = rows < cols;
+    DRE_REQUIRE(rows >= 0 && cols >= 0, std::string(who) + ": negative shape");
+    DRE_REQUIRE(w <= SVJ_MAX_W, std::string(who) + ": the shorter dimension is limited to 4096");
+    DRE_REQUIRE(m <= DENSE_MAX_N, std::string(who) + ": the longer dimension is beyond the device's 32-bit index limit");
+    DRE_REQUIRE(std::isfinite(tol), std::string(who) + ": tol is not finite");
+    SvdBatch out;
+    out.svd.resize((size_t)B); out.stats.resize((size_t)B); out.status.resize((size_t)B);
     if (w == 0) {
-        SvdResult out;
-        out.U = Mat(ctx, A.rows, 0); out.S = Mat(ctx, 0, 1); out.V = Mat(ctx, A.cols, 0);
+        for (auto& r : out.svd) { r.U = Mat(ctx, rows, 0); r.S = Mat(ctx, 0, 1); r.V = Mat(ctx, cols, 0); }
         return out;
     }
-    const size_t W = (size_t)std::max(2, ceil_div(w, SB)) * SB;
-    // G, V, the outputs U and V, the transposed copy of a wide input, partial sums and the small arrays
-    require_memory(ctx, (size_t)m * W + W * W + 2 * (size_t)m * w + (size_t)w * w + NORM_PARTS + 4 * W + (W / SB) * (W / SB));
-    if (A.rows >= A.cols) return svd_tall(ctx, A, tol, stats);
-    Mat At(ctx, A.cols, A.rows);
-    transpose_mat(ctx, A, At);
-    SvdResult out = svd_tall(ctx, At, tol, stats);
-    std::swap(out.U, out.V);
+    const int p = std::max(2, ceil_div(w, SB)), W = p * SB, nrounds = p - 1 + (p & 1), np = p / 2;
+    const size_t sg = (size_t)m * W, sv = (size_t)W * W, ldg = (size_t)m, nrot = (size_t)nrounds * np;
+    // per member: G, V, the outputs, partial sums and the small arrays
+    require_memory(ctx, (size_t)B * (sg + sv + 2 * (size_t)m * w + (size_t)w * w + NORM_PARTS + 4 * (size_t)W + (size_t)(W / SB) * (W / SB)));
+
+    const std::vector<int> tab = rr_schedule(p, false);
+    DevArr<int> dtab(ctx, tab.size());
+    dtab.upload(ctx, tab);
+
+    // G_b = [A_b 0] (m x W; a wide member is transposed on the way in), V_b = I
+    DevArr<double> G(ctx, (size_t)B * sg), V(ctx, (size_t)B * sv), part(ctx, (size_t)B * NORM_PARTS), dsig(ctx, (size_t)B * w);
+    DevArr<int> rotated(ctx, (size_t)B * nrot), dperm(ctx, (size_t)B * w);
+    DevArr<SvjCtl> ctl(ctx, (size_t)B);
+    if (W != w) DRE_HIP(hipMemsetAsync(G.p, 0, (size_t)B * sg * sizeof(double), ctx->stream));
+    if (wide) {
+        for (int b = 0; b < B; ++b) { Mat left = stack_view(G, (size_t)b * sg, m, w); transpose_mat(ctx, A[(size_t)b], left); }
+    } else {
+        std::vector<CopyDesc> cp((size_t)B);
+        for (int b = 0; b < B; ++b) cp[(size_t)b] = CopyDesc{A[(size_t)b].p, G.p + (size_t)b * sg, m, w, A[(size_t)b].ld, m};
+        copy_batched(ctx, cp);
+    }
+    hipLaunchKernelGGL(k_jb_eye, dim3(grid_for(sv), B), dim3(256), 0, ctx->stream, W, V.p, sv);
+    {
+        TimedScope ts(ctx, single ? "svj_norm" : "svjb_norm", 8.0 * B * m * w, 0.0, 2);
+        hipLaunchKernelGGL(k_svjb_sumsq, dim3(NORM_PARTS, B), dim3(256), 0, ctx->stream, m, w, (const double*)G.p, ldg, sg, part.p);
+        hipLaunchKernelGGL(k_svjb_init, dim3(B), dim3(256), 0, ctx->stream, NORM_PARTS, (const double*)part.p, ctl.p);
+    }
+    std::vector<SvjCtl> h((size_t)B);
+    fetch_ctl(ctx, ctl, h);
+    if (!(tol > 0.0)) tol = std::sqrt((double)m) * DBL_EPS;
+    auto judge = [&] {
+        bool live = false;
+        for (int b = 0; b < B; ++b) {
+            if (h[(size_t)b].done || out.status[(size_t)b].code) continue;
+            if (h[(size_t)b].nonfinite) out.status[(size_t)b] = {ERR_INVALID, "the matrix has non-finite entries"};
+            else if (h[(size_t)b].failed) out.status[(size_t)b] = {ERR_INTERNAL, "no convergence in " + std::to_string(h[(size_t)b].sweeps) + " sweeps"};
+            else live = true;
+        }
+        return live;
+    };
+    bool live = judge();
+    while (live) {
+        {
+            TimedScope ts(ctx, single ? "svj_round" : "svjb_round", 16.0 * B * nrounds * ((double)m + W) * W, 2.0 * B * nrounds * np * (3.0 * m + 2.0 * W) * PB * PB,
+                          nrounds);
+            for (int r = 0; r < nrounds; ++r)
+                hipLaunchKernelGGL(k_svjb_round, dim3(np, B), dim3(256), 0, ctx->stream, m, W, G.p, ldg, sg, V.p, sv, (const int*)(dtab.p + (size_t)r * 2 * np),
+                                   (const SvjCtl*)ctl.p, tol, rotated.p + (size_t)r * np, nrot);
+        }
+        hipLaunchKernelGGL(k_svjb_fold, dim3(B), dim3(256), 0, ctx->stream, (int)nrot, (const int*)rotated.p, ctl.p);
+        fetch_ctl(ctx, ctl, h);
+        live = judge();
+    }
+    DRE_HIP(hipGetLastError());
+
+    // sigma = column norms of every member in one copy, sorted per member on the host (stable, descending); the permutations in one upload
+    hipLaunchKernelGGL(k_svjb_colnorm, dim3(w, B), dim3(256), 0, ctx->stream, m, (const double*)G.p, ldg, sg, dsig.p);
+    std::vector<double> sig((size_t)B * w), ssort((size_t)B * w);
+    DRE_HIP(hipMemcpyAsync(sig.data(), dsig.p, sig.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
+    std::vector<int> perm((size_t)B * w);
+    for (int b = 0; b < B; ++b) {
+        int* pb = perm.data() + (size_t)b * w;
+        const double* sb = sig.data() + (size_t)b * w;
+        std::iota(pb, pb + w, 0);
+        if (out.status[(size_t)b].code) continue;          // (a dropped member's columns are not looked at)
+        std::stable_sort(pb, pb + w, [&](int a, int c) { return sb[a] > sb[c]; });
+        SvdResult& r = out.svd[(size_t)b];
+        r.s.resize((size_t)w);
+        for (int j = 0; j < w; ++j) r.s[(size_t)j] = ssort[(size_t)b * w + j] = sb[pb[j]];
+        const double thr = tol * h[(size_t)b].norm;
+        long rank = 0;
+        for (int j = 0; j < w; ++j) rank += r.s[(size_t)j] > thr ? 1 : 0;
+        r.norm = h[(size_t)b].norm;
+        out.stats[(size_t)b].sweeps = h[(size_t)b].sweeps;
+        out.stats[(size_t)b].rounds = (long)nrounds * h[(size_t)b].sweeps;
+        out.stats[(size_t)b].rank = rank;
+    }
+    dperm.upload(ctx, perm);
+    DevArr<double> Ss(ctx, (size_t)B * w), Us(ctx, (size_t)B * m * w), Vo(ctx, (size_t)B * w * w);
+    Ss.upload(ctx, ssort);
+    hipLaunchKernelGGL(k_svjb_gather, dim3(grid_for(((size_t)m + w) * w), B), dim3(256), 0, ctx->stream, m, w, (const double*)G.p, ldg, sg, (const double*)V.p,
+                       (size_t)W, sv, (const int*)dperm.p, (const double*)Ss.p, tol, (const SvjCtl*)ctl.p, Us.p, Vo.p);
+    DRE_HIP(hipGetLastError());
+    ctx->sync();
+    for (int b = 0; b < B; ++b) {
+        if (out.status[(size_t)b].code) continue;
+        SvdResult& r = out.svd[(size_t)b];
+        const SvjStats& st = out.stats[(size_t)b];
+        r.S = stack_view(Ss, (size_t)b * w, w, 1);
+        r.U = stack_view(Us, (size_t)b * m * w, m, w);
+        r.V = stack_view(Vo, (size_t)b * w * w, w, w);
+        if (wide) std::swap(r.U, r.V);
+        if (!env_trace("compress")) continue;
+        if (single) std::fprintf(stderr, "[svd_jacobi] %d x %d: %ld sweeps, %ld rounds, rank %ld\n", m, w, st.sweeps, st.rounds, st.rank);
+        else std::fprintf(stderr, "[svd_jacobi_batch] member %d, %d x %d: %ld sweeps, rank %ld\n", b, rows, cols, st.sweeps, st.rank);
+    }
     return out;
+}
+
+SvdBatch svd_jacobi_batch(Ctx* ctx, const std::vector<Mat>& A, double tol, const char* who) {
+    SvdBatch out = svd_jacobi_run(ctx, A, tol, who, false);
+    name_members(out.status, who);
+    return out;
+}
+
+SvdResult svd_jacobi(Ctx* ctx, const Mat& A, double tol, SvjStats* stats) {
+    if (stats) *stats = SvjStats{};
+    SvdBatch r = svd_jacobi_run(ctx, {A}, tol, "svd_jacobi", true);
+    if (r.status[0].code) throw Error(r.status[0].code, "svd_jacobi: " + r.status[0].msg);
+    if (stats) *stats = r.stats[0];
+    return std::move(r.svd[0]);
 }
 
 }  // namespace dre

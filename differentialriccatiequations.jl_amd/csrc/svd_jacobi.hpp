@@ -13,15 +13,15 @@ constexpr int SVJ_MAX_SWEEPS = 60;      // block sweeps before DRE_ERR_INTERNAL 
 constexpr int SVJ_MAX_W = 4096;         // the shorter dimension at most
 constexpr int SVJ_SLAB = 64;            // rows of a slab staged through LDS
 
-// Device-side control block (shaped like BjCtl): written by the norm kernel at the entry and by the one-workgroup fold kernel after every
-// sweep, read back once per sweep.
+// Device-side control block (shaped like BjCtl), one per member: written only by the one-workgroup-per-member init kernel at the entry and
+// fold kernel after every sweep, read by the kernels enqueued after them on the same stream and read back once per sweep.
 struct SvjCtl {
     double norm;       // ||A||_F
     double pad0_;
     int sweeps;        // block sweeps done
     int done;          // the last sweep rotated nothing
     int nonfinite;     // ||A||_F is not finite
-    int pad_;
+    int failed;        // SVJ_MAX_SWEEPS sweeps with rotations
 };
 
 struct SvjStats { long sweeps = 0, rounds = 0, rank = 0; };

@@ -6,17 +6,17 @@
 namespace dre {
 
 constexpr int BJ_BLOCK = 16;          // block size b; a pivot block is 2 b x 2 b
-constexpr int BJ_INNER_MAX = 10;      // cyclic sweeps of a pivot block at most (ended by the first sweep without a rotation)
 constexpr int BJ_MAX_SWEEPS = 30;     // block sweeps before DRE_ERR_INTERNAL
 
-// Device-side control block, filled by the one-workgroup decide kernel after every sweep and read back once per sweep.
+// Device-side control block, one per member: written only by the one-workgroup-per-member decide kernel after every sweep, read by the kernels
+// enqueued after it on the same stream and read back once per sweep.
 struct BjCtl {
     double off;        // off(A) = Frobenius norm of the off-diagonal part
     double norm;       // ||A||_F
     int sweeps;        // block sweeps done
     int done;          // off <= tol * norm
     int nonfinite;     // ||A||_F is not finite
-    int pad_;
+    int failed;        // BJ_MAX_SWEEPS sweeps without convergence
 };
 
 struct BjStats { long sweeps = 0, rounds = 0; };

@@ -1,4 +1,4 @@
-"""Batched block Jacobi on the device (sym_eigh_batch, svd_jacobi_batch; csrc/jacobi_batch.hip) against the single solvers.
+"""Batched block Jacobi on the device (sym_eigh_batch, svd_jacobi_batch; csrc/sym_jacobi.hip, csrc/svd_jacobi.hip) against the single solvers.
 
 The contract is bitwise: every output array of every member of a batch equals what svd_jacobi / sym_eigh(method="jacobi") returns for that
 member alone (numpy.array_equal), and so do the sweeps, rounds and rank.  The members of a batch (tests/_jacobi_batch_cases.py) need different
