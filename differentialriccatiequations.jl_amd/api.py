@@ -2260,6 +2260,147 @@ def bt_error(E, A, B, C, rom, omega, chunk=None, ctx=None):
     return dict(max_error=float(err[k]), omega_at_max=float(w[k]), bound=bound, ratio=bound / float(err[k]) if err[k] > 0 else math.inf)
 
 
+# ------------------------------------------------------------------------------------------------
+# LQG balanced truncation from one Hamiltonian sign iteration               csrc/dense_are.hip, csrc/balance.hip
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class LQGReducedModel:
+    """ẋ_r = Ar x_r + Br u, y = Cr x_r (Er is the identity): the LQG balanced truncation of E ẋ = A x + B u, y = C x to order len(Ar); the plant
+    need not be stable.  mu: the LQG characteristic values; T, W: the projections (Wᵀ E T = I); Kr, Lr, Ac: the reduced-order LQG controller
+    ẋ_c = Ac x_c + Lr y, u = −Kr x_c with Kr = Brᵀ Σ_r, Lr = Σ_r Crᵀ, Ac = Ar − Br Kr − Lr Cr.  K: the full-order feedback BᵀXE that
+    `lqg_error` needs (None for a model that was put together by hand)."""
+    Er: np.ndarray
+    Ar: np.ndarray
+    Br: np.ndarray
+    Cr: np.ndarray
+    mu: np.ndarray
+    T: np.ndarray
+    W: np.ndarray
+    Kr: np.ndarray
+    Lr: np.ndarray
+    Ac: np.ndarray
+    K: np.ndarray | None = None
+
+    @property
+    def order(self):
+        return self.Ar.shape[0]
+
+    def controller(self):
+        """(Ac, Lr, Kr) of ẋ_c = Ac x_c + Lr y, u = −Kr x_c"""
+        return self.Ac, self.Lr, self.Kr
+
+    def freq_response(self, omega, D=None, **kw):
+        """H_r(iω) = Cr (iω I - Ar)⁻¹ Br (+ D) of the reduced model at every frequency of omega, on the device (as `ReducedModel.freq_response`)."""
+        return freq_response(self.Er, self.Ar, self.Br, self.Cr, omega, D=D, **kw)
+
+
+def _lqg_check(name, E, A, B, C, alg, order, tol, Rinv=None, S=None):
+    if not isinstance(alg, MatrixSign):
+        raise TypeError(f"{name} takes alg = MatrixSign(), not {type(alg).__name__} (both Riccati solutions come from the dense Hamiltonian sign "
+                        "iteration); nothing was run on the device")
+    Eh, Ah, Bh, Ch = (_dense_f64(M) for M in _balance_check(name, E, A, B, C, alg, order, tol))
+    n, m, q = Eh.shape[0], Bh.shape[1], Ch.shape[0]
+    if n < 1 or m < 1 or q < 1:
+        raise ValueError(f"{name}: n, m and q must be at least 1; got E {Eh.shape}, B {Bh.shape}, C {Ch.shape}; nothing was run on the device")
+    inner = []
+    for nm, M, k in (("Rinv", Rinv, m), ("S", S, q)):
+        if M is not None:
+            M = np.asarray(M, dtype=float)
+            if M.shape != (k, k):
+                raise ValueError(f"{name}: {nm} must be {k} x {k}, got {M.shape}; nothing was run on the device")
+            M = _dense_f64(M)
+        inner.append(M)
+    return Eh, Ah, Bh, Ch, inner[0], inner[1]
+
+
+def _gare_pair_device(ctx, alg, Ed, Ad, Bd, Ctd, Rd=None, Sd=None):
+    """`dre_dense_gare_solve_pair` on uploaded operands -> (X, Y) as device matrices and the info dict"""
+    maxiters, tol, max_refine = _sign_params(alg)
+    xp, yp = C.c_void_p(), C.c_void_p()
+    ii, dd = (C.c_int64 * 4)(), (C.c_double * 4)()
+    ptr = lambda u: u.ptr if u is not None else None                          # noqa: E731
+    ctx.chk(ctx.lib.dre_dense_gare_solve_pair(ctx.ptr, Ed.ptr, Ad.ptr, Bd.ptr, ptr(Rd), Ctd.ptr, ptr(Sd), maxiters, tol, max_refine, C.byref(xp),
+                                              C.byref(yp), ii, dd))
+    info = dict(iters=int(ii[0]), factorizations=1, regulator=dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1])),
+                filter=dict(iters=int(ii[2]), refinements=int(ii[3]), res0=float(dd[2]), res=float(dd[3])))
+    return dev.DenseMatrix(ctx, xp), dev.DenseMatrix(ctx, yp), info
+
+
+def solve_gare_pair(E, A, B, C, alg=MatrixSign(), Rinv=None, S=None, ctx=None, return_info=False):
+    """Both Riccati equations of LQG design from ONE sign iteration of the Hamiltonian pencil (`dre_dense_gare_solve_pair`) -> (X, Y):
+        AᵀXE + EᵀXA − EᵀXGXE + Q = 0   (regulator)        A Y Eᵀ + E Y Aᵀ − E Y Q Y Eᵀ + G = 0   (filter)        G = B R⁻¹ Bᵀ, Q = Cᵀ S C
+    (Rinv m x m and S q x q: None is the identity).  X is bit for bit what solve(GAREProblem(E, A, G, Q), MatrixSign()) returns; Y comes from
+    the transposed blocks of the same sign matrix and is refined on the dual closed loop A − E Y Q.  Open-loop unstable plants are fine as
+    long as (A, B, E) is stabilizable and (A, C, E) detectable.  return_info=True adds dict(iters, factorizations=1, regulator=dict(iters,
+    refinements, res0, res), filter=the same).  Wrong types and shapes are errors before anything runs on the device."""
+    name = "solve_gare_pair"
+    Eh, Ah, Bh, Ch, Rh, Sh = _lqg_check(name, E, A, B, C, alg, None, 0.0, Rinv, S)
+    ctx = ctx or dev.default_context()
+    ups = [ctx.upload(M) if M is not None else None for M in (Eh, Ah, Bh, np.asfortranarray(Ch.T), Rh, Sh)]
+    X, Y, info = _gare_pair_device(ctx, alg, *ups)
+    X, Y = X.numpy(), Y.numpy()
+    return ((X, Y), info) if return_info else (X, Y)
+
+
+def _lqg_balance(name, E, A, B, Cout, alg, order, tol, ctx):
+    Eh, Ah, Bh, Ch, _, _ = _lqg_check(name, E, A, B, Cout, alg, order, tol)
+    ctx = ctx or dev.default_context()
+    Ed, Ad, Bd, Cd, Ctd = (ctx.upload(M) for M in (Eh, Ah, Bh, Ch, np.asfortranarray(Ch.T)))
+    X, Y, pair = _gare_pair_device(ctx, alg, Ed, Ad, Bd, Ctd)
+    out = [C.c_void_p() for _ in range(9)]
+    ii, dd = (C.c_int64 * 6)(), (C.c_double * 3)()
+    ctx.chk(ctx.lib.dre_lqg_balance(ctx.ptr, Ed.ptr, Ad.ptr, Bd.ptr, Cd.ptr, X.ptr, Y.ptr, int(order or 0), float(tol), *(C.byref(p) for p in out), ii, dd))
+    mu, T, W, Ar, Br, Cr, Kr, Lr, Ac = (dev.DenseMatrix(ctx, p).numpy() for p in out)
+    info = dict(regulator=pair["regulator"], filter=pair["filter"], iters=pair["iters"], factorizations=1, order=int(ii[0]), rank=int(ii[1]),
+                r_c=int(ii[2]), r_o=int(ii[3]), dropped=int(ii[4]), svd_sweeps=int(ii[5]), eye_err=float(dd[0]), bound=float(dd[1]), neg_max=float(dd[2]))
+    K = Bh.T @ X.numpy() @ Eh
+    return LQGReducedModel(np.eye(Ar.shape[0]), Ar, Br, Cr, mu.ravel(), T, W, Kr, Lr, Ac, K), info
+
+
+def lqg_balanced_truncation(E, A, B, C, alg=MatrixSign(), order=None, tol=1e-8, ctx=None, return_info=False):
+    """LQG balanced truncation of E ẋ = A x + B u, y = C x on the device -> LQGReducedModel.  The pencil (A, E) need not be c-stable (only
+    stabilizable and detectable): instead of the Gramians the stabilizing solutions X and Y of the regulator and the filter Riccati equations
+    are balanced, and both come from ONE Hamiltonian sign iteration (`dre_dense_gare_solve_pair`).  `dre_lqg_balance` factors them, runs the
+    steps of `balanced_truncation` and adds the reduced-order LQG controller.
+    order: the reduced order (above the numerical rank: DREError(-1)); None: the smallest r with 2 Σ_{i>r} ν_i <= tol, ν_i = μ_i / √(1 + μ_i²)
+    (absolute: it bounds the error of the normalised right coprime factors, whose norm is 1).
+    return_info=True adds dict(iters, factorizations=1, regulator, filter (each dict(iters, refinements, res0, res)), order, rank, r_c, r_o,
+    dropped, svd_sweeps, eye_err = ||WᵀET - I||_F, bound = 2 Σ_{i>r} ν_i, neg_max).  Wrong types and shapes are errors before anything runs
+    on the device."""
+    red, info = _lqg_balance("lqg_balanced_truncation", E, A, B, C, alg, order, tol, ctx)
+    return (red, info) if return_info else red
+
+
+def lqg_characteristic_values(E, A, B, C, alg=MatrixSign(), ctx=None):
+    """The LQG characteristic values of E ẋ = A x + B u, y = C x, descending: the square roots of the eigenvalues of Y EᵀX E (the `mu` of
+    `lqg_balanced_truncation`)."""
+    return _lqg_balance("lqg_characteristic_values", E, A, B, C, alg, None, 0.0, ctx)[0].mu
+
+
+def lqg_error(E, A, B, C, rom, omega, chunk=None, ctx=None):
+    """LQG balanced truncation's guarantee, measured -> (err, bound): err = max_k ‖[N; M](iω_k) − [N_r; M_r](iω_k)‖₂ of the normalised right
+    coprime factors of the plant and of the LQGReducedModel `rom`, from two `freq_response` calls on (E, A − BK, B, [C; −K]) with
+    D = [0; I], K = BᵀXE, and on (I, Ar − Br Kr, Br, [Cr; −Kr]); bound = 2 Σ_{i>r} μ_i / √(1 + μ_i²).  K is taken from `rom`; a model
+    without it costs one regulator solve."""
+    name = "lqg_error"
+    if not isinstance(rom, LQGReducedModel):
+        raise TypeError(f"{name}: rom must be an LQGReducedModel, not {type(rom).__name__}; nothing was run on the device")
+    mats, w, _ = _freq_check(name, [(E, A, B, C)], omega, None, "raise", chunk)
+    Eh, Ah, Bh, Ch = mats[0]
+    m, q = Bh.shape[1], Ch.shape[0]
+    if (rom.Br.shape[1], rom.Cr.shape[0]) != (m, q):
+        raise ValueError(f"{name}: the reduced model has (m, q) = {(rom.Br.shape[1], rom.Cr.shape[0])}, the system {(m, q)}; nothing was run on the device")
+    K = rom.K
+    if K is None:
+        K = Bh.T @ solve_gare_pair(Eh, Ah, Bh, Ch, ctx=ctx)[0] @ Eh
+    Dn = np.vstack([np.zeros((q, m)), np.eye(m)])
+    H = freq_response(Eh, Ah - Bh @ K, Bh, np.vstack([Ch, -K]), w, D=Dn, chunk=chunk, ctx=ctx)
+    Hr = freq_response(rom.Er, rom.Ar - rom.Br @ rom.Kr, rom.Br, np.vstack([rom.Cr, -rom.Kr]), w, D=Dn, chunk=chunk, ctx=ctx)
+    err = float(np.linalg.svd(H - Hr, compute_uv=False)[:, 0].max())
+    mu = np.asarray(rom.mu, dtype=float)[rom.order:]
+    return err, 2.0 * float(np.sum((mu / np.sqrt(1.0 + mu * mu))[::-1]))
+
+
 def _solve_gdre_factored_sign(prob, alg, order, inner, dt, save_state, observer, ctx, return_stats):
     """solve(::GDREProblem{<:LDLᵀ}, ::Ros1/Ros2(FactoredSign()); dt, save_state, observer): the host-driven Rosenbrock loop with one kept sign
     factorisation per time step and one factored replay per stage.  The observe_gdre_* hooks fire as on the other paths; there are no ADI

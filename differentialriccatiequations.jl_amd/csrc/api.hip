@@ -84,7 +84,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 112; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 113; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -93,6 +93,7 @@ int dre_version(void) { return 112; }   // 101: dense path (dre_dense_gale_solve
                                         // 111: batched block Jacobi and ensemble balanced truncation (dre_sym_eig_jacobi_batched, dre_svd_jacobi_batched,
                                         //      dre_balance_lr_batched)
                                         // 112: frequency response batched by frequency (dre_freq_response, dre_freq_response_batched)
+                                        // 113: LQG balanced truncation from one Hamiltonian sign iteration (dre_dense_gare_solve_pair, dre_lqg_balance)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1354,6 +1355,18 @@ int dre_dense_gare_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, c
         *X = out;
     });
 }
+int dre_dense_gare_solve_pair(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                              const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, dre_dense** Y, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && B && Ct && X && Y, "dre_dense_gare_solve_pair: null argument");
+        DenseGarePair r = dense_gare_solve_pair(&ctx->c, E->m, A->m, B->m, Rinv ? &Rinv->m : nullptr, Ct->m, S ? &S->m : nullptr, maxiters, tol, max_refine);
+        if (iinfo) { iinfo[0] = r.X.iters; iinfo[1] = r.X.refinements; iinfo[2] = r.Y.iters; iinfo[3] = r.Y.refinements; }
+        if (dinfo) { dinfo[0] = r.X.res0; dinfo[1] = r.X.res; dinfo[2] = r.Y.res0; dinfo[3] = r.Y.res; }
+        auto Xo = std::make_unique<dre_dense>(), Yo = std::make_unique<dre_dense>();
+        Xo->m = std::move(r.X.X); Yo->m = std::move(r.Y.X);
+        *X = Xo.release(); *Y = Yo.release();
+    });
+}
 int dre_dense_gare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
                             const dre_dense* S, const dre_dense* X, dre_dense** Res, double* norm) {
     return guarded(ctx, [&] {
@@ -1736,6 +1749,25 @@ int dre_balance_lr(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const d
         if (ii) { ii[0] = r.order; ii[1] = r.rank; ii[2] = r.r_c; ii[3] = r.r_o; ii[4] = r.dropped; ii[5] = r.sweeps; }
         if (dd) { dd[0] = r.eye_err; dd[1] = r.bound; dd[2] = r.neg_max; }
         *hsv = o[0].release(); *T = o[1].release(); *W = o[2].release(); *Ar = o[3].release(); *Br = o[4].release(); *Cr = o[5].release();
+    });
+}
+// LQG balanced truncation from the two Riccati solutions (113)
+int dre_lqg_balance(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X, const dre_dense* Y,
+                    int order, double tol, dre_dense** mu, dre_dense** T, dre_dense** W, dre_dense** Ar, dre_dense** Br, dre_dense** Cr, dre_dense** Kr,
+                    dre_dense** Lr, dre_dense** Ac, int64_t* ii, double* dd) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(E && A && B && C && X && Y && mu && T && W && Ar && Br && Cr && Kr && Lr && Ac, "dre_lqg_balance: null argument");
+        LqgBalanceResult l = lqg_balance(c, E->m, A->m, B->m, C->m, X->m, Y->m, order, tol);
+        const BalanceResult& r = l.bal;
+        c->sync();
+        std::unique_ptr<dre_dense> o[9];
+        const Mat* src[9] = {&r.hsv, &r.T, &r.W, &r.Ar, &r.Br, &r.Cr, &l.Kr, &l.Lr, &l.Ac};
+        for (int i = 0; i < 9; ++i) { o[i] = std::make_unique<dre_dense>(); o[i]->m = *src[i]; }
+        if (ii) { ii[0] = r.order; ii[1] = r.rank; ii[2] = r.r_c; ii[3] = r.r_o; ii[4] = r.dropped; ii[5] = r.sweeps; }
+        if (dd) { dd[0] = r.eye_err; dd[1] = r.bound; dd[2] = r.neg_max; }
+        dre_dense** dst[9] = {mu, T, W, Ar, Br, Cr, Kr, Lr, Ac};
+        for (int i = 0; i < 9; ++i) *dst[i] = o[i].release();
     });
 }
 

@@ -16,6 +16,8 @@ namespace dre {
 
 namespace {
 
+enum OrderRule { ORDER_HANKEL, ORDER_LQG };      // order = 0: 2 sum_{i > r} sigma_i <= tol sigma_1 (balance_lr), 2 sum_{i > r} nu_i <= tol (lqg_balance)
+
 // Z(:, j) = L(:, idx[j]) * sqrt(d[idx[j] * stride])
 __global__ __launch_bounds__(256) void k_bal_sqrt_cols(int n, int cols, const double* __restrict__ L, size_t ldl, const double* __restrict__ d, size_t stride,
                                                        const int* __restrict__ idx, double* __restrict__ Z, size_t ldz) {
@@ -83,12 +85,20 @@ void scale_cols(Ctx* ctx, Mat& X, const double* s_dev) {
 // steps (4)-(7) for one system after the SVD: U, V are the factors of M (r_o x k' and r_c x k'; in a batch the member's blocks of the padded
 // factors), s the singular values on the host (the first k = min(r_o, r_c) count), S_dev the same on the device
 void balance_member_finish(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Zc, const Mat& Zo, const Mat& U, const Mat& V,
-                           const std::vector<double>& s, const double* S_dev, long rank, int order, double tol, BalanceResult& out) {
+                           const std::vector<double>& s, const double* S_dev, long rank, int order, double tol, BalanceResult& out,
+                           OrderRule rule = ORDER_HANKEL) {
     const int n = E.rows, k = std::min(out.r_c, out.r_o);
     int r = order;
+    auto nu = [&](int i) { return s[i] / std::sqrt(1.0 + s[i] * s[i]); };
     if (order > 0) {
         if (order > rank)
             throw Error(ERR_INVALID, "balance_lr: the requested order " + std::to_string(order) + " is above the numerical rank " + std::to_string(rank));
+    } else if (rule == ORDER_LQG) {
+        // the smallest r with 2 sum_{i > r} nu_i <= tol, nu_i = mu_i / sqrt(1 + mu_i^2): absolute, the normalised coprime factors have norm 1
+        r = k;
+        double tail = 0.0;
+        while (r > 0 && 2.0 * (tail + nu(r - 1)) <= tol) { tail += nu(r - 1); --r; }
+        r = (int)std::min<long>(r, rank);
     } else {
         // the smallest r with 2 sum_{i > r} sigma_i <= tol sigma_1, the tail summed from the smallest sigma upward
         r = k;
@@ -97,7 +107,7 @@ void balance_member_finish(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, c
         r = (int)std::min<long>(r, rank);
     }
     out.order = r;
-    { double tail = 0.0; for (int i = k - 1; i >= r; --i) tail += s[i]; out.bound = 2.0 * tail; }
+    { double tail = 0.0; for (int i = k - 1; i >= r; --i) tail += rule == ORDER_LQG ? nu(i) : s[i]; out.bound = 2.0 * tail; }
 
     out.W = Mat(ctx, n, r); out.T = Mat(ctx, n, r);
     out.Ar = Mat(ctx, r, r); out.Br = Mat(ctx, r, B.cols); out.Cr = Mat(ctx, C.rows, r);
@@ -118,10 +128,10 @@ void balance_member_finish(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, c
     out.eye_err = frob_norm_host(ctx, I);
 }
 
-}  // namespace
-
-BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do,
-                         int order, double tol) {
+// the argument checks of balance_lr and the size of its work space in doubles: Z_c, Z_o, E Z_c, M and its SVD (svd_jacobi checks its own share
+// again), the projections with their products, the reduced matrices
+size_t balance_check(const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do, int order,
+                     double tol) {
     const int n = E.rows;
     DRE_REQUIRE(n >= 1 && E.cols == n && A.rows == n && A.cols == n, "balance_lr: E and A must be n x n");
     DRE_REQUIRE(n <= DENSE_MAX_N, "balance_lr: order beyond the device's 32-bit index limit");
@@ -132,9 +142,13 @@ BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, con
     DRE_REQUIRE(order > 0 || (tol >= 0.0 && std::isfinite(tol)), "balance_lr: tol must be finite and non-negative");
     DRE_REQUIRE(std::min(Lc.cols, Lo.cols) <= SVJ_MAX_W, "balance_lr: more than 4096 columns in both Gramian factors");
     const size_t rc0 = Lc.cols, ro0 = Lo.cols, mb = B.cols, qc = C.rows;
-    // Z_c, Z_o, E Z_c, M and its SVD (svd_jacobi checks its own share again), the projections with their products, the reduced matrices
-    require_memory(ctx, (size_t)n * (2 * rc0 + ro0) + 6 * ro0 * rc0 + 4 * (size_t)n * std::min(rc0, ro0) + (mb + qc + std::min(rc0, ro0)) * std::min(rc0, ro0));
+    return (size_t)n * (2 * rc0 + ro0) + 6 * ro0 * rc0 + 4 * (size_t)n * std::min(rc0, ro0) + (mb + qc + std::min(rc0, ro0)) * std::min(rc0, ro0);
+}
 
+// steps (1)-(7) of balance_lr after its checks; rule: how order = 0 chooses r and what `bound` sums
+BalanceResult balance_core(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do,
+                           int order, double tol, OrderRule rule) {
+    const int n = E.rows;
     BalanceResult out;
     SqrtFactor fc = sqrt_factor(ctx, Lc, Dc), fo = sqrt_factor(ctx, Lo, Do);
     const Mat &Zc = fc.Z, &Zo = fo.Z;
@@ -157,7 +171,87 @@ BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, con
     SvdResult sv = svd_jacobi(ctx, M, 0.0, &st);
     out.hsv = sv.S;
     out.rank = st.rank; out.sweeps = st.sweeps;
-    balance_member_finish(ctx, E, A, B, C, Zc, Zo, sv.U, sv.V, sv.s, sv.S.p, st.rank, order, tol, out);
+    balance_member_finish(ctx, E, A, B, C, Zc, Zo, sv.U, sv.V, sv.s, sv.S.p, st.rank, order, tol, out, rule);
+    return out;
+}
+
+}  // namespace
+
+BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do,
+                         int order, double tol) {
+    require_memory(ctx, balance_check(E, A, B, C, Lc, Dc, Lo, Do, order, tol));
+    return balance_core(ctx, E, A, B, C, Lc, Dc, Lo, Do, order, tol, ORDER_HANKEL);
+}
+
+// ---- LQG balanced truncation -----------------------------------------------------------------------------------------------
+namespace {
+
+// S = L diag(d) L' by the Householder + QL solver, in the form dre_sym_eig returns it: d ascending (j x 1), L n x j (j < n after the early
+// termination on a low-rank S)
+void eig_factor(Ctx* ctx, const Mat& S, Mat& L, Mat& D) {
+    Mat W(ctx, S.rows, S.cols);
+    copy_mat(ctx, S, W);
+    struct Method0 { Ctx* c; int was; ~Method0() { c->sym_eig_method = was; } } method0{ctx, ctx->sym_eig_method};
+    ctx->sym_eig_method = 0;
+    SymEig e = sym_eig(ctx, W, 4.0);
+    std::vector<int> ids((size_t)e.j);
+    for (int i = 0; i < e.j; ++i) ids[(size_t)i] = i;
+    std::sort(ids.begin(), ids.end(), [&](int a, int b) { return e.w[(size_t)a] < e.w[(size_t)b]; });
+    std::vector<double> w((size_t)e.j);
+    for (int i = 0; i < e.j; ++i) w[(size_t)i] = e.w[(size_t)ids[(size_t)i]];
+    L = sym_eig_backtransform(ctx, e, ids);
+    D = Mat(ctx, e.j, 1);
+    if (e.j) {
+        DRE_HIP(hipMemcpyAsync(D.p, w.data(), (size_t)e.j * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        ctx->sync();          // (w is released on return)
+    }
+}
+
+}  // namespace
+
+LqgBalanceResult lqg_balance(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X, const Mat& Y, int order, double tol) {
+    const int n = E.rows;
+    DRE_REQUIRE(n >= 1 && E.cols == n && A.rows == n && A.cols == n, "lqg_balance: E and A must be n x n");
+    DRE_REQUIRE(n <= 8192, "lqg_balance: order above 8192 (the eigensolver that factors X and Y)");
+    DRE_REQUIRE(B.rows == n && C.cols == n && B.cols >= 1 && C.rows >= 1, "lqg_balance: B must be n x m and C q x n with m, q >= 1");
+    DRE_REQUIRE(X.rows == n && X.cols == n && Y.rows == n && Y.cols == n, "lqg_balance: X and Y must be n x n");
+    DRE_REQUIRE(order >= 0, "lqg_balance: negative order");
+    DRE_REQUIRE(order > 0 || (tol >= 0.0 && std::isfinite(tol)), "lqg_balance: tol must be finite and non-negative");
+    const size_t nn = (size_t)n * n, mb = B.cols, qc = C.rows;
+    // the two eigen-factors (2 n^2 + 2 n), one eigensolver's work at a time (copy, reflectors, tridiagonal vectors, back-transform: 4 n^2),
+    // balance_lr's work space at full rank, and the controller's matrices
+    require_memory(ctx, 6 * nn + 2 * (size_t)n + (3 * nn + 6 * nn + 4 * nn + (mb + qc + n) * n) + (2 * (mb + qc) + 2 * (size_t)n) * n);
+
+    Mat Lo, Do, Lc, Dc;
+    eig_factor(ctx, X, Lo, Do);
+    eig_factor(ctx, Y, Lc, Dc);
+    LqgBalanceResult out;
+    try {
+        balance_check(E, A, B, C, Lc, Dc, Lo, Do, order, tol);
+        out.bal = balance_core(ctx, E, A, B, C, Lc, Dc, Lo, Do, order, tol, ORDER_LQG);
+    } catch (const Error& e) {
+        std::string msg = e.what();
+        if (msg.rfind("balance_lr: ", 0) == 0) msg = "lqg_balance: " + msg.substr(12);
+        throw Error(e.code, msg);
+    }
+    // the reduced-order LQG controller x_c' = Ac x_c + Lr y, u = -Kr x_c:  Kr = Br' Sigma_r, Lr = Sigma_r Cr', Ac = Ar - Br Kr - Lr Cr
+    const int r = out.bal.order, m = B.cols, q = C.rows;
+    out.Kr = Mat(ctx, m, r); out.Lr = Mat(ctx, r, q); out.Ac = Mat(ctx, r, r);
+    if (r > 0) {
+        Mat Sig(ctx, r, r);
+        std::vector<double> mu((size_t)r), hs((size_t)r * Sig.ld, 0.0);          // Sigma_r, built on the host (r is small)
+        DRE_HIP(hipMemcpyAsync(mu.data(), out.bal.hsv.p, (size_t)r * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        for (int i = 0; i < r; ++i) hs[(size_t)i * ((size_t)Sig.ld + 1)] = mu[(size_t)i];
+        DRE_HIP(hipMemcpyAsync(Sig.p, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        ctx->sync();
+        gemm(ctx, true, false, 1.0, out.bal.Br, Sig, 0.0, out.Kr, nullptr, "bal_gemm");
+        gemm(ctx, false, true, 1.0, Sig, out.bal.Cr, 0.0, out.Lr, nullptr, "bal_gemm");
+        copy_mat(ctx, out.bal.Ar, out.Ac);
+        gemm(ctx, false, false, -1.0, out.bal.Br, out.Kr, 1.0, out.Ac, nullptr, "bal_gemm");
+        gemm(ctx, false, false, -1.0, out.Lr, out.bal.Cr, 1.0, out.Ac, nullptr, "bal_gemm");
+    }
+    ctx->sync();
     return out;
 }
 

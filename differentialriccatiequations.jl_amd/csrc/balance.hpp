@@ -27,6 +27,18 @@ struct BalanceResult {
 BalanceResult balance_lr(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& Lc, const Mat& Dc, const Mat& Lo, const Mat& Do,
                          int order, double tol);
 
+// LQG balanced truncation (host restatement tests/_lqg_model.py): X and Y are the dense stabilising solutions of the regulator
+// and the filter Riccati equations (dense_gare_solve_pair).  Both are factored by the Householder + QL eigensolver (non-positive eigenvalues are
+// left out) and balance_lr's steps run with (Lo, Do) from X and (Lc, Dc) from Y: bal.hsv holds the LQG characteristic values mu, and W'E T = I.
+// order = 0: the smallest r with 2 sum_{i > r} nu_i <= tol, nu_i = mu_i / sqrt(1 + mu_i^2) (absolute); bal.bound is that sum, the bound on the
+// error of the normalised right coprime factors.  The reduced-order controller x_c' = Ac x_c + Lr y, u = -Kr x_c comes with it:
+// Kr = Br' Sigma_r (m x r), Lr = Sigma_r Cr' (r x q), Ac = Ar - Br Kr - Lr Cr.  Shape errors are DRE_ERR_INVALID before any launch; n <= 8192.
+struct LqgBalanceResult {
+    BalanceResult bal;
+    Mat Kr, Lr, Ac;
+};
+LqgBalanceResult lqg_balance(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X, const Mat& Y, int order, double tol);
+
 // Ensemble form: the members share (n, m, q); each has its own E, A, B, C and factored Gramians, whose ranks may differ.  Every
 // M_b = Z_o'(E Z_c) is written into a zero-filled stack of the common shape (max_b r_o) x (max_b r_c) and ONE svd_jacobi_batch diagonalises the
 // stack; the order rule, the projections and the reduced matrices then run per member with balance_lr's steps, the member's own r_o and r_c

@@ -6,6 +6,14 @@
 //   (A - GXE)'DE + E'D(A - GXE) = -R(X), X <- X + D       Newton-Kleinman refinement with SignLyap on the closed loop.
 // Every kernel indexes n x n blocks of the 2n x 2n operands in size_t (2n <= DENSE_MAX_N).  The host model of exactly this solver is
 // tests/_hamiltonian_sign_model.py.
+//
+// dense_gare_solve_pair (host model tests/_lqg_model.py) returns, from the SAME sign iteration, also the filter solution Y of
+//   G + A Y E' + E Y A' - E Y Q Y E' = 0:   its pencil is (H', K'), whose Z_inf is Z_inf', so
+//   (Z_inf' + K')[I; Y E'] = 0              extraction from the transposed blocks, M_f = [Z21'; Z22' + E], rhs_f = -[Z11' + E'; Z12'] (k_are_extract_ops_t),
+//   F_f D E' + E D F_f' = -R_f(Y)           Newton-Kleinman on the dual closed loop F_f = A - E Y Q with SignLyap::solve_t.
+// The dual extraction runs first, in Zi, and leaves Z untouched; the regulator's extraction then runs exactly as in the single call.  Memory,
+// checked before any kernel: the single call's 24 n^2 plus Y, 25 n^2; with refinement SignLyap's (maxiters + 10) n^2 and the step's two n x n
+// (the regulator's and the filter's residual and step matrices are live one after the other and share the pool's blocks).
 #include "dense_are.hpp"
 
 #include <cmath>
@@ -127,6 +135,44 @@ __global__ __launch_bounds__(256) void k_are_extract_ops(int n, const double* __
     }
 }
 
+// the filter's extraction operands from the transposed blocks: M_f = [Z21'; Z22' + E] into Zi(:, 0:n), rhs_f = -[Z11' + E'; Z12'] into Zi(:, n:2n)
+// (ld 2n; E ld n).  One workgroup per 32 x 32 tile of the n x n blocks: the source tile (rows j0.., columns i0..) is read along its columns
+// into LDS (33 doubles per row: no bank conflicts on the transposed read-out) and written along the destination's columns, so both sides of
+// each of the four transpositions are coalesced.  The untransposed E of the second block is read at the destination index.
+__global__ __launch_bounds__(256) void k_are_extract_ops_t(int n, const double* __restrict__ Z, const double* __restrict__ E, double* __restrict__ Zi) {
+    __shared__ double tile[32][33];
+    const size_t L = 2 * (size_t)n, N = (size_t)n;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                      // 32 x 8
+    const size_t i0 = (size_t)blockIdx.x * 32, j0 = (size_t)blockIdx.y * 32;     // destination rows i0.., columns j0..
+#pragma unroll 1
+    for (int blk = 0; blk < 4; ++blk) {
+        // blk 0: Z21' -> (0, 0);  1: Z22' + E -> (n, 0);  2: -(Z11 + E)' -> (0, n);  3: -Z12' -> (n, n)
+        const size_t sr = blk < 2 ? N : 0, sc = (blk == 1 || blk == 3) ? N : 0;
+        const size_t dr = (blk & 1) ? N : 0, dc = blk < 2 ? 0 : N;
+        const size_t js = j0 + tx;                                               // source row
+        for (int k = ty; k < 32; k += 8) {
+            const size_t is = i0 + k;                                            // source column
+            double v = 0.0;
+            if (js < N && is < N) {
+                v = Z[(sr + js) + (sc + is) * L];
+                if (blk == 2) v += E[js + is * N];
+            }
+            tile[k][tx] = v;
+        }
+        __syncthreads();
+        const size_t id = i0 + tx;                                               // destination row
+        for (int k = ty; k < 32; k += 8) {
+            const size_t jd = j0 + k;                                            // destination column
+            if (id < N && jd < N) {
+                double v = tile[tx][k];
+                if (blk == 1) v += E[id + jd * N];
+                Zi[(dr + id) + (dc + jd) * L] = blk < 2 ? v : -v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // Res = sym(Q) + AXE + AXE' - sym(XGX) and the partial sums of ||Res||^2, ||Q||^2, ||AXE||^2, ||XGX||^2 (all n x n, ld n)
 __global__ __launch_bounds__(256) void k_are_residual(int n, const double* __restrict__ Q, const double* __restrict__ AXE, const double* __restrict__ XGX,
                                                       double* __restrict__ Res, double* __restrict__ part) {
@@ -176,22 +222,25 @@ void check_operands(const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, c
     DRE_REQUIRE(!S || (S->rows == Ct.cols && S->cols == Ct.cols), "dense GARE: S must be q x q");
 }
 
+// The regulator's residual and, with dual = true and the roles of G and Q exchanged by the caller, the filter's: R_f(Y) = G + A Y E' + E Y A' - E Y Q Y E'
+// is the same chain with the transposition flags of its first two GEMMs flipped (XE holds Y E', AXE holds A Y E', GXE holds Q Y E').
 struct Residual {
     Ctx* c;
     const Mat &E, &A, &G, &Q;
+    const bool tE, tA;          // X op(E) and op(A) (X op(E)): regulator (N, T), filter (T, N)
     Mat XE, AXE, GXE, XGX, Res;
     DevArr<double> part;
     DevArr<AreCtl> ctl;
-    Residual(Ctx* ctx, const Mat& E_, const Mat& A_, const Mat& G_, const Mat& Q_, const DevArr<AreCtl>& ctl_)
-        : c(ctx), E(E_), A(A_), G(G_), Q(Q_), part(ctx, 4 * NORM_PARTS), ctl(ctl_) {
+    Residual(Ctx* ctx, const Mat& E_, const Mat& A_, const Mat& G_, const Mat& Q_, const DevArr<AreCtl>& ctl_, bool dual = false)
+        : c(ctx), E(E_), A(A_), G(G_), Q(Q_), tE(dual), tA(!dual), part(ctx, 4 * NORM_PARTS), ctl(ctl_) {
         const int n = E.rows;
         XE = Mat(c, n, n); AXE = Mat(c, n, n); GXE = Mat(c, n, n); XGX = Mat(c, n, n); Res = Mat(c, n, n);
     }
     // Res = R(X); returns the scaled residual, *fro = ||R(X)||_F (synchronising)
     double eval(const Mat& X, double* fro = nullptr) {
         const int n = E.rows;
-        gemm(c, false, false, 1.0, X, E, 0.0, XE, nullptr, "are_residual");        // X E
-        gemm(c, true, false, 1.0, A, XE, 0.0, AXE, nullptr, "are_residual");       // A' X E
+        gemm(c, false, tE, 1.0, X, E, 0.0, XE, nullptr, "are_residual");           // X E
+        gemm(c, tA, false, 1.0, A, XE, 0.0, AXE, nullptr, "are_residual");         // A' X E
         gemm(c, false, false, 1.0, G, XE, 0.0, GXE, nullptr, "are_residual");      // G X E
         gemm(c, true, false, 1.0, XE, GXE, 0.0, XGX, nullptr, "are_residual");     // E' X G X E
         {
@@ -223,8 +272,46 @@ Mat dense_gare_residual(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, cons
     return r.Res;
 }
 
-DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S, int maxiters,
-                                 double tol, int max_refine) {
+namespace {
+
+// One solution's refinement: Newton-Kleinman steps on res (the regulator's Residual, or the filter's with dual = true) while the scaled residual
+// exceeds the target and decreases.  who: empty in the single call, else the solution's name for the messages of the pair call.
+void refine(Ctx* ctx, Residual& res, SignLyap* lyap, const Mat& A, int max_refine, bool dual, const char* who, DenseGareResult& out) {
+    const int n = A.rows;
+    out.res0 = out.res = res.eval(out.X);
+    const double target = 100.0 * n * DBL_EPS;
+    auto axpby = [&](Mat& o, double a0, const Mat& M0, double a1, const Mat& M1) { comb(ctx, o, a0, M0, a1, &M1, 0.0, nullptr, false, "are_axpby"); };
+    if (lyap && out.res > target) {
+        Mat F(ctx, n, n), D(ctx, n, n), Xn(ctx, n, n);
+        while (out.res > target && out.refinements < max_refine) {
+            try {
+                if (dual) {
+                    gemm(ctx, true, false, 1.0, res.XE, res.G, 0.0, D, nullptr, "are_residual");   // (Y E')' Q = E Y Q  (res.G is the filter's Q)
+                    axpby(F, 1.0, A, -1.0, D);                                           // F_f = A - E Y Q
+                    lyap->factor(F);
+                    lyap->solve_t(res.Res, D);                                           // F_f D E' + E D F_f' = -R_f(Y)
+                } else {
+                    axpby(F, 1.0, A, -1.0, res.GXE);                                     // F = A - G X E
+                    lyap->factor(F);                                                     // NOT_STABLE: X is not the stabilizing solution
+                    lyap->solve(res.Res, D);                                             // F'DE + E'DF = -R(X)
+                }
+            } catch (const Error& e) {
+                if (!*who) throw;
+                throw Error(e.code, std::string("dense GARE pair, ") + who + " refinement: " + e.what());
+            }
+            axpby(Xn, 1.0, out.X, 1.0, D);
+            const double rn = res.eval(Xn);
+            ++out.refinements;
+            if (!(rn < out.res)) break;                                                  // stopped decreasing: keep the better iterate
+            std::swap(out.X, Xn);
+            out.res = rn;
+        }
+    }
+}
+
+// dense_gare_solve (dual null) and dense_gare_solve_pair (dual: receives the filter solution)
+DenseGareResult gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S, int maxiters, double tol,
+                           int max_refine, DenseGareResult* dual) {
     check_operands(E, A, B, Rinv, Ct, S);
     const int n = E.rows, n2 = 2 * n;
     gj_check_order(ctx, n2, "dense GARE (the Hamiltonian of order 2n)");
@@ -233,7 +320,8 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
     const double tol2 = tol > 0.0 ? tol : 10.0 * n2 * DBL_EPS;
     // Up-front memory check, before any kernel: Z, Zi (8 n^2), the extraction's QR (V, VT, grouped VT: 6 n^2; R: n^2), E^-1, G, Q, X and the
     // residual's five n x n work matrices (9 n^2): 24 n^2; with refinement also SignLyap's (maxiters + 10) n^2 and the step's two n x n.
-    const size_t own = 24;
+    // The pair call adds Y: 25 n^2 (the dual extraction works in Zi, its residual and step matrices follow the regulator's in the same blocks).
+    const size_t own = dual ? 25 : 24;
     std::unique_ptr<SignLyap> lyap;
     if (max_refine > 0) lyap.reset(new SignLyap(ctx, E, maxiters, tol, max_refine, own + 2));     // (its constructor checks the whole sum)
     else require_memory(ctx, own * (size_t)n * n);
@@ -293,6 +381,28 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
         throw Error(ERR_NOT_STABLE, "dense GARE: the sign iteration did not converge in " + std::to_string(maxiters) + " iterations (relative step " +
                                         std::to_string(h.step) + "; Hamiltonian eigenvalues on or near the imaginary axis?)");
 
+    // ---- pair: the filter's extraction first, [Z21'; Z22' + E] Yr = -[Z11' + E'; Z12'], Y = sym(Yr E^-T); it works in Zi and leaves Z as it is ----
+    if (dual) {
+        dual->iters = out.iters;
+        {
+            TimedScope ts(ctx, "are_extract_ops", 8.0 * 10 * n * n, 0.0);
+            const unsigned tiles = (unsigned)((n + 31) / 32);
+            hipLaunchKernelGGL(k_are_extract_ops_t, dim3(tiles, tiles), dim3(256), 0, ctx->stream, n, (const double*)Z.p, (const double*)E.p, Zi.p);
+        }
+        Mat M = Zi.colsview(0, n), rhs = Zi.colsview(n, n);
+        dual->X = Mat(ctx, n, n);
+        QRFact f = qr_factor(ctx, M);
+        qr_apply_q(ctx, f, rhs, true);
+        gj_invert(ctx, f.R, piv.p, ictl.p);
+        if (read_back(ctx, ictl.p).singular)
+            throw Error(ERR_SINGULAR, "dense GARE pair, filter: [Z21'; Z22' + E] is rank deficient (no stable deflating subspace of dimension n)");
+        const Mat top = rhs.view(0, 0, n, n);
+        gemm(ctx, false, false, 1.0, f.R, top, 0.0, T, nullptr, "are_extract");      // Yr = R^-1 (Q' rhs)(0:n, :)
+        Mat YEi = Zi.view(0, 0, n, n);                                               // (M and rhs are spent)
+        gemm(ctx, false, true, 1.0, T, Einv, 0.0, YEi, nullptr, "are_extract");      // Yr E^-T
+        comb(ctx, dual->X, 1.0, YEi, 0.0, nullptr, 0.0, nullptr, true, "are_sym", 3);
+    }
+
     // ---- extraction: [Z12; Z22 + E'] Y = -[Z11 + E; Z21] by Householder QR, X = sym(Y E^-1) ----
     {
         TimedScope ts(ctx, "are_extract_ops", 8.0 * 10 * n * n, 0.0);
@@ -305,7 +415,8 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
         qr_apply_q(ctx, f, rhs, true);                                               // Q' rhs
         gj_invert(ctx, f.R, piv.p, ictl.p);                                          // R^-1
         if (read_back(ctx, ictl.p).singular)
-            throw Error(ERR_SINGULAR, "dense GARE: [Z12; Z22 + E'] is rank deficient (no stable deflating subspace of dimension n)");
+            throw Error(ERR_SINGULAR, std::string(dual ? "dense GARE pair, regulator" : "dense GARE") +
+                                          ": [Z12; Z22 + E'] is rank deficient (no stable deflating subspace of dimension n)");
         const Mat top = rhs.view(0, 0, n, n);
         gemm(ctx, false, false, 1.0, f.R, top, 0.0, T, nullptr, "are_extract");      // Y = R^-1 (Q' rhs)(0:n, :)
         Mat YEi = Z.view(0, 0, n, n);
@@ -315,25 +426,29 @@ DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
     Z = Mat(); Zi = Mat(); M = Mat(); rhs = Mat();      // (back to the pool for the refinement)
 
     // ---- Newton-Kleinman refinement ----
-    Residual res(ctx, E, A, G, Q, actl);
-    out.res0 = out.res = res.eval(out.X);
-    const double target = 100.0 * n * DBL_EPS;
-    auto axpby = [&](Mat& o, double a0, const Mat& M0, double a1, const Mat& M1) { comb(ctx, o, a0, M0, a1, &M1, 0.0, nullptr, false, "are_axpby"); };
-    if (lyap && out.res > target) {
-        Mat F(ctx, n, n), D(ctx, n, n), Xn(ctx, n, n);
-        while (out.res > target && out.refinements < max_refine) {
-            axpby(F, 1.0, A, -1.0, res.GXE);                                         // F = A - G X E
-            lyap->factor(F);                                                         // NOT_STABLE: X is not the stabilizing solution
-            lyap->solve(res.Res, D);                                                 // F'DE + E'DF = -R(X)
-            axpby(Xn, 1.0, out.X, 1.0, D);
-            const double rn = res.eval(Xn);
-            ++out.refinements;
-            if (!(rn < out.res)) break;                                              // stopped decreasing: keep the better iterate
-            std::swap(out.X, Xn);
-            out.res = rn;
-        }
+    {
+        Residual res(ctx, E, A, G, Q, actl);
+        refine(ctx, res, lyap.get(), A, max_refine, false, dual ? "regulator" : "", out);
+    }
+    if (dual) {          // the filter's equation is the regulator's with G and Q exchanged and the pencil transposed
+        Residual res(ctx, E, A, Q, G, actl, true);
+        refine(ctx, res, lyap.get(), A, max_refine, true, "filter", *dual);
     }
     ctx->sync();
+    return out;
+}
+
+}  // namespace
+
+DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S, int maxiters,
+                                 double tol, int max_refine) {
+    return gare_solve(ctx, E, A, B, Rinv, Ct, S, maxiters, tol, max_refine, nullptr);
+}
+
+DenseGarePair dense_gare_solve_pair(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S, int maxiters,
+                                    double tol, int max_refine) {
+    DenseGarePair out;
+    out.X = gare_solve(ctx, E, A, B, Rinv, Ct, S, maxiters, tol, max_refine, &out.Y);
     return out;
 }
 

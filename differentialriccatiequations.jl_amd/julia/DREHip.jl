@@ -606,6 +606,7 @@ include("DREHipSignDual.jl")          # solve_dense_t, solve_lr_t: the dual equa
 include("DREHipBalance.jl")           # svd_jacobi, balanced_truncation: device SVD and balanced truncation (dre_version >= 110)
 include("DREHipBatchJacobi.jl")       # sym_eigh_batch, svd_jacobi_batch, balance_lr_batch: ensembles in shared launches (dre_version >= 111)
 include("DREHipFreq.jl")              # freq_response, sigma_response, bt_error: frequency response batched by frequency (dre_version >= 112)
+include("DREHipLQG.jl")               # solve_gare_pair, lqg_balanced_truncation, lqg_error: LQG balanced truncation (dre_version >= 113)
 
 """Dense GARE: Q + A'XE + E'XA - E'XGXE = 0 with G = β B R⁻¹ Bᵀ, Q = γ Cᵀ S C (riccati/types.jl:41-52), all dense.  `solve(prob, MatrixSign())`
 returns the stabilizing X from the sign function of the Hamiltonian pencil plus Newton-Kleinman refinement (DREError(-7) when the

@@ -437,6 +437,22 @@ int dre_dense_invert(dre_ctx* ctx, dre_dense* A, int32_t* piv, double* logabsdet
  * iinfo: [0] sign iterations [1] refinement steps;  dinfo: [0] scaled residual after extraction [1] final */
 int dre_dense_gare_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
                          const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo);
+/* Both Riccati solutions of LQG design from ONE Hamiltonian sign iteration (dre_version >= 113): *X as dre_dense_gare_solve returns it for the
+ * same arguments, bit for bit, and *Y, the stabilizing solution of the filter equation
+ *     G + A Y E' + E Y A' - E Y Q Y E' = 0.
+ * The filter's Hamiltonian pencil is the transpose (H', K') of the regulator's, and the sign iteration commutes with transposition, so Y is
+ * extracted from the transposed blocks of the same Z_inf: [Z21'; Z22' + E] Yr = -[Z11' + E'; Z12'], Y = sym(Yr E^-T).  Its Newton-Kleinman steps
+ * run on the dual closed loop (A - E Y Q, E) with the dual replay of the refinement's sign solver, while the scaled residual
+ * ||R_f(Y)||_F / (||G||_F + 2 ||A Y E'||_F + ||E Y Q Y E'||_F) exceeds 100 n eps and decreases.
+ * Arguments, limits and errors are those of dre_dense_gare_solve, checked before any kernel runs; a failure of the shared iteration fails the
+ * call, one that concerns a single solution (a rank-deficient extraction operand: DRE_ERR_SINGULAR; a refinement whose closed loop is not
+ * c-stable: DRE_ERR_NOT_STABLE) names it in the message ("regulator", "filter").  Device memory of about 25 n^2 doubles (the single call's
+ * 24 n^2 and Y; the dual extraction works in the iteration's own buffers), plus (maxiters + 12) n^2 when max_refine > 0, is checked up front.
+ * iinfo (4): [0] sign iterations [1] refinement steps of X, [2] sign iterations (the same count: there is one iteration) [3] refinement steps of Y;
+ * dinfo (4): [0] [1] scaled residual of X after extraction and final, [2] [3] the same for Y */
+int dre_dense_gare_solve_pair(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                              const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, dre_dense** Y, int64_t* iinfo /* 4 */,
+                              double* dinfo /* 4 */);
 /* residual(::GAREProblem, X) for a dense X (riccati/residual.jl:54-66): Res = Q + A'XE + E'XA - E'XGXE (symmetrised) as a new n x n matrix,
  * *norm = ||Res||_F.  G, Q as for dre_dense_gare_solve. */
 int dre_dense_gare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
@@ -544,6 +560,21 @@ int dre_svd_jacobi(dre_ctx* ctx, const dre_dense* A, double tol, dre_dense** U, 
 int dre_balance_lr(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* Lc, const dre_dense* Dc,
                    const dre_dense* Lo, const dre_dense* Do, int order, double tol, dre_dense** hsv, dre_dense** T, dre_dense** W, dre_dense** Ar,
                    dre_dense** Br, dre_dense** Cr, int64_t* ii /* 6 */, double* dd /* 3 */);
+/* LQG balanced truncation (dre_version >= 113) of  E x' = A x + B u,  y = C x,  which need not be c-stable: X and Y are the dense stabilizing
+ * solutions of the regulator and the filter Riccati equations (dre_dense_gare_solve_pair).  Both are factored by the eigensolver of dre_sym_eig
+ * (eigenvalues that are not positive are left out) and the steps of dre_balance_lr run with the factor of X in the place of the observability
+ * Gramian's and the factor of Y in the place of the controllability Gramian's:  *mu the LQG characteristic values (the singular values of
+ * Zo'E Zc, descending),  *T, *W (n x r, W'E T = I),  *Ar = W'A T, *Br = W'B, *Cr = C T, which satisfy both reduced Riccati equations with
+ * diag(mu_1 .. mu_r), and the reduced-order LQG controller  x_c' = Ac x_c + Lr y,  u = -Kr x_c:  *Kr = Br' Sigma_r (m x r),
+ * *Lr = Sigma_r Cr' (r x q),  *Ac = Ar - Br Kr - Lr Cr.
+ * order > 0: r = order (above the numerical rank: DRE_ERR_INVALID); order = 0: the smallest r with 2 sum_{i > r} nu_i <= tol,
+ * nu_i = mu_i / sqrt(1 + mu_i^2) (absolute: the normalised coprime factors have norm 1), at most the numerical rank.  n <= 8192, m, q >= 1.
+ * ii (6, may be NULL): as dre_balance_lr;  dd (3, may be NULL): [0] ||W'E T - I||_F [1] the bound 2 sum_{i > r} nu_i on the error of the
+ * normalised right coprime factors, max_w ||[N; M](iw) - [N_r; M_r](iw)||_2 [2] largest |eigenvalue| left out.
+ * Shape and argument errors are DRE_ERR_INVALID before any launch; the context stays usable after every error. */
+int dre_lqg_balance(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X, const dre_dense* Y,
+                    int order, double tol, dre_dense** mu, dre_dense** T, dre_dense** W, dre_dense** Ar, dre_dense** Br, dre_dense** Cr, dre_dense** Kr,
+                    dre_dense** Lr, dre_dense** Ac, int64_t* ii /* 6 */, double* dd /* 3 */);
 
 /* ---- batched block Jacobi and ensemble balanced truncation (dre_version >= 111) -----------------------------------------------------------
  * The eigensolver of dre_sym_eig_jacobi, the SVD of dre_svd_jacobi and dre_balance_lr for `batch` members of one shape in shared launches
