@@ -88,13 +88,7 @@ DenseAdaptiveResult dense_gdre_solve_adaptive(Ctx* ctx, const Mat& E, const Mat&
         gemm(ctx, false, false, 1.0, K, B, 0.0, XB, nullptr, "dense_ros");
         gemm(ctx, true, false, 1.0, E, XB, 0.0, V, nullptr, "dense_ros");
     };
-    auto sym_rhs = [&] { comb(ctx, Rs, 1.0, Racc, 0.0, nullptr, 0.0, nullptr, true); };      // Rs = sym(Racc)
-    // Y = E' M E
-    auto EtME = [&](const Mat& M, Mat& Y) {
-        gemm(ctx, false, false, 1.0, M, E, 0.0, T, nullptr, "dense_ros");
-        gemm(ctx, true, false, 1.0, E, T, 0.0, Y, nullptr, "dense_ros");
-    };
-    auto solve = [&](const Mat& Rsym, Mat& Xout) { out.solves.push_back(lyap.solve(Rsym, Xout)); };
+    const Ros2Ops ros2{E, A, B, CtC, Acl, gF, T, AXE, Racc, Rs, XB, V1};
     // the result grows by chunks: a failed growth names the step
     Mat Kchunk, Xchunk;
     int kfill = ADAPT_K_CHUNK, xfill = ADAPT_X_CHUNK;
@@ -147,23 +141,7 @@ DenseAdaptiveResult dense_gdre_solve_adaptive(Ctx* ctx, const Mat& E, const Mat&
             throw Error(ERR_STEP, "adaptive dense path: more than max_steps = " + std::to_string(sc.max_steps) + " trial steps (t = " + std::to_string(t) +
                                       ", " + std::to_string(res.accepted) + " accepted, " + std::to_string(res.rejected) + " rejected)");
         // one Ros2 step of dense_gdre_solve from (X, Kt) with step tau, up to its last combination
-        copy_mat(ctx, A, Acl);
-        gemm(ctx, false, true, -1.0, B, Kt, 1.0, Acl, nullptr, "dense_ros");                  // Acl = A - B K
-        comb(ctx, gF, gamma2 * tau, Acl, -0.5, &E);                                           // gF = gamma tau (A - BK) - E/2
-        lyap.factor(gF);
-        gemm(ctx, false, false, 1.0, X, E, 0.0, T, nullptr, "dense_ros");                     // R = C'C + A'XE + E'XA - K'K
-        gemm(ctx, true, false, 1.0, A, T, 0.0, AXE, nullptr, "dense_ros");
-        copy_mat(ctx, CtC, Racc);
-        gemm(ctx, false, true, -1.0, Kt, Kt, 1.0, Racc, nullptr, "dense_ros");
-        comb(ctx, Racc, 1.0, Racc, 2.0, &AXE);
-        sym_rhs();
-        solve(Rs, K1);
-        EtKB(K1, V1);
-        EtME(K1, Racc);
-        comb(ctx, Racc, -(2.0 - 1.0 / gamma2), Racc);
-        gemm(ctx, false, true, -tau * tau, V1, V1, 1.0, Racc, nullptr, "dense_ros");
-        sym_rhs();
-        solve(Rs, K2);
+        ros2_stages(ctx, lyap, ros2, X, Kt, tau, gamma2, K1, K2, out.solves);
         {
             TimedScope ts(ctx, "dense_step_error", 32.0 * n * n, 0.0);
             hipLaunchKernelGGL(k_step_error, dim3(NORM_PARTS), dim3(256), 0, ctx->stream, n, (const double*)X.p, (const double*)K1.p, (const double*)K2.p,

@@ -20,13 +20,10 @@
 #include <memory>
 
 #include "dense.hpp"
-#include "dense_device.hpp"
+#include "dense_are_body.hpp"
 #include "profiling.hpp"
 
 namespace dre {
-
-static constexpr double ARE_SCALE_OFF = 1e-2;    // tests/_hamiltonian_sign_model.py: SCALE_OFF, STAG_WINDOW
-static constexpr int ARE_STAG_WINDOW = 3;
 
 // Device-side control words of the sign iteration and of the residual (read back once per step by the host).
 struct AreCtl {
@@ -45,66 +42,21 @@ __global__ void k_are_ctl_init(AreCtl* c) {
     c->since = 0; c->scale = 1; c->done = 0; c->pad = 0;
 }
 
-// Z0 = [[A, -sym(G)], [-sym(Q), -A']] into Z and Zi (ld 2n; A, G, Q ld n)
+// The kernels' bodies are dense_are_body.hpp's, shared with the member-indexed kernels of dense_are_batch.hip.
 __global__ __launch_bounds__(256) void k_are_assemble(int n, const double* __restrict__ A, const double* __restrict__ G, const double* __restrict__ Q,
                                                       double* __restrict__ Z, double* __restrict__ Zi) {
-    const size_t L = 2 * (size_t)n, tot = (size_t)n * n;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n, t = j + i * n;
-        const double a = A[idx], at = A[t], g = -0.5 * (G[idx] + G[t]), q = -0.5 * (Q[idx] + Q[t]);
-        const size_t p11 = i + j * L, p12 = i + (n + j) * L, p21 = (n + i) + j * L, p22 = (n + i) + (n + j) * L;
-        Z[p11] = a; Zi[p11] = a;
-        Z[p12] = g; Zi[p12] = g;
-        Z[p21] = q; Zi[p21] = q;
-        Z[p22] = -at; Zi[p22] = -at;
-    }
+    are_assemble_body(KERNEL_GRID_STRIDE, n, A, G, Q, Z, Zi);
 }
 
-// Z_{k+1} = struct((Z_k / c + c Y) / 2) with Y = K Z_k^-1 K in Zi, written to Z and to Zi (the next inversion's operand), and the partial sums
-// of ||Z_{k+1} - Z_k||^2 and ||Z_{k+1}||^2 per workgroup.  c = (|det Z_k| / |det K|)^(1/2n) while ctl->scale, else 1.  Thread idx = (i, j) owns
-// the orbits {Z11(i,j), Z22(j,i)} and, for i <= j, {Z12(i,j), Z12(j,i)} and {Z21(i,j), Z21(j,i)}: it reads and writes only its own orbits, so
-// the structured average runs in place.
+// c = (|det Z_k| / |det K|)^(1/2n) while ctl->scale, else 1
 __global__ __launch_bounds__(256) void k_are_update(int n, double* __restrict__ Z, double* __restrict__ Zi, const GjCtl* ictl, const AreCtl* actl,
                                                     double logdetK, double* __restrict__ part) {
     if (ictl->singular) return;                     // (uniform: k_are_decide reports it)
     const double c = actl->scale ? exp((ictl->logdet - logdetK) / (2.0 * n)) : 1.0;
-    const double h0 = 0.5 / c, h1 = 0.5 * c;
-    const size_t L = 2 * (size_t)n, tot = (size_t)n * n;
-    double sd = 0.0, sz = 0.0;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n;
-        {   // Z11(i,j) and Z22(j,i):  Z11 := (Z11 - Z22')/2,  Z22 := -Z11'
-            const size_t pa = i + j * L, pb = (n + j) + (n + i) * L;
-            const double a = Z[pa], b = Z[pb];
-            const double s = 0.5 * ((h0 * a + h1 * Zi[pa]) - (h0 * b + h1 * Zi[pb]));
-            sd += (s - a) * (s - a) + (s + b) * (s + b);
-            sz += 2.0 * s * s;
-            Z[pa] = s; Zi[pa] = s;
-            Z[pb] = -s; Zi[pb] = -s;
-        }
-        if (i <= j) {   // Z12 and Z21 symmetrised
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                const size_t r0 = blk ? n : 0, c0 = blk ? 0 : n;
-                const size_t pa = (r0 + i) + (c0 + j) * L, pb = (r0 + j) + (c0 + i) * L;
-                const double a = Z[pa], b = Z[pb];
-                const double s = 0.5 * ((h0 * a + h1 * Zi[pa]) + (h0 * b + h1 * Zi[pb]));
-                if (i < j) {
-                    sd += (s - a) * (s - a) + (s - b) * (s - b);
-                    sz += 2.0 * s * s;
-                } else {
-                    sd += (s - a) * (s - a);
-                    sz += s * s;
-                }
-                Z[pa] = s; Zi[pa] = s;
-                Z[pb] = s; Zi[pb] = s;
-            }
-        }
-    }
-    store_partials(part, sd, sz);
+    are_update_body(KERNEL_GRID_STRIDE, n, Z, Zi, c, part);
 }
 
-// the stopping norm and the decision of the sign iteration (tests/_hamiltonian_sign_model.py: sign_iteration)
+// the stopping norm and the decision of the sign iteration
 __global__ __launch_bounds__(256) void k_are_decide(int nparts, const double* __restrict__ part, double tol, const GjCtl* ictl, AreCtl* c) {
     double s[2];                                    // ||Z_{k+1} - Z_k||^2, ||Z_{k+1}||^2
     load_partials(nparts, part, s);
@@ -112,89 +64,39 @@ __global__ __launch_bounds__(256) void k_are_decide(int nparts, const double* __
     if (ictl->singular) { c->done = 4; return; }
     const double d = sqrt(s[0] / s[1]);
     c->step = d;
-    if (!isfinite(d)) { c->done = 3; return; }
-    if (d <= tol) { c->done = 1; return; }
-    if (d < c->best) {
-        c->best = d; c->since = 0;
-    } else if (!c->scale && ++c->since >= ARE_STAG_WINDOW) {     // (the scaled phase is not monotone: its first steps often grow)
-        c->done = 2; return;
-    }
-    if (d < ARE_SCALE_OFF) c->scale = 0;
+    const int done = are_step_rule(d, tol, c->best, c->since, c->scale);
+    if (done) c->done = done;
 }
 
-// extraction operands: M = [Z12; Z22 + E'] into Zi(:, 0:n), rhs = -[Z11 + E; Z21] into Zi(:, n:2n)  (ld 2n; E ld n)
 __global__ __launch_bounds__(256) void k_are_extract_ops(int n, const double* __restrict__ Z, const double* __restrict__ E, double* __restrict__ Zi) {
-    const size_t L = 2 * (size_t)n, tot = (size_t)n * n;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n;
-        const double e = E[idx], et = E[j + i * n];
-        Zi[i + j * L] = Z[i + (n + j) * L];                                  // Z12
-        Zi[(n + i) + j * L] = Z[(n + i) + (n + j) * L] + et;                 // Z22 + E'
-        Zi[i + (n + j) * L] = -(Z[i + j * L] + e);                           // -(Z11 + E)
-        Zi[(n + i) + (n + j) * L] = -Z[(n + i) + j * L];                     // -Z21
-    }
+    are_extract_ops_body(KERNEL_GRID_STRIDE, n, Z, E, Zi);
 }
 
-// the filter's extraction operands from the transposed blocks: M_f = [Z21'; Z22' + E] into Zi(:, 0:n), rhs_f = -[Z11' + E'; Z12'] into Zi(:, n:2n)
-// (ld 2n; E ld n).  One workgroup per 32 x 32 tile of the n x n blocks: the source tile (rows j0.., columns i0..) is read along its columns
-// into LDS (33 doubles per row: no bank conflicts on the transposed read-out) and written along the destination's columns, so both sides of
-// each of the four transpositions are coalesced.  The untransposed E of the second block is read at the destination index.
+// one workgroup per 32 x 32 tile of the n x n blocks
 __global__ __launch_bounds__(256) void k_are_extract_ops_t(int n, const double* __restrict__ Z, const double* __restrict__ E, double* __restrict__ Zi) {
-    __shared__ double tile[32][33];
-    const size_t L = 2 * (size_t)n, N = (size_t)n;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                      // 32 x 8
-    const size_t i0 = (size_t)blockIdx.x * 32, j0 = (size_t)blockIdx.y * 32;     // destination rows i0.., columns j0..
-#pragma unroll 1
-    for (int blk = 0; blk < 4; ++blk) {
-        // blk 0: Z21' -> (0, 0);  1: Z22' + E -> (n, 0);  2: -(Z11 + E)' -> (0, n);  3: -Z12' -> (n, n)
-        const size_t sr = blk < 2 ? N : 0, sc = (blk == 1 || blk == 3) ? N : 0;
-        const size_t dr = (blk & 1) ? N : 0, dc = blk < 2 ? 0 : N;
-        const size_t js = j0 + tx;                                               // source row
-        for (int k = ty; k < 32; k += 8) {
-            const size_t is = i0 + k;                                            // source column
-            double v = 0.0;
-            if (js < N && is < N) {
-                v = Z[(sr + js) + (sc + is) * L];
-                if (blk == 2) v += E[js + is * N];
-            }
-            tile[k][tx] = v;
-        }
-        __syncthreads();
-        const size_t id = i0 + tx;                                               // destination row
-        for (int k = ty; k < 32; k += 8) {
-            const size_t jd = j0 + k;                                            // destination column
-            if (id < N && jd < N) {
-                double v = tile[tx][k];
-                if (blk == 1) v += E[id + jd * N];
-                Zi[(dr + id) + (dc + jd) * L] = blk < 2 ? v : -v;
-            }
-        }
-        __syncthreads();
-    }
+    are_extract_ops_t_body(n, Z, E, Zi);
 }
 
-// Res = sym(Q) + AXE + AXE' - sym(XGX) and the partial sums of ||Res||^2, ||Q||^2, ||AXE||^2, ||XGX||^2 (all n x n, ld n)
 __global__ __launch_bounds__(256) void k_are_residual(int n, const double* __restrict__ Q, const double* __restrict__ AXE, const double* __restrict__ XGX,
                                                       double* __restrict__ Res, double* __restrict__ part) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    const size_t tot = (size_t)n * n;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n, t = j + i * n;
-        const double v = 0.5 * (Q[idx] + Q[t]) + (AXE[idx] + AXE[t]) - 0.5 * (XGX[idx] + XGX[t]);     // (exactly symmetric)
-        Res[idx] = v;
-        s0 += v * v; s1 += Q[idx] * Q[idx]; s2 += AXE[idx] * AXE[idx]; s3 += XGX[idx] * XGX[idx];
-    }
-    store_partials(part, s0, s1, s2, s3);
+    are_residual_body(KERNEL_GRID_STRIDE, n, Q, AXE, XGX, Res, part);
 }
 
 __global__ __launch_bounds__(256) void k_are_residual_finish(int nparts, const double* __restrict__ part, AreCtl* c) {
     double s[4];
     load_partials(nparts, part, s);
-    if (threadIdx.x == 0) {
-        const double r = sqrt(s[0]), den = sqrt(s[1]) + 2.0 * sqrt(s[2]) + sqrt(s[3]);
-        c->resnorm = r;
-        c->res = den > 0.0 ? r / den : r;
-    }
+    if (threadIdx.x == 0) c->res = are_scaled_residual(s, &c->resnorm);
+}
+
+// the "what" of a sign iteration that ended with done > 1 at iteration k (done 4: the singular Z_k), behind the caller's "dense GARE: "
+std::string gare_sign_failure(int done, int k, double step, int maxiters) {
+    if (done == 4) return "singular Z_" + std::to_string(k) + " in the sign iteration";
+    if (done == 2)
+        return "the sign iteration stagnated at a relative step " + std::to_string(step) +
+               " (Hamiltonian eigenvalues on or near the imaginary axis: not stabilizable or not detectable?)";
+    if (done == 3) return "the sign iteration produced non-finite values";
+    return "the sign iteration did not converge in " + std::to_string(maxiters) + " iterations (relative step " + std::to_string(step) +
+           "; Hamiltonian eigenvalues on or near the imaginary axis?)";
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
@@ -371,15 +273,9 @@ DenseGareResult gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, c
         h = read_back(ctx, actl.p);
         out.iters = k + 1;
         if (h.done == 1) converged = true;
-        else if (h.done == 2)
-            throw Error(ERR_NOT_STABLE, "dense GARE: the sign iteration stagnated at a relative step " + std::to_string(h.step) +
-                                            " (Hamiltonian eigenvalues on or near the imaginary axis: not stabilizable or not detectable?)");
-        else if (h.done == 3) throw Error(ERR_NOT_STABLE, "dense GARE: the sign iteration produced non-finite values");
-        else if (h.done == 4) throw Error(ERR_SINGULAR, "dense GARE: singular Z_" + std::to_string(k) + " in the sign iteration");
+        else if (h.done) throw Error(h.done == 4 ? ERR_SINGULAR : ERR_NOT_STABLE, "dense GARE: " + gare_sign_failure(h.done, k, h.step, maxiters));
     }
-    if (!converged)
-        throw Error(ERR_NOT_STABLE, "dense GARE: the sign iteration did not converge in " + std::to_string(maxiters) + " iterations (relative step " +
-                                        std::to_string(h.step) + "; Hamiltonian eigenvalues on or near the imaginary axis?)");
+    if (!converged) throw Error(ERR_NOT_STABLE, "dense GARE: " + gare_sign_failure(5, maxiters, h.step, maxiters));
 
     // ---- pair: the filter's extraction first, [Z21'; Z22' + E] Yr = -[Z11' + E'; Z12'], Y = sym(Yr E^-T); it works in Zi and leaves Z as it is ----
     if (dual) {

@@ -18,6 +18,11 @@ struct DenseGareResult {
 DenseGareResult dense_gare_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat* Rinv, const Mat& Ct, const Mat* S, int maxiters,
                                  double tol, int max_refine);
 
+// What went wrong in a Hamiltonian sign iteration that ended with done = 2 (stagnated), 3 (non-finite), 4 (singular Z_k) or 5 (out of maxiters),
+// shared by the single and the batched solver, which put "dense GARE: " or "batched dense GARE, member b: " in front.  k: the iteration of the
+// singular Z_k; step: the last relative step.
+std::string gare_sign_failure(int done, int k, double step, int maxiters);
+
 // Both Riccati solutions of LQG design from ONE Hamiltonian sign iteration: X as dense_gare_solve returns it, bit for bit, and the
 // filter solution Y of  G + A Y E' + E Y A' - E Y Q Y E' = 0,  extracted from the transposed blocks of the same Z_inf (the filter's pencil is
 // (H', K')) and refined on the dual closed loop A - E Y Q with SignLyap::solve_t.  Y.iters is the shared iteration count; refinements, res0 and res

@@ -7,8 +7,8 @@
 //   (Z_inf + K)[I; XE] = 0                                       Householder QR member by member (qr_factor has no batched form), everything
 //                                                                behind it on stacks;
 //   Newton-Kleinman refinement                                   BatchedSignLyap on the gathered sub-batch of the members that need a step.
-// The element-wise kernels are restated here with a member axis instead of being shared with dense_are.hip, so that the single path's code
-// generation stays what it was.  A member's arithmetic never looks at B, at its position or at another member's data: no atomics, per-member
+// The element-wise kernels are thin wrappers: the bodies live in dense_are_body.hpp, shared with dense_are.hip, and a wrapper here only
+// applies the member's mask and offsets the base pointers.  A member's arithmetic never looks at B, at its position or at another member's data: no atomics, per-member
 // grids and partial-sum buffers, fixed-order sums.  Offsets into the stacks are formed in size_t.
 #include "dense_are_batch.hpp"
 
@@ -17,13 +17,10 @@
 #include <memory>
 
 #include "dense.hpp"
-#include "dense_device.hpp"
+#include "dense_are_body.hpp"
 #include "profiling.hpp"
 
 namespace dre {
-
-static constexpr double BARE_SCALE_OFF = 1e-2;   // as dense_are.hip (tests/_hamiltonian_sign_model.py: SCALE_OFF, STAG_WINDOW)
-static constexpr int BARE_STAG_WINDOW = 3;
 
 // ---- control blocks ------------------------------------------------------------------------------------------------------------------
 __global__ void k_bare_ctl_init(BatchCtl* ctl, AreBatchCtl* ext) {
@@ -45,74 +42,29 @@ __global__ void k_bare_ctl_after_inverse(BatchCtl* ctl, int phase) {
     else if (phase == 0) ctl[b].logdetE = ctl[b].s.gj.logdet;
 }
 
-// ---- sign iteration --------------------------------------------------------------------------------------------------------------------
-// k_are_assemble per member: Z0 = [[A, -sym(G)], [-sym(Q), -A']] into Z and Zi (members 2n x 2n; A, G, Q members n x n)
+// ---- the kernels of dense_are.hip per member: bodies of dense_are_body.hpp on the member's slices ------------------------------------------
 __global__ __launch_bounds__(256) void k_bare_assemble(int n, const double* __restrict__ A, const double* __restrict__ G, const double* __restrict__ Q,
                                                        double* __restrict__ Z, double* __restrict__ Zi, BatchMask mask) {
     const int b = blockIdx.y;
     if (batch_off(mask, b)) return;
-    const size_t L = 2 * (size_t)n, tot = (size_t)n * n, o = (size_t)b * tot, oz = (size_t)b * 4 * tot;
-    A += o; G += o; Q += o; Z += oz; Zi += oz;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n, t = j + i * n;
-        const double a = A[idx], at = A[t], g = -0.5 * (G[idx] + G[t]), q = -0.5 * (Q[idx] + Q[t]);
-        const size_t p11 = i + j * L, p12 = i + (n + j) * L, p21 = (n + i) + j * L, p22 = (n + i) + (n + j) * L;
-        Z[p11] = a; Zi[p11] = a;
-        Z[p12] = g; Zi[p12] = g;
-        Z[p21] = q; Zi[p21] = q;
-        Z[p22] = -at; Zi[p22] = -at;
-    }
+    const size_t tot = (size_t)n * n, o = (size_t)b * tot, oz = (size_t)b * 4 * tot;
+    are_assemble_body(KERNEL_GRID_STRIDE, n, A + o, G + o, Q + o, Z + oz, Zi + oz);
 }
 
-// k_are_update per member: Z_{k+1} = struct((Z_k / c + c Y) / 2) with Y = K Z_k^-1 K in Zi, written to Z and Zi, and the member's partial
-// sums of ||Z_{k+1} - Z_k||^2 and ||Z_{k+1}||^2.  c = (|det Z_k| / |det K|)^(1/2n) from the member's own log|det Z_k| and log|det E| while
-// its scaling is on.  The thread of (i, j) owns its orbits as in dense_are.hip, so the structured average runs in place.  The mask
-// (BM_FACTOR) leaves out a member whose inversion met a zero pivot: k_bare_decide reports it.
+// c = (|det Z_k| / |det K|)^(1/2n) from the member's own log|det Z_k| and log|det E| while its scaling is on.  The mask (BM_FACTOR) leaves
+// out a member whose inversion met a zero pivot: k_bare_decide reports it.
 __global__ __launch_bounds__(256) void k_bare_update(int n, double* __restrict__ Z, double* __restrict__ Zi, double* __restrict__ part, BatchMask mask) {
     const int b = blockIdx.y;
     if (batch_off(mask, b)) return;
     const BatchCtl& cb = mask.ctl[b];
     const double logdetK = 2.0 * cb.logdetE;
     const double c = cb.scale ? exp((cb.s.gj.logdet - logdetK) / (2.0 * n)) : 1.0;
-    const double h0 = 0.5 / c, h1 = 0.5 * c;
-    const size_t L = 2 * (size_t)n, tot = (size_t)n * n, oz = (size_t)b * 4 * tot;
-    Z += oz; Zi += oz;
-    double sd = 0.0, sz = 0.0;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n;
-        {   // Z11(i,j) and Z22(j,i):  Z11 := (Z11 - Z22')/2,  Z22 := -Z11'
-            const size_t pa = i + j * L, pb = (n + j) + (n + i) * L;
-            const double a = Z[pa], bb = Z[pb];
-            const double s = 0.5 * ((h0 * a + h1 * Zi[pa]) - (h0 * bb + h1 * Zi[pb]));
-            sd += (s - a) * (s - a) + (s + bb) * (s + bb);
-            sz += 2.0 * s * s;
-            Z[pa] = s; Zi[pa] = s;
-            Z[pb] = -s; Zi[pb] = -s;
-        }
-        if (i <= j) {   // Z12 and Z21 symmetrised
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                const size_t r0 = blk ? n : 0, c0 = blk ? 0 : n;
-                const size_t pa = (r0 + i) + (c0 + j) * L, pb = (r0 + j) + (c0 + i) * L;
-                const double a = Z[pa], bb = Z[pb];
-                const double s = 0.5 * ((h0 * a + h1 * Zi[pa]) + (h0 * bb + h1 * Zi[pb]));
-                if (i < j) {
-                    sd += (s - a) * (s - a) + (s - bb) * (s - bb);
-                    sz += 2.0 * s * s;
-                } else {
-                    sd += (s - a) * (s - a);
-                    sz += s * s;
-                }
-                Z[pa] = s; Zi[pa] = s;
-                Z[pb] = s; Zi[pb] = s;
-            }
-        }
-    }
-    store_partials(part + (size_t)b * 2 * NORM_PARTS, sd, sz);
+    const size_t tot = (size_t)n * n, oz = (size_t)b * 4 * tot;
+    are_update_body(KERNEL_GRID_STRIDE, n, Z + oz, Zi + oz, c, part + (size_t)b * 2 * NORM_PARTS);
 }
 
-// k_are_decide per member (one workgroup each), and what the single path's host loop does with the decision: a failure sets the member's
-// code, so that it drops out of every later launch; running out of maxiters is done = 5
+// one workgroup per member: the decision, and what the single path's host loop does with it: a failure sets the member's code, so that it
+// drops out of every later launch; running out of maxiters is done = 5
 __global__ __launch_bounds__(256) void k_bare_decide(const double* __restrict__ part, double tol, int k, int maxiters, BatchCtl* ctl, AreBatchCtl* ext) {
     const int b = blockIdx.y;
     BatchCtl* c = ctl + b;
@@ -127,54 +79,29 @@ __global__ __launch_bounds__(256) void k_bare_decide(const double* __restrict__ 
     AreBatchCtl* e = ext + b;
     const double d = sqrt(s[0] / s[1]);
     c->s.step = d; c->iters = k + 1;
-    if (!isfinite(d)) { c->s.done = 3; c->fail = ERR_NOT_STABLE; return; }
-    if (d <= tol) { c->s.done = 1; return; }
-    if (d < e->best) {
-        e->best = d; e->since = 0;
-    } else if (!c->scale && ++e->since >= BARE_STAG_WINDOW) {    // (the scaled phase is not monotone: its first steps often grow)
-        c->s.done = 2; c->fail = ERR_NOT_STABLE; return;
-    }
-    if (d < BARE_SCALE_OFF) c->scale = 0;
-    if (k + 1 >= maxiters) { c->s.done = 5; c->fail = ERR_NOT_STABLE; }
+    int done = are_step_rule(d, tol, e->best, e->since, c->scale);
+    if (done == 0 && k + 1 >= maxiters) done = 5;
+    if (done) c->s.done = done;
+    if (done > 1) c->fail = ERR_NOT_STABLE;
 }
 
-// ---- extraction ------------------------------------------------------------------------------------------------------------------------
-// k_are_extract_ops per member: M = [Z12; Z22 + E'] into Zi(:, 0:n), rhs = -[Z11 + E; Z21] into Zi(:, n:2n)
 __global__ __launch_bounds__(256) void k_bare_extract_ops(int n, const double* __restrict__ Z, const double* __restrict__ E, double* __restrict__ Zi,
                                                           BatchMask mask) {
     const int b = blockIdx.y;
     if (batch_off(mask, b)) return;
-    const size_t L = 2 * (size_t)n, tot = (size_t)n * n, oz = (size_t)b * 4 * tot;
-    Z += oz; Zi += oz; E += (size_t)b * tot;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n;
-        const double e = E[idx], et = E[j + i * n];
-        Zi[i + j * L] = Z[i + (n + j) * L];                                  // Z12
-        Zi[(n + i) + j * L] = Z[(n + i) + (n + j) * L] + et;                 // Z22 + E'
-        Zi[i + (n + j) * L] = -(Z[i + j * L] + e);                           // -(Z11 + E)
-        Zi[(n + i) + (n + j) * L] = -Z[(n + i) + j * L];                     // -Z21
-    }
+    const size_t tot = (size_t)n * n, oz = (size_t)b * 4 * tot;
+    are_extract_ops_body(KERNEL_GRID_STRIDE, n, Z + oz, E + (size_t)b * tot, Zi + oz);
 }
 
-// ---- residual and refinement -------------------------------------------------------------------------------------------------------------
-// k_are_residual per member: Res = sym(Q) + AXE + AXE' - sym(XGX) and the member's partial sums of ||Res||^2, ||Q||^2, ||AXE||^2, ||XGX||^2
 __global__ __launch_bounds__(256) void k_bare_residual(int n, const double* __restrict__ Q, const double* __restrict__ AXE, const double* __restrict__ XGX,
                                                        double* __restrict__ Res, double* __restrict__ part, BatchMask mask) {
     const int b = blockIdx.y;
     if (batch_off(mask, b)) return;
     const size_t tot = (size_t)n * n, o = (size_t)b * tot;
-    Q += o; AXE += o; XGX += o; Res += o;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = idx % n, j = idx / n, t = j + i * n;
-        const double v = 0.5 * (Q[idx] + Q[t]) + (AXE[idx] + AXE[t]) - 0.5 * (XGX[idx] + XGX[t]);     // (exactly symmetric)
-        Res[idx] = v;
-        s0 += v * v; s1 += Q[idx] * Q[idx]; s2 += AXE[idx] * AXE[idx]; s3 += XGX[idx] * XGX[idx];
-    }
-    store_partials(part + (size_t)b * 4 * NORM_PARTS, s0, s1, s2, s3);
+    are_residual_body(KERNEL_GRID_STRIDE, n, Q + o, AXE + o, XGX + o, Res + o, part + (size_t)b * 4 * NORM_PARTS);
 }
 
-// k_are_residual_finish per member, and the refinement loop's decision of dense_gare_solve.  phase 0: the residual of the extracted X;
+// the scaled residual per member, and the refinement loop's decision of dense_gare_solve.  phase 0: the residual of the extracted X;
 // phase 1: the residual of the candidate X + D, which replaces X only when it is smaller.  A live member that the mask leaves out took no
 // step: its accept word is cleared.
 __global__ __launch_bounds__(256) void k_bare_residual_finish(const double* __restrict__ part, double target, int max_refine, int phase, BatchCtl* ctl,
@@ -189,9 +116,8 @@ __global__ __launch_bounds__(256) void k_bare_residual_finish(const double* __re
     if (threadIdx.x != 0) return;
     BatchCtl* c = ctl + b;
     AreBatchCtl* e = ext + b;
-    const double r = sqrt(s[0]), den = sqrt(s[1]) + 2.0 * sqrt(s[2]) + sqrt(s[3]);
-    const double res = den > 0.0 ? r / den : r;
-    e->resnorm = r; e->cand = res;
+    const double res = are_scaled_residual(s, &e->resnorm);
+    e->cand = res;
     if (phase == 0) {
         c->res0 = res; c->s.res = res; c->nref = 0; e->accept = 0;
         c->refine = (res > target && max_refine > 0) ? 1 : 0;
@@ -326,16 +252,10 @@ void dense_gare_solve_batched(Ctx* ctx, int batch, const Mat& E, const Mat& A, c
             st.code = h.fail;
             if (h.fail == ERR_SINGULAR)
                 st.msg = who(b) + (h.s.done == 0   ? std::string("E is singular (zero pivot in the Gauss-Jordan inversion)")
-                                   : h.s.done == 4 ? "singular Z_" + std::to_string(h.iters) + " in the sign iteration"
+                                   : h.s.done == 4 ? gare_sign_failure(4, h.iters, h.s.step, maxiters)
                                                    : std::string("[Z12; Z22 + E'] is rank deficient (no stable deflating subspace of dimension n)"));
-            else if (h.s.done == 2)
-                st.msg = who(b) + "the sign iteration stagnated at a relative step " + std::to_string(h.s.step) +
-                         " (Hamiltonian eigenvalues on or near the imaginary axis: not stabilizable or not detectable?)";
-            else if (h.s.done == 3)
-                st.msg = who(b) + "the sign iteration produced non-finite values";
             else
-                st.msg = who(b) + "the sign iteration did not converge in " + std::to_string(maxiters) + " iterations (relative step " +
-                         std::to_string(h.s.step) + "; Hamiltonian eigenvalues on or near the imaginary axis?)";
+                st.msg = who(b) + gare_sign_failure(h.s.done, h.iters, h.s.step, maxiters);
         }
     };
     auto any_alive = [&] {

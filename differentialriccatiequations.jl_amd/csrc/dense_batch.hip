@@ -1,6 +1,7 @@
 // Batched dense path: B independent problems of one order n in shared launches, member b on a grid axis.
-//   gj_invert_batched        the register-panel Gauss-Jordan inversion of dense_gj.hip on a stack (the panel body is dense_gj_body.hpp's);
-//   BatchedSignLyap          SignLyap on a stack of pencils, the iteration's decisions taken per member on the device;
+//   gj_invert_batched        the register-panel Gauss-Jordan inversion of dense_gj.hip on a stack (the bodies are dense_gj_body.hpp's, shared with dense_gj.hip);
+//   BatchedSignLyap          SignLyap on a stack of pencils, the iteration's decisions taken per member on the device (the element-wise bodies
+//                            and the stopping rule are dense_sign_body.hpp's, shared with dense_sign.hip);
 //   dense_gdre_solve_batched Ros1 / Ros2 of dense_sign.hip on stacks.
 // The strided MFMA GEMM is gemm_strided of gemm.hip.  A member's arithmetic never looks at B, at its position or at another member's data.
 #include "dense_batch.hpp"
@@ -8,15 +9,11 @@
 #include <cmath>
 
 #include "dense.hpp"
-#include "dense_device.hpp"
 #include "dense_gj_body.hpp"
+#include "dense_sign_body.hpp"
 #include "profiling.hpp"
 
 namespace dre {
-
-static constexpr double SCALE_OFF = 1e-2;        // as dense_sign.hip (tests/_sign_model.py)
-static constexpr double STAG_STEP = 1e-8;
-static constexpr double STAG_DIST = 1e-4;
 
 // ---- inversion ---------------------------------------------------------------------------------------------------------------------
 template <int NB, int R>
@@ -96,7 +93,7 @@ void gj_invert_batched(Ctx* ctx, int batch, int n, double* A, int* piv, BatchCtl
     DRE_HIP(hipGetLastError());
 }
 
-// ---- element-wise kernels, member = blockIdx.y ----------------------------------------------------------------------------------------
+// ---- element-wise kernels, member = blockIdx.y; the bodies shared with dense_sign.hip are dense_sign_body.hpp's -------------------------
 // k_sign_update per member; the scaling factor c_k comes from the member's own log|det Z_k| and log|det E| on the device, and the replay's
 // coefficients c/2 and 1/(2c) of iteration k are left in coef for the strided GEMM
 __global__ __launch_bounds__(256) void k_bsign_update(int n, double* __restrict__ Z, double* __restrict__ Zi, const double* __restrict__ Y,
@@ -107,14 +104,7 @@ __global__ __launch_bounds__(256) void k_bsign_update(int n, double* __restrict_
     const BatchCtl& cb = mask.ctl[b];
     const double c = cb.scale ? exp((cb.s.gj.logdet - cb.logdetE) / n) : 1.0;
     const size_t tot = (size_t)n * n, o = (size_t)b * tot;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const double z = Z[o + idx], zn = z / (2.0 * c) + (0.5 * c) * Y[o + idx];
-        const double a = zn + E[o + idx], d = zn - z;
-        s0 += a * a; s1 += d * d; s2 += zn * zn;
-        Z[o + idx] = zn; Zi[o + idx] = zn;
-    }
-    store_partials(part + (size_t)b * 3 * NORM_PARTS, s0, s1, s2);
+    sign_update_body(KERNEL_GRID_STRIDE, n, Z + o, Zi + o, Y + o, E + o, c, part + (size_t)b * 3 * NORM_PARTS);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         double* cf = coef + ((size_t)b * maxiters + mask.k) * 2;
         cf[0] = 0.5 * c; cf[1] = 1.0 / (2.0 * c);
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(256) void k_bsign_decide(const double* __restrict__
     load_partials(NORM_PARTS, part + (size_t)b * 3 * NORM_PARTS, s);
     if (threadIdx.x == 0) {
         const double e = sqrt(s[0] / nrm[2 * b]), d = sqrt(s[1] / s[2]);
-        int done = !isfinite(e) || !isfinite(d) ? 3 : (e <= tol ? 1 : ((d <= STAG_STEP && e > STAG_DIST) ? 2 : 0));
+        int done = sign_decision(e, d, tol);
         if (done == 0 && k + 1 >= maxiters) done = 5;
         c->s.dist = e; c->s.step = d; c->s.done = done; c->iters = k + 1;
         if (done > 1) c->fail = ERR_NOT_STABLE;
@@ -179,14 +169,7 @@ __global__ __launch_bounds__(256) void k_bres_sym(int n, const double* __restric
     const int b = blockIdx.y;
     if (batch_off(mask, b)) return;
     const size_t tot = (size_t)n * n, o = (size_t)b * tot;
-    double s = 0.0;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const int i = idx % n, j = idx / n;
-        const double v = Rm[o + idx] + G[o + idx] + G[o + j + (size_t)i * n];
-        Res[o + idx] = v;
-        s += v * v;
-    }
-    store_partials(part + (size_t)b * 3 * NORM_PARTS, s);
+    res_sym_body(KERNEL_GRID_STRIDE, n, Rm + o, G + o, Res + o, part + (size_t)b * 3 * NORM_PARTS);
 }
 // k_res_finish per member, and the refinement decision of SignLyap::solve: phase 0 is the residual of the first replay, phase 1 the one
 // after a refinement step
@@ -198,8 +181,7 @@ __global__ __launch_bounds__(256) void k_bres_finish(const double* __restrict__ 
     load_partials(NORM_PARTS, part + (size_t)b * 3 * NORM_PARTS, s);
     if (threadIdx.x == 0) {
         BatchCtl* c = ctl + b;
-        const double nR2 = nrm[2 * b + 1];
-        const double res = nR2 > 0.0 ? sqrt(s[0] / nR2) : sqrt(s[0]);
+        const double res = relative_residual(s[0], nrm[2 * b + 1]);
         c->s.res = res;
         if (phase == 0) { c->res0 = res; c->nref = 0; } else c->nref += 1;
         c->refine = (res > target && c->nref < max_refine) ? 1 : 0;
@@ -317,16 +299,8 @@ void BatchedSignLyap::fetch() {
         if (!h.fail || st.code) continue;
         st.code = h.fail;
         const std::string who = "batched dense path, member " + std::to_string(b) + ": ";
-        if (h.fail == ERR_SINGULAR)
-            st.msg = who + (h.s.done == 4 ? "singular Z_" + std::to_string(h.iters) + " in the sign iteration (F singular?)"
-                                          : std::string("E is singular (zero pivot in the Gauss-Jordan inversion)"));
-        else if (h.s.done == 2)
-            st.msg = who + "the pencil is not c-stable (sign iteration stagnated at ||Z + E|| / ||E|| = " + std::to_string(h.s.dist) + ")";
-        else if (h.s.done == 3)
-            st.msg = who + "the sign iteration produced non-finite values (pencil not c-stable?)";
-        else
-            st.msg = who + "the sign iteration did not reach -E in " + std::to_string(maxiters_) + " iterations (||Z + E|| / ||E|| = " +
-                     std::to_string(h.s.dist) + "); the pencil is not c-stable";
+        if (h.fail == ERR_SINGULAR && h.s.done != 4) st.msg = who + "E is singular (zero pivot in the Gauss-Jordan inversion)";
+        else st.msg = who + sign_failure(h.s.done, h.iters, h.s.dist, maxiters_);
     }
 }
 

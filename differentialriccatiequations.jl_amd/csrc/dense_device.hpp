@@ -53,6 +53,13 @@ __device__ inline double block_sum(double v, double* red /* >= 17 doubles */) {
     return red[16];
 }
 
+// First index and step of a grid-stride loop over the elements of an operand, for a loop that lives in a __device__ body shared by several
+// kernels.  KERNEL_GRID_STRIDE has to expand in the __global__ function itself: there the compiler knows that every workgroup of the launch
+// is full and reads blockDim.x as one scalar load, while in a __device__ function it keeps the test for a partial last workgroup (a
+// dependent 16-bit load in front of the loop).
+struct GridStride { size_t first, step; };
+#define KERNEL_GRID_STRIDE (GridStride{(size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x})
+
 // Norms in two launches (the fused element-wise + partial-norm kernels of dense_sign.hip and dense_are.hip): every workgroup of the first kernel
 // leaves its share of the Q sums in part[q * gridDim.x + blockIdx.x]; the one workgroup of the second kernel adds the nparts shares of each sum
 // in a fixed order.  On return of load_partials every thread holds the totals.

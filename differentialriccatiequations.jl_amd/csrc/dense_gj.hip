@@ -5,114 +5,21 @@
 #include "dense_gj.hpp"
 
 #include "dense.hpp"
+#include "dense_gj_body.hpp"
 #include "profiling.hpp"
 
 namespace dre {
 
-static constexpr int GJ_THREADS = 512;
 // the tournament panel's width: 64 columns do not fit the selection round's registers at one row per thread (604 bytes of scratch), so the
 // trailing update runs at K = 32 as the register panel's does for n <= 1536
 static constexpr int GJ_TSLU_NB = 32;
 
 // ---- Gauss-Jordan inversion ------------------------------------------------------------------------------------------------------
-// Panel kernel: columns k .. k+kb-1 of A, all n rows, in registers (thread t owns rows t, t + 512, ...).  Step jj: pivot search over rows
-// >= j = k + jj, interchange of rows j and p (through LDS), scaling of the pivot row, elimination of column j from every other row.  On exit
-// the panel columns hold the columns of the accumulated transform M, and Pn (n x kb) = M - I on the panel's rows: the trailing update of
-// every other column c is A(:, c) += Pn W(:, c) with W = A(k:k+kb, :) after the interchanges.
+// Panel kernel: one workgroup, the whole panel in registers (gj_panel_body of dense_gj_body.hpp)
 template <int NB, int R>
 __global__ __launch_bounds__(GJ_THREADS) void k_gj_panel(int n, int k, int kb, double* __restrict__ A, int lda, double* __restrict__ Pn,
                                                          int* __restrict__ piv, GjCtl* ctl) {
-    if (ctl->singular) return;
-    __shared__ double prow[2][NB], jrow[2][NB];
-    __shared__ double redv[GJ_THREADS / 64];
-    __shared__ int redi[GJ_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double a[R][NB];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = tid + r * GJ_THREADS;
-#pragma unroll
-        for (int c = 0; c < NB; ++c) a[r][c] = (i < n && c < kb) ? A[i + (size_t)(k + c) * lda] : 0.0;
-    }
-    double ldacc = 0.0;
-    // fully unrolled, so that a[r][jj] has a compile-time column index and the panel stays in registers: the tail panel (kb < NB) is
-    // handled by predicating the body on the uniform jj < kb, not by leaving the loop (a loop exit keeps it rolled and moves a[][] to scratch)
-#pragma clang loop unroll(full)
-    for (int jj = 0; jj < NB; ++jj) {
-        if (jj < kb) {
-        const int j = k + jj, buf = jj & 1;
-        double best = -1.0;
-        int bi = n;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int i = tid + r * GJ_THREADS;
-            const double v = fabs(a[r][jj]);
-            if (i >= j && i < n && v > best) { best = v; bi = i; }      // (rows ascend with r: ties keep the smaller index; NaN never wins)
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(best, off);
-            const int oi = __shfl_xor(bi, off);
-            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
-        if (lane == 0) { redv[wave] = best; redi[wave] = bi; }
-        __syncthreads();
-        best = redv[0]; bi = redi[0];
-#pragma unroll
-        for (int w = 1; w < GJ_THREADS / 64; ++w)
-            if (redv[w] > best || (redv[w] == best && redi[w] < bi)) { best = redv[w]; bi = redi[w]; }
-        const int p = bi;
-        if (!(best > 0.0) || p >= n || !isfinite(best)) {        // an exactly zero (or non-finite) pivot column
-            if (tid == 0) ctl->singular = 1;
-            return;
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int i = tid + r * GJ_THREADS;
-            if (i == p) {
-#pragma unroll
-                for (int c = 0; c < NB; ++c) prow[buf][c] = a[r][c];
-            }
-            if (i == j) {
-#pragma unroll
-                for (int c = 0; c < NB; ++c) jrow[buf][c] = a[r][c];
-            }
-        }
-        __syncthreads();
-        const double dinv = 1.0 / prow[buf][jj];
-        if (tid == 0) { ldacc += log(fabs(prow[buf][jj])); piv[j] = p; }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int i = tid + r * GJ_THREADS;
-            if (i >= n) continue;
-            if (i == p && p != j) {
-#pragma unroll
-                for (int c = 0; c < NB; ++c) a[r][c] = jrow[buf][c];
-            }
-            if (i == j) {
-#pragma unroll
-                for (int c = 0; c < NB; ++c) a[r][c] = (c == jj) ? dinv : prow[buf][c] * dinv;
-            } else {
-                const double f = a[r][jj];
-#pragma unroll
-                for (int c = 0; c < NB; ++c) a[r][c] = (c == jj) ? -f * dinv : a[r][c] - f * (prow[buf][c] * dinv);
-            }
-        }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = tid + r * GJ_THREADS;
-        if (i >= n) continue;
-#pragma unroll
-        for (int c = 0; c < NB; ++c) {
-            if (c < kb) {
-                A[i + (size_t)(k + c) * lda] = a[r][c];
-                Pn[i + (size_t)c * n] = a[r][c] - (i == k + c ? 1.0 : 0.0);
-            }
-        }
-    }
-    if (tid == 0) ctl->logdet += ldacc;
+    gj_panel_body<NB, R>(n, k, kb, A, lda, Pn, piv, ctl);
 }
 
 // Tournament panel, one selection round (TSLU / CALU pivoting, Grigori, Demmel & Xiang 2011): the steps of k_gj_panel on a set of candidate
@@ -274,19 +181,10 @@ __global__ __launch_bounds__(GJ_THREADS) void k_gj_tslu(int k, int kb, const dou
     }
 }
 
-// the panel's row interchanges applied to every column outside it (with_panel: to the panel's columns too), and W(:, c) = A(k:k+kb, c) (ld nb)
-// for the trailing update
+// the panel's row interchanges applied to every column outside it (with_panel: to the panel's columns too), and W for the trailing update
 __global__ __launch_bounds__(256) void k_gj_swap(int n, int k, int kb, int nb, double* __restrict__ A, int lda, const int* __restrict__ piv,
                                                  double* __restrict__ W, const GjCtl* ctl, int with_panel) {
-    if (ctl->singular) return;
-    const int col = blockIdx.x * blockDim.x + threadIdx.x;
-    if (col >= n || (!with_panel && col >= k && col < k + kb)) return;
-    double* Ac = A + (size_t)col * lda;
-    for (int jj = 0; jj < kb; ++jj) {
-        const int j = k + jj, p = piv[j];
-        if (p != j && p > j && p < n) { const double t = Ac[j]; Ac[j] = Ac[p]; Ac[p] = t; }
-    }
-    for (int c = 0; c < kb; ++c) W[c + (size_t)col * nb] = Ac[k + c];
+    gj_swap_body(n, k, kb, nb, A, lda, piv, W, ctl, with_panel);
 }
 
 // Tournament panel, after the interchanges: A(k:k+kb, J) <- P^-1 and A(i, J) <- -A(i, J) P^-1 for every other row i (the columns J of the
@@ -326,19 +224,9 @@ __global__ __launch_bounds__(256) void k_gj_apply(int n, int k, int kb, double* 
     }
 }
 
-// inv(A) = M P_{n-1} ... P_0: the column interchanges in reverse order, one row per thread
+// inv(A) = M P_{n-1} ... P_0: the column interchanges in reverse order
 __global__ __launch_bounds__(256) void k_gj_unpivot(int n, double* __restrict__ A, int lda, const int* __restrict__ piv, const GjCtl* ctl) {
-    if (ctl->singular) return;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int j = n - 1; j >= 0; --j) {
-        const int p = piv[j];
-        if (p != j && p > j && p < n) {
-            const double t = A[i + (size_t)j * lda];
-            A[i + (size_t)j * lda] = A[i + (size_t)p * lda];
-            A[i + (size_t)p * lda] = t;
-        }
-    }
+    gj_unpivot_body(n, A, lda, piv, ctl);
 }
 
 __global__ void k_ctl_reset(GjCtl* ctl) { ctl->logdet = 0.0; ctl->singular = 0; }

@@ -1,8 +1,6 @@
-// Device bodies of the register-panel Gauss-Jordan inversion for the batched kernels of dense_batch.hip, which call them with one member's
-// slices.  They are the bodies of k_gj_panel, k_gj_swap and k_gj_unpivot of dense_gj.hip, text unchanged: same pivot rule and ties, same
-// elimination order, same log|det| accumulation.  A DUPLICATE on purpose: calling these from the single-problem kernels was tried and
-// changed the operand order of scalar address multiplies in all eight k_gj_panel instantiations (registers, LDS and scratch unchanged), so
-// dense_gj.hip keeps its own text and its code objects stay identical to the parent's.  A change to one copy belongs in the other.
+// Device bodies of the register-panel Gauss-Jordan inversion: the one text of the pivot rule and its ties, the elimination order and the
+// log|det| accumulation.  k_gj_panel, k_gj_swap and k_gj_unpivot of dense_gj.hip call them with the whole matrix, k_bgj_panel, k_bgj_swap
+// and k_bgj_unpivot of dense_batch.hip with one member's slices.
 #pragma once
 #include "dense_gj.hpp"
 

@@ -9,32 +9,18 @@
 #include <cmath>
 
 #include "dense.hpp"
-#include "dense_device.hpp"
+#include "dense_sign_body.hpp"
 #include "profiling.hpp"
 
 namespace dre {
 
-static constexpr double SCALE_OFF = 1e-2;        // tests/_sign_model.py: SCALE_OFF, STAG_STEP, STAG_DIST
-static constexpr double STAG_STEP = 1e-8;
-static constexpr double STAG_DIST = 1e-4;
-
-// ---- element-wise kernels with fused partial norms ----------------------------------------------------------------------------------
-// Z_{k+1} = Z_k / (2c) + (c/2) Y  (Y = E P_k), written to Z and to Zi (the next inversion's operand); partial sums of ||Z_{k+1} + E||^2,
-// ||Z_{k+1} - Z_k||^2 and ||Z_{k+1}||^2 per workgroup
+// ---- element-wise kernels with fused partial norms: the bodies are dense_sign_body.hpp's, shared with dense_batch.hip --------------------
 __global__ __launch_bounds__(256) void k_sign_update(int n, double* __restrict__ Z, double* __restrict__ Zi, const double* __restrict__ Y,
                                                      const double* __restrict__ E, double c, double* __restrict__ part) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    const size_t tot = (size_t)n * n;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const double z = Z[idx], zn = z / (2.0 * c) + (0.5 * c) * Y[idx];
-        const double a = zn + E[idx], b = zn - z;
-        s0 += a * a; s1 += b * b; s2 += zn * zn;
-        Z[idx] = zn; Zi[idx] = zn;
-    }
-    store_partials(part, s0, s1, s2);
+    sign_update_body(KERNEL_GRID_STRIDE, n, Z, Zi, Y, E, c, part);
 }
 
-// the stopping norm and the decision of the sign iteration (tests/_sign_model.py)
+// the stopping norm and the decision of the sign iteration
 __global__ __launch_bounds__(256) void k_sign_decide(int nparts, const double* __restrict__ part, const double* __restrict__ nE2, double tol,
                                                      SignCtl* ctl) {
     double s[3];
@@ -42,28 +28,19 @@ __global__ __launch_bounds__(256) void k_sign_decide(int nparts, const double* _
     if (threadIdx.x == 0) {
         const double e = sqrt(s[0] / nE2[0]), d = sqrt(s[1] / s[2]);
         ctl->dist = e; ctl->step = d;
-        ctl->done = !isfinite(e) || !isfinite(d) ? 3 : (e <= tol ? 1 : ((d <= STAG_STEP && e > STAG_DIST) ? 2 : 0));
+        ctl->done = sign_decision(e, d, tol);
     }
 }
 
-// Res = R + G + G' (G = F'XE) and its partial sums of squares
 __global__ __launch_bounds__(256) void k_res_sym(int n, const double* __restrict__ Rm, const double* __restrict__ G, double* __restrict__ Res,
                                                  double* __restrict__ part) {
-    double s = 0.0;
-    const size_t tot = (size_t)n * n;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (size_t)gridDim.x * blockDim.x) {
-        const int i = idx % n, j = idx / n;
-        const double v = Rm[idx] + G[idx] + G[j + (size_t)i * n];
-        Res[idx] = v;
-        s += v * v;
-    }
-    store_partials(part, s);
+    res_sym_body(KERNEL_GRID_STRIDE, n, Rm, G, Res, part);
 }
 
 __global__ __launch_bounds__(256) void k_res_finish(int nparts, const double* __restrict__ part, const double* __restrict__ nR2, SignCtl* ctl) {
     double s[1];
     load_partials(nparts, part, s);
-    if (threadIdx.x == 0) ctl->res = nR2[0] > 0.0 ? sqrt(s[0] / nR2[0]) : sqrt(s[0]);
+    if (threadIdx.x == 0) ctl->res = relative_residual(s[0], nR2[0]);
 }
 
 // out = sym?(a0 M0 + a1 M1 + a2 M2), n x n column-major, M0 with ld ld0, the others with ld n (M1, M2 may be null); out may alias an input unless sym
@@ -128,6 +105,14 @@ void SignLyap::ensure_dense_work() {
     W_ = square(c_, n_); T_ = square(c_, n_); Res_ = square(c_, n_);
 }
 
+std::string sign_failure(int done, int k, double dist, int maxiters) {
+    if (done == 4) return "singular Z_" + std::to_string(k) + " in the sign iteration (F singular?)";
+    if (done == 2) return "the pencil is not c-stable (sign iteration stagnated at ||Z + E|| / ||E|| = " + std::to_string(dist) + ")";
+    if (done == 3) return "the sign iteration produced non-finite values (pencil not c-stable?)";
+    return "the sign iteration did not reach -E in " + std::to_string(maxiters) + " iterations (||Z + E|| / ||E|| = " + std::to_string(dist) +
+           "); the pencil is not c-stable";
+}
+
 void SignLyap::factor(const Mat& F) {
     const int n = n_;
     DRE_REQUIRE(F.rows == n && F.cols == n, "dense path: F must be n x n");
@@ -141,7 +126,7 @@ void SignLyap::factor(const Mat& F) {
     for (int k = 0; k < maxiters_; ++k) {
         gj_invert(c_, Zi_, piv_.p, &ctl_.p->gj);
         h = read_back(c_, ctl_.p);
-        if (h.gj.singular) throw Error(ERR_SINGULAR, "dense path: singular Z_" + std::to_string(k) + " in the sign iteration (F singular?)");
+        if (h.gj.singular) throw Error(ERR_SINGULAR, "dense path: " + sign_failure(4, k, 0.0, maxiters_));
         const double cfac = scale ? std::exp((h.gj.logdet - logdetE_) / n) : 1.0;
         Mat P = Pstore_.colsview(k * n, n);
         gemm(c_, false, false, 1.0, Zi_, E_, 0.0, P, nullptr, "sign_gemm");            // P_k = Z_k^-1 E
@@ -156,13 +141,10 @@ void SignLyap::factor(const Mat& F) {
         iters_ = k + 1;
         h = read_back(c_, ctl_.p);
         if (h.done == 1) return;
-        if (h.done == 2)
-            throw Error(ERR_NOT_STABLE, "dense path: the pencil is not c-stable (sign iteration stagnated at ||Z + E|| / ||E|| = " + std::to_string(h.dist) + ")");
-        if (h.done == 3) throw Error(ERR_NOT_STABLE, "dense path: the sign iteration produced non-finite values (pencil not c-stable?)");
+        if (h.done) throw Error(ERR_NOT_STABLE, "dense path: " + sign_failure(h.done, k, h.dist, maxiters_));
         if (h.dist < SCALE_OFF) scale = false;
     }
-    throw Error(ERR_NOT_STABLE, "dense path: the sign iteration did not reach -E in " + std::to_string(maxiters_) + " iterations (||Z + E|| / ||E|| = " +
-                                    std::to_string(h.dist) + "); the pencil is not c-stable");
+    throw Error(ERR_NOT_STABLE, "dense path: " + sign_failure(5, maxiters_, h.dist, maxiters_));
 }
 
 void SignLyap::replay(const Mat& R, Mat& X) {
@@ -285,6 +267,30 @@ SignStats SignLyap::solve_t(const Mat& R, Mat& Y) {
 }
 
 // ---- Rosenbrock drivers (dense_ros{1,2,3,4}.jl of the reference) ------------------------------------------------
+void ros2_stages(Ctx* ctx, SignLyap& lyap, const Ros2Ops& o, const Mat& X, const Mat& Kt, double tau, double gamma, Mat& K1, Mat& K2,
+                 std::vector<SignStats>& solves) {
+    const char* tag = "dense_ros";
+    copy_mat(ctx, o.A, o.Acl);
+    gemm(ctx, false, true, -1.0, o.B, Kt, 1.0, o.Acl, nullptr, tag);                    // Acl = A - B K
+    comb(ctx, o.gF, gamma * tau, o.Acl, -0.5, &o.E);                                    // gF = gamma tau (A - BK) - E/2
+    lyap.factor(o.gF);
+    gemm(ctx, false, false, 1.0, X, o.E, 0.0, o.T, nullptr, tag);                       // R = C'C + A'XE + E'XA - K'K
+    gemm(ctx, true, false, 1.0, o.A, o.T, 0.0, o.AXE, nullptr, tag);
+    copy_mat(ctx, o.CtC, o.Racc);
+    gemm(ctx, false, true, -1.0, Kt, Kt, 1.0, o.Racc, nullptr, tag);
+    comb(ctx, o.Racc, 1.0, o.Racc, 2.0, &o.AXE);                                        // sym(R + 2 A'XE) below
+    comb(ctx, o.Rs, 1.0, o.Racc, 0.0, nullptr, 0.0, nullptr, true);
+    solves.push_back(lyap.solve(o.Rs, K1));
+    gemm(ctx, false, false, 1.0, K1, o.B, 0.0, o.XB, nullptr, tag);                     // V1 = E'(K1 B)
+    gemm(ctx, true, false, 1.0, o.E, o.XB, 0.0, o.V1, nullptr, tag);
+    gemm(ctx, false, false, 1.0, K1, o.E, 0.0, o.T, nullptr, tag);                      // E' K1 E
+    gemm(ctx, true, false, 1.0, o.E, o.T, 0.0, o.Racc, nullptr, tag);
+    comb(ctx, o.Racc, -(2.0 - 1.0 / gamma), o.Racc);
+    gemm(ctx, false, true, -tau * tau, o.V1, o.V1, 1.0, o.Racc, nullptr, tag);
+    comb(ctx, o.Rs, 1.0, o.Racc, 0.0, nullptr, 0.0, nullptr, true);
+    solves.push_back(lyap.solve(o.Rs, K2));
+}
+
 DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X0, double t0, double tf, double dt,
                                  int order, bool save_state, int maxiters, double tol, int max_refine) {
     const int n = E.rows, m = B.cols;
@@ -326,11 +332,14 @@ DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
     Mat Kt = feedback(X);
     out.Kt.push_back(Kt);
     const double gamma2 = 1.0 + 1.0 / std::sqrt(2.0);
+    const Ros2Ops ros2{E, A, B, CtC, Acl, gF, T, AXE, Racc, Rs, XB, V1};
     for (int i = 1; i <= nsteps; ++i) {
         const double tau = out.t[(size_t)i - 1] - out.t[(size_t)i];
-        // Acl = A - B K
-        copy_mat(ctx, A, Acl);
-        gemm(ctx, false, true, -1.0, B, Kt, 1.0, Acl, nullptr, "dense_ros");
+        // Acl = A - B K (Ros2: the first of ros2_stages)
+        auto closed_loop = [&] {
+            copy_mat(ctx, A, Acl);
+            gemm(ctx, false, true, -1.0, B, Kt, 1.0, Acl, nullptr, "dense_ros");
+        };
         // R of the first stage (Ros2..4): C'C + A'XE + E'XA - K'K
         auto first_rhs = [&]() {
             gemm(ctx, false, false, 1.0, X, E, 0.0, T, nullptr, "dense_ros");
@@ -341,6 +350,7 @@ DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
             sym_rhs();
         };
         if (order == 1) {
+            closed_loop();
             comb(ctx, gF, 1.0, Acl, -1.0 / (2.0 * tau), &E);                                 // F = (A - BK) - E/(2 tau)
             lyap.factor(gF);
             copy_mat(ctx, CtC, Racc);                                                        // R = C'C + K'K + E'XE / tau
@@ -349,21 +359,13 @@ DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
             comb(ctx, Rs, 1.0, Racc, 1.0 / tau, &K2, 0.0, nullptr, true);
             solve(Rs, X);
         } else if (order == 2) {
-            comb(ctx, gF, gamma2 * tau, Acl, -0.5, &E);                                       // gF = gamma tau (A - BK) - E/2
-            lyap.factor(gF);
-            first_rhs();
-            solve(Rs, K1);
-            EtKB(K1, V1);
-            EtME(K1, Racc);
-            comb(ctx, Racc, -(2.0 - 1.0 / gamma2), Racc);
-            gemm(ctx, false, true, -tau * tau, V1, V1, 1.0, Racc, nullptr, "dense_ros");
-            sym_rhs();
-            solve(Rs, K2);
+            ros2_stages(ctx, lyap, ros2, X, Kt, tau, gamma2, K1, K2, out.solves);
             comb(ctx, X, 1.0, X, tau / 2.0, &K2, (tau / 2.0) * (4.0 - 1.0 / gamma2), &K1);  // X + tau/2 (Kt2 + (4 - 1/gamma) K1)
         } else if (order == 3) {
             const double g = 7.886751345948129e-1, a21 = 1.267949192431123;
             const double c21 = -1.607695154586736, c31 = -3.464101615137755, c32 = -1.732050807568877;
             const double m1 = 2.0, m2 = 5.773502691896258e-1, m3 = 4.226497308103742e-1;
+            closed_loop();
             comb(ctx, gF, 1.0, Acl, -1.0 / (2.0 * g * tau), &E);                            // gF = (A - BK) - E/(2 gamma tau)
             lyap.factor(gF);
             first_rhs();
@@ -380,6 +382,7 @@ DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat
             comb(ctx, X, 1.0, X, m1 + m2 + m3, &K1, m2, &K2);
             comb(ctx, X, 1.0, X, m3, &K3);
         } else {
+            closed_loop();
             comb(ctx, gF, tau / 2.0, Acl, -0.5, &E);                                         // gF = (tau (A - BK) - E)/2
             lyap.factor(gF);
             first_rhs();

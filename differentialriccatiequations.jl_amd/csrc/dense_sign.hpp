@@ -64,6 +64,18 @@ class SignLyap {
     DevArr<double> part_, nrm_;
 };
 
+// What went wrong in a sign iteration that ended with done = 2 (stagnated away from -E), 3 (non-finite), 4 (singular Z_k) or 5 (out of
+// maxiters), shared by SignLyap and BatchedSignLyap, which put "dense path: " or "batched dense path, member b: " in front.  k: the iteration
+// of the singular Z_k; dist: the last ||Z + E|| / ||E||.
+std::string sign_failure(int done, int k, double dist, int maxiters);
+
+// The stages of one Ros2 step from (X, Kt) with step tau, from Acl = A - BK through the solve for K2, for dense_gdre_solve (order 2) and
+// dense_gdre_solve_adaptive; the caller does its own last combination of X, K1 and K2.  o: the operands and the driver's work matrices
+// (n x n; XB, V1 n x m); both solves' statistics are appended to solves.
+struct Ros2Ops { const Mat &E, &A, &B, &CtC; Mat &Acl, &gF, &T, &AXE, &Racc, &Rs, &XB, &V1; };
+void ros2_stages(Ctx* ctx, SignLyap& lyap, const Ros2Ops& o, const Mat& X, const Mat& Kt, double tau, double gamma, Mat& K1, Mat& K2,
+                 std::vector<SignStats>& solves);
+
 struct DenseGdreResult {
     std::vector<double> t;
     std::vector<Mat> Kt;         // K(t_i)' as n x m
