@@ -113,6 +113,7 @@ PROTOTYPES = {
     "dre_spmm": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, C.c_double, _vp]),
     "dre_orthf": (C.c_int, [_vp, _vp, _pvp, _pvp]),
     "dre_sym_eig": (C.c_int, [_vp, _vp, C.c_double, _pvp, _pvp]),
+    "dre_sym_eig_probe": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, _pi32, C.c_int, _pi64, _pd] + [_pvp] * 7),
     "dre_sym_eig_jacobi": (C.c_int, [_vp, _vp, C.c_double, _pvp, _pvp, _pi64]),
     "dre_shift_factor": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_double, _pvp]),
     "dre_shift_solve": (C.c_int, [_vp, _vp, _vp, _pvp, _pvp]),

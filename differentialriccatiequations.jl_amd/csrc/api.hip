@@ -84,7 +84,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 113; }   // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 114; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -94,6 +94,7 @@ int dre_version(void) { return 113; }   // 101: dense path (dre_dense_gale_solve
                                         //      dre_balance_lr_batched)
                                         // 112: frequency response batched by frequency (dre_freq_response, dre_freq_response_batched)
                                         // 113: LQG balanced truncation from one Hamiltonian sign iteration (dre_dense_gare_solve_pair, dre_lqg_balance)
+                                        // 114: dre_sym_eig_probe (test surface of the Householder + QL eigensolver); sym_eig refuses a non-finite input
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -678,6 +679,55 @@ int dre_sym_eig(dre_ctx* ctx, const dre_dense* S, double tolfac, dre_dense** val
             DRE_HIP(hipStreamSynchronize(c->stream));
         }
         *values = W; *vectors = V;
+    });
+}
+// ---- dre_sym_eig_probe: the stages of the Householder + QL solver one by one (test and diagnostic surface) --------------------------------
+int dre_sym_eig_probe(dre_ctx* ctx, const dre_dense* S, double tolfac, int want_eig, double abs_tol, int floor_mode, double deflate, const int32_t* ids,
+                      int nids, int64_t* ii, double* snorm, dre_dense** d, dre_dense** e, dre_dense** tau, dre_dense** V, dre_dense** w, dre_dense** Z,
+                      dre_dense** B) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        dre_dense** outs[7] = {d, e, tau, V, w, Z, B};
+        for (dre_dense** o : outs) if (o) *o = nullptr;
+        DRE_REQUIRE(S && ii, "dre_sym_eig_probe: null argument");
+        DRE_REQUIRE(S->m.rows == S->m.cols, "dre_sym_eig_probe: square matrix expected");
+        DRE_REQUIRE(S->m.rows <= 8192, "dre_sym_eig_probe: order above 8192 not supported by the single-workgroup reduction");
+        DRE_REQUIRE(nids <= 0 || ids, "dre_sym_eig_probe: ids missing");
+        DRE_REQUIRE(nids == 0 || B, "dre_sym_eig_probe: ids without a place for B");
+        DRE_REQUIRE(tolfac > 0.0 && deflate >= 0.0, "dre_sym_eig_probe: tolfac must be positive, deflate not negative");
+        const int q = S->m.rows;
+        Mat A(c, q, q);
+        copy_mat(c, S->m, A);
+        struct Method0 { Ctx* c; int was; ~Method0() { c->sym_eig_method = was; } } method0{c, c->sym_eig_method};
+        c->sym_eig_method = 0;
+        SymEig r = sym_eig(c, A, tolfac, want_eig != 0, abs_tol, floor_mode != 0, deflate);
+        std::vector<int> cols;
+        if (nids < 0) { cols.resize((size_t)r.j); for (int i = 0; i < r.j; ++i) cols[(size_t)i] = i; }          // (every column)
+        else cols.assign(ids, ids + nids);
+        for (int id : cols) DRE_REQUIRE(id >= 0 && id < r.j, "dre_sym_eig_probe: an entry of ids lies outside [0, jdim)");
+        ii[0] = r.j; ii[1] = r.nref; ii[2] = q;
+        if (snorm) *snorm = r.snorm;
+        std::vector<std::unique_ptr<dre_dense>> made;          // (an error below frees what was made; the handles go out together at the end)
+        auto column = [&](const double* src, bool on_host, int n) {
+            made.emplace_back(new dre_dense());
+            made.back()->m = Mat(c, n, 1);
+            if (n) DRE_HIP(hipMemcpyAsync(made.back()->m.p, src, (size_t)n * sizeof(double), on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+            return made.back().get();
+        };
+        auto matrix = [&](const Mat& M) { made.emplace_back(new dre_dense()); made.back()->m = M; return made.back().get(); };
+        const bool has_z = want_eig && r.j > 0;
+        dre_dense* od = d ? column(r.d.p, false, r.j) : nullptr;
+        dre_dense* oe = e ? column(r.e.p, false, std::max(r.j - 1, 0)) : nullptr;
+        dre_dense* ot = tau ? column(r.tau.p, false, q) : nullptr;
+        dre_dense* oV = V ? matrix(q ? r.V : Mat(c, 0, 0)) : nullptr;
+        dre_dense* ow = (w && has_z) ? column(r.w.data(), true, r.j) : nullptr;
+        dre_dense* oZ = (Z && has_z) ? matrix(r.Z) : nullptr;
+        dre_dense* oB = nullptr;
+        if (B && !cols.empty()) oB = matrix(sym_eig_backtransform(c, r, cols));
+        c->sync();          // (r.w is host memory of this scope)
+        dre_dense* res[7] = {od, oe, ot, oV, ow, oZ, oB};
+        for (int k = 0; k < 7; ++k) if (outs[k]) *outs[k] = res[k];
+        for (auto& m : made) m.release();
     });
 }
 int dre_sym_eig_jacobi(dre_ctx* ctx, const dre_dense* S, double tol, dre_dense** values, dre_dense** vectors, int64_t* stats) {

@@ -1395,6 +1395,9 @@ SymEig sym_eig(Ctx* ctx, Mat& S, double tolfac, bool want_eig, double abs_tol, b
     out.j = hi.jdim;
     out.nref = hi.nref;
     out.snorm = hi.snorm;
+    // (a NaN or Inf entry, or finite entries whose squares overflow: every comparison of the reduction was false, so it reduced all q columns of
+    // garbage; nothing of it reaches the QL iteration or a caller's sort)
+    if (!std::isfinite(hi.snorm)) throw Error(ERR_INVALID, "sym_eig: non-finite input");
     if (out.j == 0 || !want_eig) return out;
     const int j = out.j;
     out.Z = Mat(ctx, j, j);

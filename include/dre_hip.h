@@ -160,6 +160,24 @@ int dre_ctx_set_orthf(dre_ctx* ctx, dre_orthf_fn fn, void* user);
 /* eigen(Symmetric(S)) with early-terminating tridiagonalisation (src/LDLt.jl:214); returns the j computed
  * eigenpairs (all those above tolfac*eps*||S||_F in magnitude), values ascending */
 int dre_sym_eig(dre_ctx* ctx, const dre_dense* S, double tolfac, dre_dense** values, dre_dense** vectors);
+/* Test and diagnostic surface of that solver (dre_version >= 114): ONE run of its chain with the arguments the library's own callers pass, and
+ * every intermediate result.  The reduction stops at the first j with ||S22||_F^2 + 2 e_(j-1)^2 <= tol^2, where S22 is the trailing block not
+ * yet reduced and tol = tolfac eps ||S||_F;  abs_tol > 0 replaces tol (floor_mode = 0) or is its lower limit (floor_mode = 1: tol =
+ * max(tolfac eps ||S||_F, abs_tol)).  deflate: an off-diagonal entry of T_j at or below deflate eps ||S||_F counts as zero in the QL iteration
+ * for jdim > 128; at jdim <= 128 the constant is 1e-3 whatever deflate says.  S is left untouched; the context option "sym_eig_method" does
+ * not reroute the call.
+ * ii (3): [0] jdim, the order of the kept tridiagonal matrix [1] nref, the reflectors generated [2] q;  *snorm = ||S||_F.
+ * *d (jdim x 1), *e (max(jdim - 1, 0) x 1): T_j;  *tau (q x 1, zero from nref on);  *V (q x q): column i holds reflector i, H_i = I - tau_i v v',
+ * v(i + 1) = 1, zero above, zero columns from nref on.  want_eig != 0 and jdim > 0: *w (jdim x 1) the eigenvalues of T_j, UNSORTED, and *Z
+ * (jdim x jdim), column i the eigenvector of w(i); otherwise both are NULL.
+ * ids (nids entries of [0, jdim), any order, repeats allowed): *B (q x nids) = H_0 ... H_(nref-1) [Z(:, ids); 0], with want_eig = 0 the same
+ * with the unit vectors e_ids in the place of Z's columns; nids < 0: every column 0 .. jdim - 1 (ids is not read); no column: *B is NULL.
+ * Every output pointer but ii may be NULL (B only with nids = 0).
+ * DRE_ERR_INVALID before any launch for a matrix that is not square or of an order above 8192; after the reduction, before anything else is
+ * launched, for a non-finite S (or one whose squares overflow) and for an entry of ids outside [0, jdim).  The context stays usable. */
+int dre_sym_eig_probe(dre_ctx* ctx, const dre_dense* S, double tolfac, int want_eig, double abs_tol, int floor_mode, double deflate, const int32_t* ids,
+                      int nids, int64_t* ii /* 3 */, double* snorm, dre_dense** d, dre_dense** e, dre_dense** tau, dre_dense** V, dre_dense** w,
+                      dre_dense** Z, dre_dense** B);
 /* eigen(Symmetric(S)) by two-sided cyclic block Jacobi on the whole device (blocks of 16, round-robin ordering, both products of the update on
  * v_mfma_f64_16x16x4_f64): all q eigenpairs, values ascending, S untouched (full symmetric storage; indefinite, rank-deficient and clustered
  * spectra are fine).  Converged when off(A) <= tol ||A||_F; tol <= 0: q eps.  stats (may be NULL): [0] block sweeps, [1] rounds.
