@@ -1508,6 +1508,53 @@ def dense_invert_batch(As, ctx=None):
     return [(Ad[b].numpy(), piv[b].copy(), float(ld[b])) for b in range(nb)]
 
 
+COMPLEX_PANEL_MAX_N = 4096       # the complex register panel of csrc/dense_cgj.hip
+
+
+def dense_invert_complex_batch(As, errors="raise", ctx=None):
+    """inv(A_b) for a list of square complex matrices of one order n <= 4096 in shared launches (`dre_dense_invert_complex_batched`): the
+    native complex Gauss-Jordan inversion on the register panel, pivoting by |re| + |im|, 8 n³ real flops and 2 n² doubles per member ->
+    the list of (Ainv complex, piv, logabsdet = log|det A_b|).  A singular member (exactly zero or non-finite pivot) raises DREError(-4)
+    naming it; errors="return" puts that DREError in the member's place and returns the others.  An empty list, a member that is not
+    n x n and n > 4096 are errors before anything runs on the device."""
+    name = "dense_invert_complex_batch"
+    _batch_errors_arg(name, errors)
+    As = [np.asarray(A, dtype=complex) for A in As]
+    if len(As) == 0:
+        raise ValueError(f"{name}: empty list of matrices; nothing was run on the device")
+    n = As[0].shape[0] if As[0].ndim == 2 else -1
+    for b, A in enumerate(As):
+        if A.ndim != 2 or A.shape != (n, n) or n < 1:
+            raise ValueError(f"{name}: member {b} has shape {A.shape}, expected a square matrix of the order of member 0; nothing was run on the device")
+    if n > COMPLEX_PANEL_MAX_N:
+        raise ValueError(f"{name}: the complex register panel inverts matrices of order n <= {COMPLEX_PANEL_MAX_N}; got n = {n}; nothing was run "
+                         "on the device")
+    ctx = ctx or dev.default_context()
+    nb = len(As)
+    Ar, Ai = [ctx.upload(_dense_f64(A.real)) for A in As], [ctx.upload(_dense_f64(A.imag)) for A in As]
+    piv, ld, status = np.zeros((nb, n), dtype=np.int32), np.zeros(nb), np.zeros(nb, dtype=np.int32)
+    ctx.chk(ctx.lib.dre_dense_invert_complex_batched(ctx.ptr, nb, _handle_array(Ar), _handle_array(Ai), piv.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     ld.ctypes.data_as(C.POINTER(C.c_double)), status.ctypes.data_as(C.POINTER(C.c_int32))))
+    out = []
+    for b, e in enumerate(_batch_errors(ctx, status)):
+        if e is not None:
+            if errors == "raise":
+                raise e
+            out.append(e)
+        else:
+            out.append((Ar[b].numpy() + 1j * Ai[b].numpy(), piv[b].copy(), float(ld[b])))
+    return out
+
+
+def dense_invert_complex(A, ctx=None):
+    """inv(A) of a square complex matrix of order n <= 4096 by the device's complex Gauss-Jordan inversion (a batch of one of
+    `dense_invert_complex_batch`) -> (Ainv complex, piv, logabsdet).  A singular matrix raises DREError(-4)."""
+    A = np.asarray(A, dtype=complex)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError(f"dense_invert_complex: a square matrix is expected, got shape {A.shape}; nothing was run on the device")
+    return dense_invert_complex_batch([A], ctx=ctx)[0]
+
+
 def _dense_result(ctx, r, prob, return_stats):
     """a dense dre_gdre_result handle -> DRESolution (or (DRESolution, stats)); frees the handle"""
     lib = ctx.lib
@@ -1809,7 +1856,7 @@ class ReducedModel:
 
     def freq_response(self, omega, D=None, **kw):
         """H_r(iω) = Cr (iω I - Ar)⁻¹ Br (+ D) of the reduced model at every frequency of omega, on the device: `freq_response` with E_r = I
-        and its keyword arguments."""
+        and its keyword arguments (method="embedding" | "complex" among them)."""
         return freq_response(self.Er, self.Ar, self.Br, self.Cr, omega, D=D, **kw)
 
 
@@ -2126,20 +2173,32 @@ def balanced_truncation_batch(systems, alg=MatrixSign(), order=None, tol=1e-8, e
 # Frequency response, batched by frequency                                  csrc/freq_response.hip
 # ------------------------------------------------------------------------------------------------
 FREQ_RESPONSE_MAX_N = 2048      # the real form of iωE - A has order 2n and is inverted with the register panel (2n <= 4096)
+TRANSFER_MAX_N = COMPLEX_PANEL_MAX_N   # method="complex": s E - A itself goes through the complex register panel
+FREQ_METHODS = ("embedding", "complex")
 
 
-def _freq_check(name, systems, omega, D, errors, chunk):
-    """the argument errors of the frequency-response calls, before anything runs on the device -> (list of (E, A, B, C), omega, D)"""
+def _freq_method(name, method):
+    if method not in FREQ_METHODS:
+        raise ValueError(f"{name}: method must be 'embedding' (the real form of order 2n, n <= {FREQ_RESPONSE_MAX_N}) or 'complex' (the complex "
+                         f"Gauss-Jordan inversion, n <= {TRANSFER_MAX_N}), got {method!r}; nothing was run on the device")
+
+
+def _freq_check(name, systems, omega, D, errors, chunk, method="embedding", points=False):
+    """the argument errors of the frequency-response calls, before anything runs on the device -> (list of (E, A, B, C), omega, D); points:
+    omega holds complex points s (transfer_function), not real frequencies"""
     _batch_errors_arg(name, errors)
+    _freq_method(name, method)
     if chunk is not None and (isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= 65535):
         raise ValueError(f"{name}: chunk must be None (as many frequencies as fit) or an int in 1 .. 65535; nothing was run on the device")
-    w = np.asarray(omega, dtype=float)
+    what = "s" if points else "omega"
+    w = np.asarray(omega, dtype=complex if points else float)
     if w.ndim != 1:
-        raise ValueError(f"{name}: omega must be a one-dimensional array of frequencies, got shape {w.shape}; nothing was run on the device")
+        raise ValueError(f"{name}: {what} must be a one-dimensional array of {'points' if points else 'frequencies'}, got shape {w.shape}; nothing "
+                         "was run on the device")
     if w.size < 1:
-        raise ValueError(f"{name}: at least one frequency is needed; nothing was run on the device")
+        raise ValueError(f"{name}: at least one {'point' if points else 'frequency'} is needed; nothing was run on the device")
     if not np.isfinite(w).all():
-        raise ValueError(f"{name}: omega has a non-finite entry; nothing was run on the device")
+        raise ValueError(f"{name}: {what} has a non-finite entry; nothing was run on the device")
     mats = []
     for b, sys_ in enumerate(systems):
         ms = []
@@ -2160,9 +2219,12 @@ def _freq_check(name, systems, omega, D, errors, chunk):
             raise ValueError(f"{name}: member {b} has (n, m, q) = {shape(t)}, member 0 has {shape(mats[0])}: the systems of a batch share n, m "
                              "and q; nothing was run on the device")
     n, m, q = shape(mats[0])
-    if n > FREQ_RESPONSE_MAX_N:
+    if method == "embedding" and n > FREQ_RESPONSE_MAX_N:
         raise ValueError(f"{name}: the real form of i omega E - A has order 2n and goes through the register panel, n <= {FREQ_RESPONSE_MAX_N}; "
                          f"got n = {n}; nothing was run on the device")
+    if method == "complex" and n > TRANSFER_MAX_N:
+        raise ValueError(f"{name}: s E - A goes through the complex register panel, n <= {TRANSFER_MAX_N}; got n = {n}; nothing was run on the "
+                         "device")
     if D is not None:
         D = np.asarray(D)
         if D.shape != (q, m):
@@ -2170,8 +2232,9 @@ def _freq_check(name, systems, omega, D, errors, chunk):
     return mats, w, D
 
 
-def _freq_run(name, mats, w, chunk, ctx):
-    """-> (H (nsys, K, q, m) complex, list of DREError / None per member s K + k, info)"""
+def _freq_run(name, mats, w, chunk, ctx, method="embedding"):
+    """-> (H (nsys, K, q, m) complex, list of DREError / None per member s K + k, info).  method="embedding": w real frequencies
+    (`dre_freq_response`); "complex": w complex points (`dre_transfer_eval`)"""
     ctx = ctx or dev.default_context()
     nsys, K = len(mats), w.size
     n, m, q = mats[0][0].shape[0], mats[0][2].shape[1], mats[0][3].shape[0]
@@ -2179,14 +2242,20 @@ def _freq_run(name, mats, w, chunk, ctx):
     re, im = np.zeros(nsys * K * q * m), np.zeros(nsys * K * q * m)
     status, info = np.zeros(nsys * K, dtype=np.int32), (C.c_int64 * 2)()
     pd, pi32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    wc = np.ascontiguousarray(w)
-    tail = (K, wc.ctypes.data_as(pd), int(chunk or 0), re.ctypes.data_as(pd), im.ctypes.data_as(pd), status.ctypes.data_as(pi32), info)
-    if nsys == 1:
-        ctx.chk(ctx.lib.dre_freq_response(ctx.ptr, *(u.ptr for u in ups[0]), *tail))
+    if method == "complex":
+        pts = np.asarray(w, dtype=complex)
+        sr, si = np.ascontiguousarray(pts.real), np.ascontiguousarray(pts.imag)
+        points, single, batched = (sr.ctypes.data_as(pd), si.ctypes.data_as(pd)), ctx.lib.dre_transfer_eval, ctx.lib.dre_transfer_eval_batched
     else:
-        ctx.chk(ctx.lib.dre_freq_response_batched(ctx.ptr, nsys, *(_handle_array([u[j] for u in ups]) for j in range(4)), *tail))
+        wc = np.ascontiguousarray(w)
+        points, single, batched = (wc.ctypes.data_as(pd),), ctx.lib.dre_freq_response, ctx.lib.dre_freq_response_batched
+    tail = (K, *points, int(chunk or 0), re.ctypes.data_as(pd), im.ctypes.data_as(pd), status.ctypes.data_as(pi32), info)
+    if nsys == 1:
+        ctx.chk(single(ctx.ptr, *(u.ptr for u in ups[0]), *tail))
+    else:
+        ctx.chk(batched(ctx.ptr, nsys, *(_handle_array([u[j] for u in ups]) for j in range(4)), *tail))
     H = (re + 1j * im).reshape(nsys, K, m, q).transpose(0, 1, 3, 2)         # members hold q x m column-major
-    return H, _batch_errors(ctx, status), dict(chunk=int(info[0]), chunks=int(info[1]), members=nsys * K, order=2 * n)
+    return H, _batch_errors(ctx, status), dict(chunk=int(info[0]), chunks=int(info[1]), members=nsys * K, order=n if method == "complex" else 2 * n)
 
 
 def _freq_out(H, errs, info, errors, return_info):
@@ -2196,44 +2265,85 @@ def _freq_out(H, errs, info, errors, return_info):
     return (H, errs, info) if return_info else (H, errs)
 
 
-def freq_response(E, A, B, C, omega, D=None, errors="raise", chunk=None, ctx=None, return_info=False):
+def _freq_points(w, method):
+    """what _freq_run takes: the frequencies themselves, or the points i w of the complex method"""
+    return 1j * w if method == "complex" else w
+
+
+def freq_response(E, A, B, C, omega, D=None, errors="raise", chunk=None, ctx=None, return_info=False, method="embedding"):
     """H(iω_k) = C (iω_k E - A)⁻¹ B + D of the dense descriptor system E ẋ = A x + B u, y = C x + D u at every frequency of omega, in shared
-    launches with the frequency on the member axis (`dre_freq_response`): a complex array (K, q, m).  Per frequency the real form
-    [[-A, -ωE], [ωE, -A]] of iωE - A is inverted with the register panel, so n <= 2048; 16 n³ flops per frequency.  E may be singular; D
-    (q x m) is added on the host.  The sweep runs in chunks of `chunk` frequencies (None: as many as fit the device memory); a frequency's
-    result is bit for bit the same whatever the others are and whatever chunk it falls in.
+    launches with the frequency on the member axis: a complex array (K, q, m).
+    method="embedding" (the default, `dre_freq_response`): per frequency the real form [[-A, -ωE], [ωE, -A]] of iωE - A is inverted with the
+    register panel, so n <= 2048; 16 n³ flops and 4 n² doubles per frequency.  method="complex" (`dre_transfer_eval` at s = iω): iωE - A
+    itself is inverted by the complex Gauss-Jordan panel, n <= 4096; 8 n³ flops and 2 n² doubles per frequency; the two agree to rounding,
+    not bit for bit.  E may be singular; D (q x m) is added on the host.  The sweep runs in chunks of `chunk` frequencies (None: as many as
+    fit the device memory); a frequency's result is bit for bit the same whatever the others are and whatever chunk it falls in.
     A frequency at which iωE - A is exactly singular (ω on a pole, a NaN in the system) fails alone: its H is NaN.  errors="raise" raises that
     DREError(-4); errors="return" returns (H, errs) with errs[k] None or the DREError of frequency k.  return_info=True appends
-    dict(chunk, chunks, members, order = 2n).  Wrong types, shapes, a non-finite ω and an empty omega are errors before anything runs on the
-    device."""
+    dict(chunk, chunks, members, order = 2n, or n for "complex").  Wrong types, shapes, an unknown method, a non-finite ω and an empty omega
+    are errors before anything runs on the device."""
     name = "freq_response"
-    mats, w, D = _freq_check(name, [(E, A, B, C)], omega, D, errors, chunk)
-    H, errs, info = _freq_run(name, mats, w, chunk, ctx)
+    mats, w, D = _freq_check(name, [(E, A, B, C)], omega, D, errors, chunk, method)
+    H, errs, info = _freq_run(name, mats, _freq_points(w, method), chunk, ctx, method)
     H = H[0] if D is None else H[0] + D
     return _freq_out(H, errs, info, errors, return_info)
 
 
-def freq_response_batch(systems, omega, errors="raise", chunk=None, ctx=None, return_info=False):
+def freq_response_batch(systems, omega, errors="raise", chunk=None, ctx=None, return_info=False, method="embedding"):
     """`freq_response` for an ensemble: systems is the list of (E, A, B, C) of one (n, m, q) that `balanced_truncation_batch` takes -> a
-    complex array (nsys, K, q, m) from one `dre_freq_response_batched` call, member s K + k = system s at ω_k.  Entry (s, k) is bit for bit
-    what freq_response gives for system s at ω_k.  errors="return": (H, errs) with errs[s][k]."""
+    complex array (nsys, K, q, m) from one `dre_freq_response_batched` call (method="complex": one `dre_transfer_eval_batched` call, n <=
+    4096), member s K + k = system s at ω_k.  Entry (s, k) is bit for bit what freq_response gives for system s at ω_k with the same
+    method.  errors="return": (H, errs) with errs[s][k]."""
     name = "freq_response_batch"
     systems = _batch_members(name, systems, "(E, A, B, C) systems")
     for b, sys_ in enumerate(systems):
         if not isinstance(sys_, (tuple, list)) or len(sys_) != 4:
             raise TypeError(f"{name}: member {b} must be a tuple (E, A, B, C); nothing was run on the device")
-    mats, w, _ = _freq_check(name, systems, omega, None, errors, chunk)
-    H, errs, info = _freq_run(name, mats, w, chunk, ctx)
+    mats, w, _ = _freq_check(name, systems, omega, None, errors, chunk, method)
+    H, errs, info = _freq_run(name, mats, _freq_points(w, method), chunk, ctx, method)
     if errors == "raise":
         return _freq_out(H, errs, info, errors, return_info)
     K = w.size
     return _freq_out(H, [errs[s * K:(s + 1) * K] for s in range(len(mats))], info, errors, return_info)
 
 
-def sigma_response(E, A, B, C, omega, D=None, errors="raise", chunk=None, ctx=None, return_info=False):
+def transfer_function(E, A, B, C, s, D=None, errors="raise", chunk=None, ctx=None, return_info=False):
+    """H(s_k) = C (s_k E - A)⁻¹ B + D at every complex point of s, in shared launches with the point on the member axis
+    (`dre_transfer_eval`): a complex array (K, q, m).  Per point the planes of s E - A are inverted by the complex Gauss-Jordan panel
+    (n <= 4096; 8 n³ flops, 2 n² doubles), with one refinement step whose residual is formed from E and A.  Points off the imaginary axis
+    are what interpolation-based model reduction and pole/zero work need; at s = iω this is `freq_response(..., method="complex")`.
+    Everything else is `freq_response`'s: E may be singular, D is added on the host, chunks, a point on a pole fails alone (DREError(-4), its
+    H NaN), errors="return", return_info (order = n), and the argument errors before anything runs on the device (a non-finite point among
+    them)."""
+    name = "transfer_function"
+    mats, pts, D = _freq_check(name, [(E, A, B, C)], s, D, errors, chunk, "complex", points=True)
+    H, errs, info = _freq_run(name, mats, pts, chunk, ctx, "complex")
+    H = H[0] if D is None else H[0] + D
+    return _freq_out(H, errs, info, errors, return_info)
+
+
+def transfer_function_batch(systems, s, errors="raise", chunk=None, ctx=None, return_info=False):
+    """`transfer_function` for an ensemble of (E, A, B, C) of one (n, m, q) -> a complex array (nsys, K, q, m) from one
+    `dre_transfer_eval_batched` call, member s K + k = system s at point k, bit for bit what transfer_function gives for it.
+    errors="return": (H, errs) with errs[s][k]."""
+    name = "transfer_function_batch"
+    systems = _batch_members(name, systems, "(E, A, B, C) systems")
+    for b, sys_ in enumerate(systems):
+        if not isinstance(sys_, (tuple, list)) or len(sys_) != 4:
+            raise TypeError(f"{name}: member {b} must be a tuple (E, A, B, C); nothing was run on the device")
+    mats, pts, _ = _freq_check(name, systems, s, None, errors, chunk, "complex", points=True)
+    H, errs, info = _freq_run(name, mats, pts, chunk, ctx, "complex")
+    if errors == "raise":
+        return _freq_out(H, errs, info, errors, return_info)
+    K = pts.size
+    return _freq_out(H, [errs[i * K:(i + 1) * K] for i in range(len(mats))], info, errors, return_info)
+
+
+def sigma_response(E, A, B, C, omega, D=None, errors="raise", chunk=None, ctx=None, return_info=False, method="embedding"):
     """The singular values of H(iω_k), descending: a real array (K, min(q, m)), the data of a sigma plot.  H comes from `freq_response` (same
-    arguments and returns); the K tiny SVDs run on the host on purpose (numpy.linalg.svd).  A failed frequency's row is NaN."""
-    out = freq_response(E, A, B, C, omega, D=D, errors=errors, chunk=chunk, ctx=ctx, return_info=return_info)
+    arguments and returns, `method` among them); the K tiny SVDs run on the host on purpose (numpy.linalg.svd).  A failed frequency's row
+    is NaN."""
+    out = freq_response(E, A, B, C, omega, D=D, errors=errors, chunk=chunk, ctx=ctx, return_info=return_info, method=method)
     H = out[0] if isinstance(out, tuple) else out
     S = np.full((H.shape[0], min(H.shape[1:])), np.nan)
     ok = np.isfinite(H).all(axis=(1, 2))
@@ -2242,18 +2352,19 @@ def sigma_response(E, A, B, C, omega, D=None, errors="raise", chunk=None, ctx=No
     return (S,) + out[1:] if isinstance(out, tuple) else S
 
 
-def bt_error(E, A, B, C, rom, omega, chunk=None, ctx=None):
+def bt_error(E, A, B, C, rom, omega, chunk=None, ctx=None, method="embedding"):
     """Balanced truncation's guarantee, measured: max_k ‖H(iω_k) - H_r(iω_k)‖₂ of the full system against the ReducedModel `rom`, both
-    frequency responses from the device -> dict(max_error, omega_at_max, bound = 2 Σ_{i>r} hsv_i, ratio = bound / max_error)."""
+    frequency responses from the device -> dict(max_error, omega_at_max, bound = 2 Σ_{i>r} hsv_i, ratio = bound / max_error).  method: as
+    `freq_response` ("complex" serves n <= 4096 at half the flops)."""
     if not isinstance(rom, ReducedModel):
         raise TypeError(f"bt_error: rom must be a ReducedModel, not {type(rom).__name__}; nothing was run on the device")
     name = "bt_error"
-    mats, w, _ = _freq_check(name, [(E, A, B, C)], omega, None, "raise", chunk)
+    mats, w, _ = _freq_check(name, [(E, A, B, C)], omega, None, "raise", chunk, method)
     if (rom.Br.shape[1], rom.Cr.shape[0]) != (mats[0][2].shape[1], mats[0][3].shape[0]):
         raise ValueError(f"{name}: the reduced model has (m, q) = {(rom.Br.shape[1], rom.Cr.shape[0])}, the system "
                          f"{(mats[0][2].shape[1], mats[0][3].shape[0])}; nothing was run on the device")
-    H = freq_response(E, A, B, C, w, chunk=chunk, ctx=ctx)
-    Hr = rom.freq_response(w, chunk=chunk, ctx=ctx)
+    H = freq_response(E, A, B, C, w, chunk=chunk, ctx=ctx, method=method)
+    Hr = rom.freq_response(w, chunk=chunk, ctx=ctx, method=method)
     err = np.linalg.svd(H - Hr, compute_uv=False)[:, 0]
     k = int(np.argmax(err))
     bound = 2.0 * float(np.sum(np.asarray(rom.hsv, dtype=float)[rom.order:][::-1]))
@@ -2290,7 +2401,8 @@ class LQGReducedModel:
         return self.Ac, self.Lr, self.Kr
 
     def freq_response(self, omega, D=None, **kw):
-        """H_r(iω) = Cr (iω I - Ar)⁻¹ Br (+ D) of the reduced model at every frequency of omega, on the device (as `ReducedModel.freq_response`)."""
+        """H_r(iω) = Cr (iω I - Ar)⁻¹ Br (+ D) of the reduced model at every frequency of omega, on the device (as `ReducedModel.freq_response`;
+        keywords as `freq_response`, method="embedding" | "complex" among them)."""
         return freq_response(self.Er, self.Ar, self.Br, self.Cr, omega, D=D, **kw)
 
 
@@ -2377,15 +2489,15 @@ def lqg_characteristic_values(E, A, B, C, alg=MatrixSign(), ctx=None):
     return _lqg_balance("lqg_characteristic_values", E, A, B, C, alg, None, 0.0, ctx)[0].mu
 
 
-def lqg_error(E, A, B, C, rom, omega, chunk=None, ctx=None):
+def lqg_error(E, A, B, C, rom, omega, chunk=None, ctx=None, method="embedding"):
     """LQG balanced truncation's guarantee, measured -> (err, bound): err = max_k ‖[N; M](iω_k) − [N_r; M_r](iω_k)‖₂ of the normalised right
     coprime factors of the plant and of the LQGReducedModel `rom`, from two `freq_response` calls on (E, A − BK, B, [C; −K]) with
     D = [0; I], K = BᵀXE, and on (I, Ar − Br Kr, Br, [Cr; −Kr]); bound = 2 Σ_{i>r} μ_i / √(1 + μ_i²).  K is taken from `rom`; a model
-    without it costs one regulator solve."""
+    without it costs one regulator solve.  method: as `freq_response` ("complex" serves n <= 4096 at half the flops)."""
     name = "lqg_error"
     if not isinstance(rom, LQGReducedModel):
         raise TypeError(f"{name}: rom must be an LQGReducedModel, not {type(rom).__name__}; nothing was run on the device")
-    mats, w, _ = _freq_check(name, [(E, A, B, C)], omega, None, "raise", chunk)
+    mats, w, _ = _freq_check(name, [(E, A, B, C)], omega, None, "raise", chunk, method)
     Eh, Ah, Bh, Ch = mats[0]
     m, q = Bh.shape[1], Ch.shape[0]
     if (rom.Br.shape[1], rom.Cr.shape[0]) != (m, q):
@@ -2394,8 +2506,8 @@ def lqg_error(E, A, B, C, rom, omega, chunk=None, ctx=None):
     if K is None:
         K = Bh.T @ solve_gare_pair(Eh, Ah, Bh, Ch, ctx=ctx)[0] @ Eh
     Dn = np.vstack([np.zeros((q, m)), np.eye(m)])
-    H = freq_response(Eh, Ah - Bh @ K, Bh, np.vstack([Ch, -K]), w, D=Dn, chunk=chunk, ctx=ctx)
-    Hr = freq_response(rom.Er, rom.Ar - rom.Br @ rom.Kr, rom.Br, np.vstack([rom.Cr, -rom.Kr]), w, D=Dn, chunk=chunk, ctx=ctx)
+    H = freq_response(Eh, Ah - Bh @ K, Bh, np.vstack([Ch, -K]), w, D=Dn, chunk=chunk, ctx=ctx, method=method)
+    Hr = freq_response(rom.Er, rom.Ar - rom.Br @ rom.Kr, rom.Br, np.vstack([rom.Cr, -rom.Kr]), w, D=Dn, chunk=chunk, ctx=ctx, method=method)
     err = float(np.linalg.svd(H - Hr, compute_uv=False)[:, 0].max())
     mu = np.asarray(rom.mu, dtype=float)[rom.order:]
     return err, 2.0 * float(np.sum((mu / np.sqrt(1.0 + mu * mu))[::-1]))

@@ -16,7 +16,9 @@
 #include "dense_sign.hpp"
 #include "dense_sign_lr.hpp"
 #include "engine.hpp"
+#include "dense_cgj.hpp"
 #include "freq_response.hpp"
+#include "transfer_eval.hpp"
 #include "gemm_probe_check.hpp"
 #include "hostla.hpp"
 #include "jacobi_batch.hpp"
@@ -84,7 +86,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 114; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 115; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -95,6 +97,8 @@ int dre_version(void) { return 114; }  // 101: dense path (dre_dense_gale_solve,
                                         // 112: frequency response batched by frequency (dre_freq_response, dre_freq_response_batched)
                                         // 113: LQG balanced truncation from one Hamiltonian sign iteration (dre_dense_gare_solve_pair, dre_lqg_balance)
                                         // 114: dre_sym_eig_probe (test surface of the Householder + QL eigensolver); sym_eig refuses a non-finite input
+                                        // 115: complex Gauss-Jordan inversion and the transfer function at complex points (dre_dense_invert_complex_batched,
+                                        //      dre_transfer_eval, dre_transfer_eval_batched)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1545,6 +1549,76 @@ int dre_freq_response_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E,
 int dre_freq_response(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* omega,
                       int chunk, double* H_re, double* H_im, int32_t* status, int64_t* info) {
     return dre_freq_response_batched(ctx, 1, &E, &A, &B, &C, K, omega, chunk, H_re, H_im, status, info);
+}
+
+// ---- complex inversion and the transfer function at complex points (dense_cgj.hip, transfer_eval.hip) -----------------------------------
+int dre_dense_invert_complex_batched(dre_ctx* ctx, int batch, dre_dense* const* Are, dre_dense* const* Aim, int32_t* piv, double* logabsdet,
+                                     int32_t* status) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        const char* who = "dre_dense_invert_complex_batched";
+        DRE_REQUIRE(Are && Aim && status && batch >= 1 && Are[0], std::string(who) + ": null argument or batch < 1");
+        const int n = Are[0]->m.rows;
+        check_batch_order(batch, n, who);
+        check_members(batch, Are, n, n, who, "Are");
+        check_members(batch, Aim, n, n, who, "Aim");
+        const int nb = cgj_batch_nb(n);
+        require_memory(c, (size_t)batch * ((size_t)2 * n * n + (size_t)6 * n * nb + n));
+        // member b: [Zr | Zi] at b * 2 n^2
+        Mat S(c, n, 2 * n * batch);
+        for (int b = 0; b < batch; ++b) {
+            Mat vr = S.colsview(2 * b * n, n), vi = S.colsview((2 * b + 1) * n, n);
+            copy_mat(c, Are[b]->m, vr);
+            copy_mat(c, Aim[b]->m, vi);
+        }
+        Mat Pt(c, n, 2 * nb * batch), Wt(c, 2 * nb, 2 * n * batch);
+        DevArr<int> pv(c, (size_t)n * batch);
+        DevArr<BatchCtl> ctl(c, batch);
+        DRE_HIP(hipMemsetAsync(ctl.p, 0, sizeof(BatchCtl) * batch, c->stream));
+        cgj_invert_batched(c, batch, n, S.p, pv.p, ctl.p, BM_GJ, Pt.p, Wt.p);
+        std::vector<BatchCtl> h((size_t)batch);
+        DRE_HIP(hipMemcpyAsync(h.data(), ctl.p, sizeof(BatchCtl) * batch, hipMemcpyDeviceToHost, c->stream));
+        if (piv) DRE_HIP(hipMemcpyAsync(piv, pv.p, (size_t)n * batch * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        std::vector<BatchMemberStatus> st((size_t)batch);
+        for (int b = 0; b < batch; ++b) {
+            if (h[(size_t)b].s.gj.singular) {
+                st[(size_t)b].code = ERR_SINGULAR;
+                st[(size_t)b].msg = std::string(who) + ", member " + std::to_string(b) + ": singular matrix (exactly zero or non-finite pivot)";
+                continue;
+            }
+            Mat vr = S.colsview(2 * b * n, n), vi = S.colsview((2 * b + 1) * n, n);
+            copy_mat(c, vr, Are[b]->m);
+            copy_mat(c, vi, Aim[b]->m);
+            if (logabsdet) logabsdet[b] = h[(size_t)b].s.gj.logdet;
+        }
+        c->sync();
+        report_members(ctx, st, status);
+    });
+}
+int dre_transfer_eval_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                              const dre_dense* const* C, int K, const double* s_re, const double* s_im, int chunk, double* H_re, double* H_im,
+                              int32_t* status, int64_t* info) {
+    return guarded(ctx, [&] {
+        const char* who = "dre_transfer_eval_batched";
+        DRE_REQUIRE(nsys >= 1, std::string(who) + ": no systems (nsys < 1)");
+        DRE_REQUIRE(K >= 1, std::string(who) + ": at least one point is needed (K >= 1)");
+        DRE_REQUIRE(E && A && B && C && s_re && s_im && H_re && H_im && status, std::string(who) + ": null argument");
+        std::vector<FreqSystem> sys((size_t)nsys);
+        for (int s = 0; s < nsys; ++s) {
+            DRE_REQUIRE(E[s] && A[s] && B[s] && C[s], std::string(who) + ": null operand in system " + std::to_string(s));
+            sys[(size_t)s] = FreqSystem{E[s]->m, A[s]->m, B[s]->m, C[s]->m};
+        }
+        const FreqResponse r = transfer_eval(&ctx->c, sys, std::vector<double>(s_re, s_re + K), std::vector<double>(s_im, s_im + K), chunk);
+        std::memcpy(H_re, r.re.data(), r.re.size() * sizeof(double));
+        std::memcpy(H_im, r.im.data(), r.im.size() * sizeof(double));
+        if (info) { info[0] = r.chunk; info[1] = r.chunks; }
+        report_members(ctx, r.status, status);
+    });
+}
+int dre_transfer_eval(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* s_re,
+                      const double* s_im, int chunk, double* H_re, double* H_im, int32_t* status, int64_t* info) {
+    return dre_transfer_eval_batched(ctx, 1, &E, &A, &B, &C, K, s_re, s_im, chunk, H_re, H_im, status, info);
 }
 
 int dre_dense_gale_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* F, const dre_dense* const* R,

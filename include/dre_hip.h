@@ -641,6 +641,31 @@ int dre_freq_response_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E,
                               const dre_dense* const* C, int K, const double* omega, int chunk, double* H_re /* q*m*K*nsys */,
                               double* H_im /* q*m*K*nsys */, int32_t* status /* K*nsys */, int64_t* info /* 2, may be NULL */);
 
+/* ---- complex inversion and the transfer function at complex points (dre_version >= 115) --------------------------------------------------
+ * A complex matrix is two dre_dense planes of one shape, its real and its imaginary part.  The complex Gauss-Jordan inversion runs on the
+ * register panel in both planes (n <= 4096), pivots by |re| + |im| and does its trailing update as one real product per panel:
+ * 8 n^3 real flops, 2 n^2 doubles per member.
+ * Are[b] + i Aim[b] <- its inverse, in place on both planes; piv: batch * n interchanges (or NULL); logabsdet: batch values log|det| (or
+ * NULL; the phase of the determinant is not returned).  The conventions of dre_dense_invert_batched: a singular member (exactly zero or
+ * non-finite pivot) gets DRE_ERR_SINGULAR in status[b] and its planes are left as they came; batch < 1, mismatched shapes and n > 4096 are the
+ * call's DRE_ERR_INVALID before any launch. */
+int dre_dense_invert_complex_batched(dre_ctx* ctx, int batch, dre_dense* const* Are, dre_dense* const* Aim, int32_t* piv /* batch*n */,
+                                     double* logabsdet /* batch */, int32_t* status /* batch */);
+/* H(s_k) = C (s_k E - A)^-1 B at K complex points s_k = s_re[k] + i s_im[k], the point on the member axis: per member the planes of s E - A
+ * are assembled, inverted in place with the complex register panel (n <= 4096) and multiplied out, with one refinement step whose residual is
+ * formed from E and A.  8 n^3 flops per point, half of dre_freq_response's, which it reproduces at s = i w to rounding.  Arguments, layouts
+ * (H_re, H_im: q*m*K doubles, member k at k*q*m, q x m column-major), status, chunk, info and error rules are those of dre_freq_response, with
+ * the two point arrays in place of omega: DRE_ERR_SINGULAR in status[k] for a point on a pole (or a NaN in the system), its H is NaN; the
+ * call's own DRE_ERR_INVALID, before any launch: a NULL argument, K < 1, a non-finite s_re or s_im, mismatched shapes, n > 4096, chunk < 0
+ * or > 65535; DRE_ERR_ALLOC, before any launch: the chunk does not fit. */
+int dre_transfer_eval(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* s_re,
+                      const double* s_im, int chunk, double* H_re /* q*m*K */, double* H_im /* q*m*K */, int32_t* status /* K */,
+                      int64_t* info /* 2, may be NULL */);
+/* the same for nsys systems of one (n, m, q) at the same K points: member s*K + k is system s at s_k */
+int dre_transfer_eval_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
+                              const dre_dense* const* C, int K, const double* s_re, const double* s_im, int chunk, double* H_re /* q*m*K*nsys */,
+                              double* H_im /* q*m*K*nsys */, int32_t* status /* K*nsys */, int64_t* info /* 2, may be NULL */);
+
 /* ---- test and diagnostic surface: the internal GEMM entry points one by one (dre_version >= 108) ----------------------------------------
  * dre_gemm_probe calls ONE entry point of the f64 MFMA GEMM family with arguments a public caller cannot form: operands that are views into
  * larger buffers, member masks, device-side counts, the `done` flag of an ADI control block.  It has no wrapper beyond the ctypes prototype
