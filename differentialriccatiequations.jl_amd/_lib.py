@@ -73,6 +73,19 @@ class GemmProbeOptionsC(C.Structure):
     ]
 
 
+class AdiChainProbeArgsC(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("k", C.c_int32),
+        ("nstack", C.c_int32), ("ncyc", C.c_int32), ("g", C.c_int32), ("nit", C.c_int32),
+        ("base_it", C.c_int32), ("maxiters", C.c_int32), ("tdiag", C.c_int32), ("mode", C.c_int32),
+        ("nt", C.c_int32), ("ld", C.c_int32),
+        ("alpha", C.c_double), ("abstol", C.c_double),
+        ("stacks", C.c_void_p), ("wks", C.c_void_p), ("wks_null", C.c_void_p), ("cycle", C.c_void_p), ("mu", C.c_void_p), ("R0", C.c_void_p), ("T", C.c_void_p),
+        ("V", C.c_void_p), ("R", C.c_void_p), ("packs", C.c_void_p), ("Rp", C.c_void_p), ("G", C.c_void_p),
+        ("state_i", C.c_void_p), ("state_d", C.c_void_p),
+    ]
+
+
 _vp = C.c_void_p
 _pvp = C.POINTER(C.c_void_p)
 _pd = C.POINTER(C.c_double)
@@ -114,6 +127,7 @@ PROTOTYPES = {
     "dre_orthf": (C.c_int, [_vp, _vp, _pvp, _pvp]),
     "dre_sym_eig": (C.c_int, [_vp, _vp, C.c_double, _pvp, _pvp]),
     "dre_sym_eig_probe": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, _pi32, C.c_int, _pi64, _pd] + [_pvp] * 7),
+    "dre_adi_chain_probe": (C.c_int, [_vp, C.POINTER(AdiChainProbeArgsC)]),
     "dre_sym_eig_jacobi": (C.c_int, [_vp, _vp, C.c_double, _pvp, _pvp, _pi64]),
     "dre_shift_factor": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_double, _pvp]),
     "dre_shift_solve": (C.c_int, [_vp, _vp, _vp, _pvp, _pvp]),

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <limits>
 
 #include "balance.hpp"
 #include "comm.hpp"
@@ -86,7 +87,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 115; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 116; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -99,6 +100,7 @@ int dre_version(void) { return 115; }  // 101: dense path (dre_dense_gale_solve,
                                         // 114: dre_sym_eig_probe (test surface of the Householder + QL eigensolver); sym_eig refuses a non-finite input
                                         // 115: complex Gauss-Jordan inversion and the transfer function at complex points (dre_dense_invert_complex_batched,
                                         //      dre_transfer_eval, dre_transfer_eval_batched)
+                                        // 116: dre_adi_chain_probe (test surface of the dense-inverse ADI chain)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -732,6 +734,173 @@ int dre_sym_eig_probe(dre_ctx* ctx, const dre_dense* S, double tolfac, int want_
         dre_dense* res[7] = {od, oe, ot, oV, ow, oZ, oB};
         for (int k = 0; k < 7; ++k) if (outs[k]) *outs[k] = res[k];
         for (auto& m : made) m.release();
+    });
+}
+// ---- dre_adi_chain_probe: the dense-inverse ADI chain on caller-supplied operands (test and diagnostic surface) ----------------------------
+// Every launch goes through adi_fast_build, adi_fast_pack_r, adi_fast_iter, adi_group_pack or adi_group_iter; the loops are those of adi_advance
+// (engine.hip, fast branch) and of the dense-X time loop (gdre.hip, group branch).
+int dre_adi_chain_probe(dre_ctx* ctx, const dre_adi_chain_probe_args* args) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(args, "dre_adi_chain_probe: null argument");
+        const dre_adi_chain_probe_args& p = *args;
+        const bool group = p.kind == DRE_ADI_PROBE_GROUP, build_only = p.kind == DRE_ADI_PROBE_BUILD;
+        DRE_REQUIRE(p.kind == DRE_ADI_PROBE_FAST || group || build_only, "dre_adi_chain_probe: unknown kind");
+        const int n = p.n, k = p.k, m = group ? 0 : p.m, nit = p.nit, g = p.g;
+        DRE_REQUIRE(n >= 1 && n <= 8192, "dre_adi_chain_probe: n must lie in 1 .. 8192");
+        DRE_REQUIRE(p.nstack >= 1 && p.nstack <= 4096 && p.stacks, "dre_adi_chain_probe: stacks missing");
+        DRE_REQUIRE(m >= 0 && m <= 4096 && (m == 0 || p.wks), "dre_adi_chain_probe: m must not be negative and needs wks");
+        int mode = 0, nt = 1;
+        if (!build_only) {
+            DRE_REQUIRE(k >= 1, "dre_adi_chain_probe: k must be at least 1");
+            DRE_REQUIRE(k <= (group ? ADI_GROUP_MAX_K : ADI_FAST_MAX_K), "dre_adi_chain_probe: residual too wide");
+            DRE_REQUIRE(nit >= 1 && nit <= 480, "dre_adi_chain_probe: nit must lie in 1 .. 480 (ring of the norm history)");
+            DRE_REQUIRE(p.ncyc >= 1 && p.mu && p.R0 && p.T, "dre_adi_chain_probe: cycle, R0 or T missing");
+            DRE_REQUIRE(p.ld >= n + 2, "dre_adi_chain_probe: ld must be at least n + 2");
+            DRE_REQUIRE(p.base_it >= 0 && p.base_it <= (1 << 30), "dre_adi_chain_probe: base_it");
+            if (group) {
+                DRE_REQUIRE(g >= 2 && g <= ADI_GROUP_MAX_G, "dre_adi_chain_probe: g must lie in 2 .. 6");
+                DRE_REQUIRE(nit % g == 0, "dre_adi_chain_probe: nit must be a multiple of g");
+                DRE_REQUIRE(p.ncyc % g == 0 && p.nstack == p.ncyc / g, "dre_adi_chain_probe: one group stack per start position of the cycle (ncyc / g)");
+                const int ct = (k + 15) / 16;
+                DRE_REQUIRE(g * ct * ((ct + 3) / 4) <= ADI_FAST_NWS - 1, "dre_adi_chain_probe: norm meeting point too small");
+            } else {
+                DRE_REQUIRE(p.cycle, "dre_adi_chain_probe: cycle missing");
+                for (int i = 0; i < p.ncyc; ++i) DRE_REQUIRE(p.cycle[i] >= 0 && p.cycle[i] < p.nstack, "dre_adi_chain_probe: entry of cycle outside [0, nstack)");
+                DRE_REQUIRE((p.mode == -1) == (p.nt == -1), "dre_adi_chain_probe: mode and nt are picked together");
+                if (p.mode == -1) adi_fast_pick(n, k, &mode, &nt);
+                else {
+                    DRE_REQUIRE(p.mode == 0 || p.mode == 1, "dre_adi_chain_probe: mode must be 0 or 1");
+                    DRE_REQUIRE(p.nt == 1 || p.nt == 2 || p.nt == 4, "dre_adi_chain_probe: nt must be 1, 2 or 4");
+                    mode = p.mode; nt = p.nt;
+                }
+            }
+        }
+        // (the arguments are judged without a context, so that the refusals can be tested on a machine without a device)
+        DRE_REQUIRE(ctx, "dre_adi_chain_probe: arguments accepted, context missing");
+        Ctx* c = &ctx->c;
+        const int nstrip = adi_fast_nstrip(n), kst = adi_fast_kst(n);
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        auto up = [&](const double* h, size_t cnt) {
+            DevArr<double> d(c, std::max<size_t>(cnt, 1));
+            if (cnt) DRE_HIP(hipMemcpyAsync(d.p, h, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            return d;
+        };
+        auto nan_arr = [&](size_t cnt) {          // (all bits set is a NaN)
+            DevArr<double> d(c, std::max<size_t>(cnt, 1));
+            DRE_HIP(hipMemsetAsync(d.p, 0xFF, d.n * sizeof(double), c->stream));
+            return d;
+        };
+        auto down = [&](double* h, const double* d, size_t cnt) { if (h && cnt) DRE_HIP(hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream)); };
+        // ---- the packed stacks ----
+        const int srows = group ? 2 * g * n : 2 * n + m;
+        const size_t pkd = group ? (size_t)2 * g * nstrip * kst * 64 : adi_fast_pack_doubles(n);
+        DevArr<double> stacks_d = up(p.stacks, (size_t)p.nstack * srows * n);
+        DevArr<double> wks_d = up(p.wks, m ? (size_t)p.nstack * 2 * n * m : 0);
+        DevArr<double> packs_d = nan_arr((size_t)p.nstack * pkd);
+        if (group) {
+            for (int s = 0; s < p.nstack; ++s) adi_group_pack(c, n, 2 * g, stacks_d.p + (size_t)s * srows * n, srows, packs_d.p + (size_t)s * pkd);
+        } else {
+            std::vector<const double*> stacks, wks; std::vector<double*> outs;
+            for (int s = 0; s < p.nstack; ++s) {
+                stacks.push_back(stacks_d.p + (size_t)s * srows * n);
+                wks.push_back(m && !(p.wks_null && p.wks_null[s]) ? wks_d.p + (size_t)s * 2 * n * m : nullptr);
+                outs.push_back(packs_d.p + (size_t)s * pkd);
+            }
+            adi_fast_build(c, n, m, stacks, srows, wks, 2 * n, outs);
+        }
+        down(p.packs, packs_d.p, (size_t)p.nstack * pkd);
+        if (build_only) { c->sync(); return; }
+        // ---- control block, meeting point, buffers ----
+        AdiState hst;
+        std::memset(&hst, 0, sizeof(hst));
+        hst.iters = p.base_it; hst.maxiters = p.maxiters; hst.abstol = p.abstol; hst.res_norm = nan;
+        for (double& v : hst.norms) v = nan;
+        DevArr<AdiState> st(c, 1);
+        DRE_HIP(hipMemcpyAsync(st.p, &hst, sizeof(AdiState), hipMemcpyHostToDevice, c->stream));
+        DevArr<double> nws(c, ADI_FAST_NWS);
+        DRE_HIP(hipMemsetAsync(nws.p, 0, ADI_FAST_NWS * sizeof(double), c->stream));
+        DevArr<double> R0 = up(p.R0, (size_t)n * k), Tm = up(p.T, (size_t)k * k);
+        const int ld = p.ld;
+        const size_t ring = (size_t)ld * k * (nit + 1);
+        DevArr<double> Vall = nan_arr(ring), Rring = nan_arr(ring);
+        const bool use_pk = group || mode == 0;
+        const size_t rpd = adi_fast_rpack_doubles(n, k);
+        DevArr<double> Rp0 = nan_arr(use_pk ? rpd : 1);                          // exactly one slot, like the time loop's
+        DevArr<double> Rpk = nan_arr(use_pk ? rpd * (size_t)(nit + 1) : 1);
+        DevArr<double> Gm = nan_arr((size_t)k * k * 2 * (group ? g : 1));
+        if (use_pk) adi_fast_pack_r(c, n, k, R0.p, n, Rp0.p, st.p);
+        const int base_it = p.base_it;
+        if (group) {
+            const int NG = nit / g;
+            AdiGroupArgs ga;
+            std::memset(&ga, 0, sizeof(ga));
+            ga.n = n; ga.k = k; ga.nstrip = nstrip; ga.kst = kst; ga.g = g;
+            ga.ldr = ld; ga.rpd = rpd; ga.ldv = ld;
+            ga.T = Tm.p; ga.ldt = k; ga.alpha = p.alpha; ga.st = st.p; ga.nws = nws.p;
+            for (int L = 0; L <= NG + 1; ++L) {
+                ga.do_strips = L < NG ? 1 : 0;
+                if (L < NG) {
+                    ga.Gpack = packs_d.p + (size_t)(((L * g) % p.ncyc) / g) * pkd;
+                    ga.Rpc = L == 0 ? Rp0.p : Rpk.p + (size_t)(L * g) * rpd;
+                    ga.Rring = Rring.p + (size_t)(L * g) * k * ld;
+                    ga.Rpk = Rpk.p + (size_t)(L * g + 1) * rpd;
+                    ga.V = Vall.p + (size_t)(L * g * k) * ld;
+                }
+                // Gram matrices of the residuals launch L - 1 produced; norms + decisions for those of launch L - 2
+                ga.n_prev = (L >= 1 && L <= NG) ? g : 0;
+                ga.Rp_prev = ga.n_prev ? Rpk.p + (size_t)((L - 1) * g + 1) * rpd : nullptr;
+                ga.G_prev = Gm.p + (size_t)(L & 1) * g * k * k;
+                ga.n_prev2 = L >= 2 ? g : 0;
+                ga.G_prev2 = Gm.p + (size_t)((L - 1) & 1) * g * k * k;
+                ga.it0_prev2 = base_it + (L - 2) * g + 1;
+                adi_group_iter(c, ga);
+            }
+        } else {
+            AdiFastArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.n = n; a.k = k; a.nstrip = nstrip; a.kst = kst; a.mode = mode; a.nt = nt;
+            a.T = Tm.p; a.ldt = k; a.tdiag = p.tdiag ? 1 : 0; a.alpha = p.alpha; a.st = st.p; a.nws = nws.p;
+            for (int j = 1; j <= nit; ++j) {
+                const int pos = (j - 1) % p.ncyc;
+                a.Apack = packs_d.p + (size_t)p.cycle[pos] * pkd;
+                if (j == 1) { a.Rcur = R0.p; a.ldr = n; } else { a.Rcur = Rring.p + (size_t)(j - 2) * k * ld; a.ldr = ld; }
+                a.Rnext = Rring.p + (size_t)(j - 1) * k * ld; a.ldr_next = ld;
+                a.Rpc = use_pk ? (j == 1 ? Rp0.p : Rpk.p + (size_t)(j - 1) * rpd) : nullptr;
+                a.Rpn = use_pk ? Rpk.p + (size_t)j * rpd : nullptr;
+                a.V = Vall.p + (size_t)(j - 1) * k * ld; a.ldv = ld;
+                a.two_mu = 2.0 * p.mu[pos];
+                const int it = base_it + j;                                 // shifts consumed after this iteration
+                a.G_prev = j >= 2 ? Gm.p + (size_t)((it - 1) & 1) * k * k : nullptr;
+                a.G_prev2 = j >= 3 ? Gm.p + (size_t)((it - 2) & 1) * k * k : nullptr;
+                a.it_prev2 = it - 2; a.do_strips = 1;
+                adi_fast_iter(c, a);
+            }
+            {   // drain the norm pipeline: Gram matrix of the last residual, decisions for the last two iterations
+                const int it = base_it + nit;
+                a.do_strips = 0; a.Apack = nullptr; a.Rnext = nullptr; a.V = nullptr;
+                a.Rpc = use_pk ? Rpk.p + (size_t)nit * rpd : nullptr; a.Rpn = nullptr;
+                a.Rcur = Rring.p + (size_t)(nit - 1) * k * ld; a.ldr = ld;
+                a.G_prev = Gm.p + (size_t)(it & 1) * k * k;
+                a.G_prev2 = nit >= 2 ? Gm.p + (size_t)((it - 1) & 1) * k * k : nullptr;
+                a.it_prev2 = it - 1;
+                adi_fast_iter(c, a);
+                a.G_prev = nullptr;
+                a.G_prev2 = Gm.p + (size_t)(it & 1) * k * k;
+                a.it_prev2 = it;
+                adi_fast_iter(c, a);
+            }
+        }
+        DRE_HIP(hipMemcpyAsync(&hst, st.p, sizeof(AdiState), hipMemcpyDeviceToHost, c->stream));
+        down(p.V, Vall.p, ring);
+        down(p.R, Rring.p, ring);
+        down(p.G, Gm.p, (size_t)k * k * 2 * (group ? g : 1));
+        if (p.Rp) {
+            if (use_pk) { down(p.Rp, Rp0.p, rpd); down(p.Rp + rpd, Rpk.p + rpd, rpd * (size_t)nit); }
+            else for (size_t i = 0; i < rpd * (size_t)(nit + 1); ++i) p.Rp[i] = nan;
+        }
+        c->sync();
+        if (p.state_i) { p.state_i[0] = hst.iters; p.state_i[1] = hst.done; p.state_i[2] = mode; p.state_i[3] = nt; }
+        if (p.state_d) { p.state_d[0] = hst.res_norm; p.state_d[1] = hst.abstol; std::memcpy(p.state_d + 2, hst.norms, sizeof(hst.norms)); }
     });
 }
 int dre_sym_eig_jacobi(dre_ctx* ctx, const dre_dense* S, double tol, dre_dense** values, dre_dense** vectors, int64_t* stats) {

@@ -1008,7 +1008,9 @@ __device__ __forceinline__ void adi_fast_tiles(const double* __restrict__ ap, co
     for (int j = 0; j < NT; ++j) {
         const int col = col0 + j * 16 + lr;
         cok[j] = col < k;
-        bp[j] = PACKED ? Rp + ((size_t)(col0 / 16 + j)) * 64 + (threadIdx.x & 63) : R + (size_t)(cok[j] ? col : 0) * ldr;
+        // (a masked-out tile past the last one loads the last tile instead: unclamped it would read the next K-step, and for the last K-step
+        // 512 bytes past the end of the packed slot)
+        bp[j] = PACKED ? Rp + (size_t)min(col0 / 16 + j, ((k + 15) >> 4) - 1) * 64 + (threadIdx.x & 63) : R + (size_t)(cok[j] ? col : 0) * ldr;
     }
     double a0[KB], a1[KB], b0[NT][KB], b1[NT][KB];
     auto load = [&](double (&av)[KB], double (&bv)[NT][KB], int tb) {

@@ -178,6 +178,44 @@ int dre_sym_eig(dre_ctx* ctx, const dre_dense* S, double tolfac, dre_dense** val
 int dre_sym_eig_probe(dre_ctx* ctx, const dre_dense* S, double tolfac, int want_eig, double abs_tol, int floor_mode, double deflate, const int32_t* ids,
                       int nids, int64_t* ii /* 3 */, double* snorm, dre_dense** d, dre_dense** e, dre_dense** tau, dre_dense** V, dre_dense** w,
                       dre_dense** Z, dre_dense** B);
+/* Test and diagnostic surface of the dense-inverse ADI chain (dre_version >= 116): the entry points adi_fast_build, adi_fast_pack_r, adi_fast_iter,
+ * adi_group_pack and adi_group_iter (csrc/dense.hip) on caller-supplied operands, driven by exactly the pipeline of the engine's fast branch and of
+ * the dense-X time loop's group branch (Gram matrix of iteration j riding on launch j + 1, norm and decision on launch j + 2, two flush launches).
+ * No kernel of its own.  Every array is HOST memory, column-major, without padding; every output array may be NULL.
+ * kind 0 (DRE_ADI_PROBE_FAST): build, pack R0, nit iterations, two flushes.  kind 2 (DRE_ADI_PROBE_BUILD): build only.
+ *   stacks: nstack matrices [N; E'N; U'N] of (2n + m) x n;  wks: nstack matrices of 2n x m (NULL with m = 0);  wks_null (nstack flags or NULL):
+ *   1 = that shift is built WITHOUT a correction (null pointer: the whole build then takes the scalar kernel);  packs: nstack packed effective
+ *   stacks of 2 nstrip kst 64 doubles, nstrip = ceil(n / 16), kst = ceil(n / 4): entry (row 16 s + (lane & 15), column 4 t + (lane >> 4)) of half h
+ *   (0: top, 1: bottom) at ((h nstrip + s) kst + t) 64 + lane, zero padded.
+ * kind 1 (DRE_ADI_PROBE_GROUP): pack, then launches L = 0 .. nit / g + 1 of g iterations each.  stacks: nstack = ncyc / g matrices
+ *   [Om_0 .. Om_(g-1); Pi_1 .. Pi_g] of (2 g n) x n, one per start position of the cycle;  packs: nstack x 2 g nstrip kst 64 doubles (same order,
+ *   block b in the place of half h).  m, wks, tdiag, mode and nt are not read.
+ * cycle (ncyc entries of [0, nstack), kinds 0 and 2 only) names the stack of every position of the cycle, mu (ncyc) its shift; iteration j
+ * (1-based) uses position (j - 1) mod ncyc.  R0: n x k;  T: k x k (tdiag = 1 promises that it is diagonal);  the control block starts with
+ * iters = base_it, done = 0, the given abstol and maxiters, and NaN in every norm.
+ * mode / nt: -1 = adi_fast_pick (both must then be -1), otherwise mode 0 (K-split tiles) or 1 (LDS-staged strips) and nt 1, 2 or 4.
+ * Outputs.  V, R: ld x k (nit + 1), prefilled with NaN: V_j / R_j (after iteration j = 1 .. nit) in rows [0, n) of columns [(j - 1) k, j k);  rows
+ * from n on and the last k columns are never written.  Rp: nit + 1 slots of 4 nstrip ceil(k / 16) 64 doubles, prefilled with NaN: slot 0 the packed
+ * R0, slot j the packed R_j as the launch that produced it left it — element (row 4 t + (lane >> 4), column 16 c + (lane & 15)) at
+ * (t ceil(k / 16) + c) 64 + lane, zero padded; all NaN with mode 1, which does not use it.  The first packed residual lives in an allocation of exactly
+ * one slot, the others in one of nit + 1 slots whose first is unused, as in the time loop.  G: the Gram matrices R_j' R_j still held when the chain
+ * ends, prefilled with NaN — kinds 0: 2 slots of k x k, slot (j & 1);  kind 1: 2 g slots, slot (L & 1) g + i for residual i of launch L - 1.
+ * state_i (4): iters, done, mode used, nt used;  state_d (514): res_norm, abstol, norms[512] (index = shifts consumed & 511).
+ * DRE_ERR_INVALID before any launch: n < 1, k < 1, k > 512 (kind 1: k > 256), m < 0, nit < 1 or > 480 (kind 1: not a multiple of g), g outside
+ * 2 .. 6, ncyc not a multiple of g or nstack != ncyc / g, g ceil(k / 16) ceil(ceil(k / 16) / 4) > 1031, mode outside {0, 1}, nt outside {1, 2, 4},
+ * ld < n + 2, an entry of cycle outside [0, nstack), base_it < 0, a missing input. */
+enum { DRE_ADI_PROBE_FAST = 0, DRE_ADI_PROBE_GROUP = 1, DRE_ADI_PROBE_BUILD = 2 };
+typedef struct dre_adi_chain_probe_args {
+    int32_t kind, n, m, k;
+    int32_t nstack, ncyc, g, nit;
+    int32_t base_it, maxiters, tdiag, mode;
+    int32_t nt, ld;
+    double alpha, abstol;
+    const double* stacks; const double* wks; const int32_t* wks_null; const int32_t* cycle; const double* mu; const double* R0; const double* T;
+    double* V; double* R; double* packs; double* Rp; double* G;
+    int32_t* state_i; double* state_d;
+} dre_adi_chain_probe_args;
+int dre_adi_chain_probe(dre_ctx* ctx, const dre_adi_chain_probe_args* args);
 /* eigen(Symmetric(S)) by two-sided cyclic block Jacobi on the whole device (blocks of 16, round-robin ordering, both products of the update on
  * v_mfma_f64_16x16x4_f64): all q eigenpairs, values ascending, S untouched (full symmetric storage; indefinite, rank-deficient and clustered
  * spectra are fine).  Converged when off(A) <= tol ||A||_F; tol <= 0: q eps.  stats (may be NULL): [0] block sweeps, [1] rounds.
