@@ -1695,24 +1695,31 @@ int dre_dense_invert_batched(dre_ctx* ctx, int batch, dre_dense* const* A, int32
     });
 }
 // ---- frequency response (freq_response.hip) --------------------------------------------------------------------------------------------
+// the two sweeps' entry points: collect the systems, run `sweep` (freq_response or transfer_eval on them), copy H, info and the members' outcomes
+// out.  noun: what the K points are called in the caller's messages
+static void sweep_entry(dre_ctx* ctx, const char* who, const char* noun, bool args_ok, int nsys, const dre_dense* const* E, const dre_dense* const* A,
+                        const dre_dense* const* B, const dre_dense* const* C, int K, double* H_re, double* H_im, int32_t* status, int64_t* info,
+                        const std::function<FreqResponse(const std::vector<FreqSystem>&)>& sweep) {
+    DRE_REQUIRE(nsys >= 1, std::string(who) + ": no systems (nsys < 1)");
+    DRE_REQUIRE(K >= 1, std::string(who) + ": at least one " + noun + " is needed (K >= 1)");
+    DRE_REQUIRE(E && A && B && C && args_ok && H_re && H_im && status, std::string(who) + ": null argument");
+    std::vector<FreqSystem> sys((size_t)nsys);
+    for (int s = 0; s < nsys; ++s) {
+        DRE_REQUIRE(E[s] && A[s] && B[s] && C[s], std::string(who) + ": null operand in system " + std::to_string(s));
+        sys[(size_t)s] = FreqSystem{E[s]->m, A[s]->m, B[s]->m, C[s]->m};
+    }
+    const FreqResponse r = sweep(sys);
+    std::memcpy(H_re, r.re.data(), r.re.size() * sizeof(double));
+    std::memcpy(H_im, r.im.data(), r.im.size() * sizeof(double));
+    if (info) { info[0] = r.chunk; info[1] = r.chunks; }
+    report_members(ctx, r.status, status);
+}
 int dre_freq_response_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E, const dre_dense* const* A, const dre_dense* const* B,
                               const dre_dense* const* C, int K, const double* omega, int chunk, double* H_re, double* H_im, int32_t* status,
                               int64_t* info) {
     return guarded(ctx, [&] {
-        const char* who = "dre_freq_response_batched";
-        DRE_REQUIRE(nsys >= 1, std::string(who) + ": no systems (nsys < 1)");
-        DRE_REQUIRE(K >= 1, std::string(who) + ": at least one frequency is needed (K >= 1)");
-        DRE_REQUIRE(E && A && B && C && omega && H_re && H_im && status, std::string(who) + ": null argument");
-        std::vector<FreqSystem> sys((size_t)nsys);
-        for (int s = 0; s < nsys; ++s) {
-            DRE_REQUIRE(E[s] && A[s] && B[s] && C[s], std::string(who) + ": null operand in system " + std::to_string(s));
-            sys[(size_t)s] = FreqSystem{E[s]->m, A[s]->m, B[s]->m, C[s]->m};
-        }
-        const FreqResponse r = freq_response(&ctx->c, sys, std::vector<double>(omega, omega + K), chunk);
-        std::memcpy(H_re, r.re.data(), r.re.size() * sizeof(double));
-        std::memcpy(H_im, r.im.data(), r.im.size() * sizeof(double));
-        if (info) { info[0] = r.chunk; info[1] = r.chunks; }
-        report_members(ctx, r.status, status);
+        sweep_entry(ctx, "dre_freq_response_batched", "frequency", omega != nullptr, nsys, E, A, B, C, K, H_re, H_im, status, info,
+                    [&](const std::vector<FreqSystem>& sys) { return freq_response(&ctx->c, sys, std::vector<double>(omega, omega + K), chunk); });
     });
 }
 int dre_freq_response(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* omega,
@@ -1769,20 +1776,10 @@ int dre_transfer_eval_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E,
                               const dre_dense* const* C, int K, const double* s_re, const double* s_im, int chunk, double* H_re, double* H_im,
                               int32_t* status, int64_t* info) {
     return guarded(ctx, [&] {
-        const char* who = "dre_transfer_eval_batched";
-        DRE_REQUIRE(nsys >= 1, std::string(who) + ": no systems (nsys < 1)");
-        DRE_REQUIRE(K >= 1, std::string(who) + ": at least one point is needed (K >= 1)");
-        DRE_REQUIRE(E && A && B && C && s_re && s_im && H_re && H_im && status, std::string(who) + ": null argument");
-        std::vector<FreqSystem> sys((size_t)nsys);
-        for (int s = 0; s < nsys; ++s) {
-            DRE_REQUIRE(E[s] && A[s] && B[s] && C[s], std::string(who) + ": null operand in system " + std::to_string(s));
-            sys[(size_t)s] = FreqSystem{E[s]->m, A[s]->m, B[s]->m, C[s]->m};
-        }
-        const FreqResponse r = transfer_eval(&ctx->c, sys, std::vector<double>(s_re, s_re + K), std::vector<double>(s_im, s_im + K), chunk);
-        std::memcpy(H_re, r.re.data(), r.re.size() * sizeof(double));
-        std::memcpy(H_im, r.im.data(), r.im.size() * sizeof(double));
-        if (info) { info[0] = r.chunk; info[1] = r.chunks; }
-        report_members(ctx, r.status, status);
+        sweep_entry(ctx, "dre_transfer_eval_batched", "point", s_re && s_im, nsys, E, A, B, C, K, H_re, H_im, status, info,
+                    [&](const std::vector<FreqSystem>& sys) {
+                        return transfer_eval(&ctx->c, sys, std::vector<double>(s_re, s_re + K), std::vector<double>(s_im, s_im + K), chunk);
+                    });
     });
 }
 int dre_transfer_eval(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* s_re,
@@ -1955,62 +1952,50 @@ int dre_sign_info(const dre_sign* s, int64_t* n_iters) {
     *n_iters = s->s->iters();
     return DRE_OK;
 }
-int dre_sign_solve_lr(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
-                      dre_dense** L, dre_dense** D, int64_t* ii, double* dd) {
+// primal (F'XE + E'XF = -R / -G S G') and dual (F Y E' + E Y F' = ..., 109) solves on the same kept factorisation: one body per pair
+static int sign_solve_lr(dre_ctx* ctx, bool dual, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
+                         dre_dense** L, dre_dense** D, int64_t* ii, double* dd, const char* null_msg) {
     return guarded(ctx, [&] {
         Ctx* c = &ctx->c;
-        DRE_REQUIRE(s && G && S && L && D, "dre_sign_solve_lr: null argument");
+        DRE_REQUIRE(s && G && S && L && D, null_msg);
         auto Lo = std::make_unique<dre_dense>(), Do = std::make_unique<dre_dense>();
-        const SignLrStats st = s->s->solve_lr(G->m, S->m, rtol, max_width, max_refine, Lo->m, Do->m);
+        const SignLrStats st = dual ? s->s->solve_lr_t(G->m, S->m, rtol, max_width, max_refine, Lo->m, Do->m)
+                                    : s->s->solve_lr(G->m, S->m, rtol, max_width, max_refine, Lo->m, Do->m);
         c->sync();
         if (ii) { ii[0] = st.rank; ii[1] = st.peak_width; ii[2] = st.compressions; ii[3] = st.refinements; }
         if (dd) { dd[0] = st.res0; dd[1] = st.res; }
         *L = Lo.release(); *D = Do.release();
     });
 }
-int dre_sign_solve_dense(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo) {
+static int sign_solve_dense(dre_ctx* ctx, bool dual, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo,
+                            const char* null_msg) {
     return guarded(ctx, [&] {
         Ctx* c = &ctx->c;
-        DRE_REQUIRE(s && R && X && max_refine >= 0, "dre_sign_solve_dense: null argument or negative max_refine");
+        DRE_REQUIRE(s && R && X && max_refine >= 0, null_msg);
         const int n = s->s->n();
         auto out = std::make_unique<dre_dense>();
         out->m = Mat(c, n, n);
         s->s->set_max_refine(max_refine);
-        const SignStats st = s->s->solve(R->m, out->m);
+        const SignStats st = dual ? s->s->solve_t(R->m, out->m) : s->s->solve(R->m, out->m);
         c->sync();
         if (iinfo) { iinfo[0] = st.iters; iinfo[1] = st.refinements; }
         if (dinfo) { dinfo[0] = st.res0; dinfo[1] = st.res; }
         *X = out.release();
     });
 }
-// the dual equation F Y E' + E Y F' = -R / -G S G' on the same kept factorisation (109)
+int dre_sign_solve_lr(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
+                      dre_dense** L, dre_dense** D, int64_t* ii, double* dd) {
+    return sign_solve_lr(ctx, false, s, G, S, rtol, max_width, max_refine, L, D, ii, dd, "dre_sign_solve_lr: null argument");
+}
+int dre_sign_solve_dense(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo) {
+    return sign_solve_dense(ctx, false, s, R, max_refine, X, iinfo, dinfo, "dre_sign_solve_dense: null argument or negative max_refine");
+}
 int dre_sign_solve_dense_t(dre_ctx* ctx, dre_sign* s, const dre_dense* R, int max_refine, dre_dense** Y, int64_t* iinfo, double* dinfo) {
-    return guarded(ctx, [&] {
-        Ctx* c = &ctx->c;
-        DRE_REQUIRE(s && R && Y && max_refine >= 0, "dre_sign_solve_dense_t: null argument or negative max_refine");
-        const int n = s->s->n();
-        auto out = std::make_unique<dre_dense>();
-        out->m = Mat(c, n, n);
-        s->s->set_max_refine(max_refine);
-        const SignStats st = s->s->solve_t(R->m, out->m);
-        c->sync();
-        if (iinfo) { iinfo[0] = st.iters; iinfo[1] = st.refinements; }
-        if (dinfo) { dinfo[0] = st.res0; dinfo[1] = st.res; }
-        *Y = out.release();
-    });
+    return sign_solve_dense(ctx, true, s, R, max_refine, Y, iinfo, dinfo, "dre_sign_solve_dense_t: null argument or negative max_refine");
 }
 int dre_sign_solve_lr_t(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre_dense* S, double rtol, int max_width, int max_refine,
                         dre_dense** L, dre_dense** D, int64_t* ii, double* dd) {
-    return guarded(ctx, [&] {
-        Ctx* c = &ctx->c;
-        DRE_REQUIRE(s && G && S && L && D, "dre_sign_solve_lr_t: null argument");
-        auto Lo = std::make_unique<dre_dense>(), Do = std::make_unique<dre_dense>();
-        const SignLrStats st = s->s->solve_lr_t(G->m, S->m, rtol, max_width, max_refine, Lo->m, Do->m);
-        c->sync();
-        if (ii) { ii[0] = st.rank; ii[1] = st.peak_width; ii[2] = st.compressions; ii[3] = st.refinements; }
-        if (dd) { dd[0] = st.res0; dd[1] = st.res; }
-        *L = Lo.release(); *D = Do.release();
-    });
+    return sign_solve_lr(ctx, true, s, G, S, rtol, max_width, max_refine, L, D, ii, dd, "dre_sign_solve_lr_t: null argument");
 }
 int dre_sign_free(dre_ctx*, dre_sign* s) { delete s; return DRE_OK; }
 

@@ -173,26 +173,33 @@ double SignLyap::residual(const Mat& R, const Mat& X) {
     return read_back(c_, ctl_.p).res;
 }
 
-SignStats SignLyap::solve(const Mat& R, Mat& X) {
+// solve() and solve_t() (the dual equation, below): the two directions differ in their replay and residual; the primal's residual wants
+// ||R||_F^2 beforehand, the dual's takes it from its own pass
+SignStats SignLyap::solve_impl(bool dual, const Mat& R, Mat& X) {
     const int n = n_;
-    DRE_REQUIRE(R.rows == n && R.cols == n && R.ld == n && X.rows == n && X.cols == n && X.ld == n, "dense path: R and X must be n x n");
+    DRE_REQUIRE(R.rows == n && R.cols == n && R.ld == n && X.rows == n && X.cols == n && X.ld == n,
+                dual ? "dense path: R and Y must be n x n" : "dense path: R and X must be n x n");
     DRE_REQUIRE(iters_ > 0, "dense path: factor() first");
     ensure_dense_work();
-    frob2_device(c_, R, nrm_.p + 1);
+    if (!dual) frob2_device(c_, R, nrm_.p + 1);
+    auto rep = [&](const Mat& rhs, Mat& out) { if (dual) replay_t(rhs, out); else replay(rhs, out); };
+    auto res = [&] { return dual ? residual_t(R, X) : residual(R, X); };
     SignStats s;
     s.iters = iters_;
-    replay(R, X);
-    s.res0 = s.res = residual(R, X);
+    rep(R, X);
+    s.res0 = s.res = res();
     const double target = 100.0 * n * DBL_EPS;
     Mat dX = square(c_, n);
     while (s.res > target && s.refinements < max_refine_) {
-        replay(Res_, dX);
+        rep(Res_, dX);
         comb(c_, X, 1.0, X, 1.0, &dX);
-        s.res = residual(R, X);
+        s.res = res();
         ++s.refinements;
     }
     return s;
 }
+
+SignStats SignLyap::solve(const Mat& R, Mat& X) { return solve_impl(false, R, X); }
 
 // ---- the dual equation F Y E' + E Y F' = -R on the same kept sequence (host model: tests/_sign_dual_model.py) ------------------
 // Res = R + G + G' (G = F Y E'), with the partial sums of squares of Res AND of R from the same pass: the dual solve needs no norm launch of its
@@ -246,25 +253,7 @@ double SignLyap::residual_t(const Mat& R, const Mat& Y) {
     return read_back(c_, ctl_.p).res;
 }
 
-SignStats SignLyap::solve_t(const Mat& R, Mat& Y) {
-    const int n = n_;
-    DRE_REQUIRE(R.rows == n && R.cols == n && R.ld == n && Y.rows == n && Y.cols == n && Y.ld == n, "dense path: R and Y must be n x n");
-    DRE_REQUIRE(iters_ > 0, "dense path: factor() first");
-    ensure_dense_work();
-    SignStats s;
-    s.iters = iters_;
-    replay_t(R, Y);
-    s.res0 = s.res = residual_t(R, Y);
-    const double target = 100.0 * n * DBL_EPS;
-    Mat dY = square(c_, n);
-    while (s.res > target && s.refinements < max_refine_) {
-        replay_t(Res_, dY);
-        comb(c_, Y, 1.0, Y, 1.0, &dY);
-        s.res = residual_t(R, Y);
-        ++s.refinements;
-    }
-    return s;
-}
+SignStats SignLyap::solve_t(const Mat& R, Mat& Y) { return solve_impl(true, R, Y); }
 
 // ---- Rosenbrock drivers (dense_ros{1,2,3,4}.jl of the reference) ------------------------------------------------
 void ros2_stages(Ctx* ctx, SignLyap& lyap, const Ros2Ops& o, const Mat& X, const Mat& Kt, double tau, double gamma, Mat& K1, Mat& K2,

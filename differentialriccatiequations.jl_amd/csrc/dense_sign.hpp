@@ -54,6 +54,8 @@ class SignLyap {
     double residual(const Mat& R, const Mat& X);
     void replay_t(const Mat& R, Mat& Y);
     double residual_t(const Mat& R, const Mat& Y);
+    SignStats solve_impl(bool dual, const Mat& R, Mat& X);          // solve() / solve_t(): one refinement loop on replay[_t], residual[_t]
+    SignLrStats solve_lr_impl(bool dual, const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D);
     Ctx* c_;
     int n_, maxiters_, max_refine_, iters_ = 0;
     double tol_, logdetE_ = 0.0;

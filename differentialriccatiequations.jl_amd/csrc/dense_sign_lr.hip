@@ -3,7 +3,8 @@
 // on the (P_k, c_k) that SignLyap::factor() kept, with a rank-revealing compression (Householder QR, R D R', symmetric eigensolver,
 // |lambda| > rtol max|lambda|) whenever the width passes the cap and once at the end.  The products, the QR and the eigensolver are the
 // library's existing ones (gemm.hip, qr_band.hip); this file adds the three small kernels that assemble the block matrices.
-// NumPy restatement: tests/_factored_sign_model.py.   DESIGN.md §9.2.
+// solve_lr (this equation) and solve_lr_t (the dual one) are two directions of one body, solve_lr_impl.
+// NumPy restatement: tests/_factored_sign_model.py, tests/_sign_dual_model.py.   DESIGN.md §9.2.
 #include "dense_sign_lr.hpp"
 
 #include <algorithm>
@@ -152,29 +153,39 @@ struct Compressor {
 
 }  // namespace
 
-SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D) {
+// One body for both directions (tests/_factored_sign_model.py, tests/_sign_dual_model.py).  The primal equation
+// F'XE + E'XF = -G S G' replays  L_0 = G,  L_{k+1} = [L_k, P_k' L_k]  and leaves through  X = (E^-T L) (D / 2) (E^-T L)';  the dual equation
+// F Y E' + E Y F' = -G S G' replays  L_0 = E^-1 G,  L_{k+1} = [L_k, P_k L_k]  and  Y = L_inf (D_inf / 2) L_inf'.  `dual` therefore selects: the
+// transform with E^-1 at the entry instead of the exit, no transposed operand (P_k, and F and E in the residual factor [G, F L, E L]), the
+// memory of the entry and residual blocks on top of sign_lr_doubles, and the name in the messages.  Cap, compression, regrowth, refinement
+// and the statistics are common.
+SignLrStats SignLyap::solve_lr_impl(bool dual, const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D) {
     Ctx* c = c_;
     const int n = n_, r = G.cols;
-    DRE_REQUIRE(iters_ > 0, "solve_lr: factor() first");
-    DRE_REQUIRE(G.rows == n && S.rows == r && S.cols == r, "solve_lr: G must be n x r and S r x r");
-    DRE_REQUIRE(rtol > 0.0 && rtol < 1.0, "solve_lr: rtol must lie in (0, 1)");
+    const std::string who = dual ? "solve_lr_t: " : "solve_lr: ";
+    const bool tr = !dual;          // the primal's products with P_k, F and E are transposed
+    DRE_REQUIRE(iters_ > 0, who + "factor() first");
+    DRE_REQUIRE(G.rows == n && S.rows == r && S.cols == r, who + "G must be n x r and S r x r");
+    DRE_REQUIRE(rtol > 0.0 && rtol < 1.0, who + "rtol must lie in (0, 1)");
     DRE_REQUIRE(max_width >= 1 && max_width >= r && max_width <= SIGN_LR_MAX_WIDTH,
-                "solve_lr: max_width must be at least the width of G (and 1) and at most " + std::to_string(SIGN_LR_MAX_WIDTH));
-    DRE_REQUIRE(max_refine >= 0, "solve_lr: max_refine must be >= 0");
+                who + "max_width must be at least the width of G (and 1) and at most " + std::to_string(SIGN_LR_MAX_WIDTH));
+    DRE_REQUIRE(max_refine >= 0, who + "max_refine must be >= 0");
     SignLrStats st;
     st.iters = iters_;
     if (r == 0) { L = Mat(c, n, 0); D = Mat(c, 0, 0); return st; }
-    require_memory(c, sign_lr_doubles(n, max_width));
+    auto doubles = [&](int w) { return dual ? sign_lr_t_doubles(n, r, w) : sign_lr_doubles(n, w); };
+    require_memory(c, doubles(max_width));
 
-    // (L0, D0) -> (E^-T L_inf, D_inf / 2) with D diagonal; the factor lives in the left columns of one buffer and P_k' L_k is written into
-    // the columns to its right
+    // (L0, D0) -> (L_inf or E^-T L_inf, D_inf / 2) with D diagonal; the factor lives in the left columns of one buffer (the dual writes
+    // E^-1 L0 straight into them) and its product with P_k is written into the columns to its right
     auto replay_lr = [&](const Mat& L0, const Mat& D0, Mat& LX, Mat& DX) {
         int w = L0.cols;
         const int cap = std::max(max_width, w);
-        if (cap > max_width) require_memory(c, sign_lr_doubles(n, cap));
+        if (cap > max_width) require_memory(c, doubles(cap));
         Mat buf(c, n, 2 * cap);
         Mat left0 = buf.colsview(0, w);
-        copy_mat(c, L0, left0);
+        if (dual) gemm(c, false, false, 1.0, Einv_, L0, 0.0, left0, nullptr, "signlr_gemm");           // E^-1 L0
+        else copy_mat(c, L0, left0);
         Mat Dk = D0;
         Compressor comp(c);
         auto compress = [&]() -> std::vector<double> {
@@ -189,7 +200,7 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
         bool fresh = false;          // Dk == diag(vals) of a compression that nothing has touched since
         for (int k = 0; k < iters_ && w > 0; ++k) {
             if (2 * w > buf.cols) {         // a rank above the cap survived the compression: the buffer follows it
-                require_memory(c, sign_lr_doubles(n, w));
+                require_memory(c, doubles(w));
                 Mat nb(c, n, 2 * w);
                 Mat dstv = nb.colsview(0, w), srcv = buf.colsview(0, w);
                 copy_mat(c, srcv, dstv);
@@ -198,7 +209,7 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
             const Mat P = Pstore_.colsview(k * n, n);
             const double cf = cs_[(size_t)k];
             Mat left = buf.colsview(0, w), right = buf.colsview(w, w);
-            gemm(c, true, false, 1.0, P, left, 0.0, right, nullptr, "signlr_gemm");          // P_k' L_k
+            gemm(c, tr, false, 1.0, P, left, 0.0, right, nullptr, "signlr_gemm");            // P_k' L_k (dual: P_k L_k)
             Mat Dn(c, 2 * w, 2 * w);
             blkdiag(c, Dk, 1.0 / (2.0 * cf), Dk, 0.5 * cf, Dn);
             Dk = Dn;
@@ -211,7 +222,8 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
         LX = Mat(c, n, w);
         if (w > 0) {
             Mat Lv = buf.colsview(0, w);
-            gemm(c, true, false, 1.0, Einv_, Lv, 0.0, LX, nullptr, "signlr_gemm");           // E^-T L
+            if (dual) copy_mat(c, Lv, LX);
+            else gemm(c, true, false, 1.0, Einv_, Lv, 0.0, LX, nullptr, "signlr_gemm");      // E^-T L
         }
         DX = diag_mat(c, vals, 0.5);
     };
@@ -223,7 +235,8 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
     Mat LX, DX;
     replay_lr(G, S, LX, DX);
 
-    // factored residual [G, F'L, E'L] blkdiag(S, [[0, D], [D, 0]]) [..]': its norm through the small matrix on the QR's basis
+    // factored residual [G, F'L, E'L] blkdiag(S, [[0, D], [D, 0]]) [..]' (dual: [G, F L, E L]): its norm through the small matrix on the QR's
+    // basis
     const double target = 100.0 * n * DBL_EPS + 10.0 * rtol;
     Mat Rf, T;
     auto residual = [&]() -> double {
@@ -233,8 +246,8 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
         copy_mat(c, G, g);
         if (p > 0) {
             Mat fl = Rf.colsview(r, p), el = Rf.colsview(r + p, p);
-            gemm(c, true, false, 1.0, F_, LX, 0.0, fl, nullptr, "signlr_gemm");
-            gemm(c, true, false, 1.0, E_, LX, 0.0, el, nullptr, "signlr_gemm");
+            gemm(c, tr, false, 1.0, F_, LX, 0.0, fl, nullptr, "signlr_gemm");
+            gemm(c, tr, false, 1.0, E_, LX, 0.0, el, nullptr, "signlr_gemm");
         }
         T = Mat(c, w, w);
         {
@@ -281,137 +294,11 @@ SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_
     return st;
 }
 
-// The dual equation F Y E' + E Y F' = -G S G' on the same kept sequence (tests/_sign_dual_model.py):
-//     L_0 = E^-1 G,   L_{k+1} = [L_k, P_k L_k],   D_{k+1} = blkdiag(D_k / (2 c_k), (c_k / 2) D_k),   Y = L_inf (D_inf / 2) L_inf'
-// The transform with E^-1 sits at the entry instead of the exit and no operand is transposed; cap, compression, regrowth, refinement and the
-// statistics are solve_lr's, statement for statement (solve_lr itself is left untouched, hence a function of its own).
+SignLrStats SignLyap::solve_lr(const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D) {
+    return solve_lr_impl(false, G, S, rtol, max_width, max_refine, L, D);
+}
 SignLrStats SignLyap::solve_lr_t(const Mat& G, const Mat& S, double rtol, int max_width, int max_refine, Mat& L, Mat& D) {
-    Ctx* c = c_;
-    const int n = n_, r = G.cols;
-    DRE_REQUIRE(iters_ > 0, "solve_lr_t: factor() first");
-    DRE_REQUIRE(G.rows == n && S.rows == r && S.cols == r, "solve_lr_t: G must be n x r and S r x r");
-    DRE_REQUIRE(rtol > 0.0 && rtol < 1.0, "solve_lr_t: rtol must lie in (0, 1)");
-    DRE_REQUIRE(max_width >= 1 && max_width >= r && max_width <= SIGN_LR_MAX_WIDTH,
-                "solve_lr_t: max_width must be at least the width of G (and 1) and at most " + std::to_string(SIGN_LR_MAX_WIDTH));
-    DRE_REQUIRE(max_refine >= 0, "solve_lr_t: max_refine must be >= 0");
-    SignLrStats st;
-    st.iters = iters_;
-    if (r == 0) { L = Mat(c, n, 0); D = Mat(c, 0, 0); return st; }
-    require_memory(c, sign_lr_t_doubles(n, r, max_width));
-
-    // (L0, D0) of a right-hand side -> (L_inf, D_inf / 2) with D diagonal; E^-1 L0 is written straight into the left columns of the buffer and
-    // P_k L_k into the columns to its right
-    auto replay_lr = [&](const Mat& L0, const Mat& D0, Mat& LY, Mat& DY) {
-        int w = L0.cols;
-        const int cap = std::max(max_width, w);
-        if (cap > max_width) require_memory(c, sign_lr_t_doubles(n, r, cap));
-        Mat buf(c, n, 2 * cap);
-        Mat left0 = buf.colsview(0, w);
-        gemm(c, false, false, 1.0, Einv_, L0, 0.0, left0, nullptr, "signlr_gemm");           // E^-1 L0
-        Mat Dk = D0;
-        Compressor comp(c);
-        auto compress = [&]() -> std::vector<double> {
-            Mat Lv = buf.colsview(0, w);
-            comp.form(Lv, Dk);
-            std::vector<double> vals = comp.finish(buf, rtol);
-            ++st.compressions;
-            w = (int)vals.size();
-            return vals;
-        };
-        std::vector<double> vals;
-        bool fresh = false;          // Dk == diag(vals) of a compression that nothing has touched since
-        for (int k = 0; k < iters_ && w > 0; ++k) {
-            if (2 * w > buf.cols) {         // a rank above the cap survived the compression: the buffer follows it
-                require_memory(c, sign_lr_t_doubles(n, r, w));
-                Mat nb(c, n, 2 * w);
-                Mat dstv = nb.colsview(0, w), srcv = buf.colsview(0, w);
-                copy_mat(c, srcv, dstv);
-                buf = nb;
-            }
-            const Mat P = Pstore_.colsview(k * n, n);
-            const double cf = cs_[(size_t)k];
-            Mat left = buf.colsview(0, w), right = buf.colsview(w, w);
-            gemm(c, false, false, 1.0, P, left, 0.0, right, nullptr, "signlr_gemm");         // P_k L_k
-            Mat Dn(c, 2 * w, 2 * w);
-            blkdiag(c, Dk, 1.0 / (2.0 * cf), Dk, 0.5 * cf, Dn);
-            Dk = Dn;
-            w *= 2;
-            fresh = false;
-            st.peak_width = std::max<long>(st.peak_width, w);
-            if (w > max_width) { vals = compress(); Dk = diag_mat(c, vals, 1.0); fresh = true; }
-        }
-        if (!fresh && w > 0) vals = compress();
-        LY = Mat(c, n, w);
-        if (w > 0) {
-            Mat Lv = buf.colsview(0, w);
-            copy_mat(c, Lv, LY);
-        }
-        DY = diag_mat(c, vals, 0.5);
-    };
-
-    Compressor comp(c);
-    comp.form(G, S);
-    const double normR = comp.norm();
-    st.peak_width = r;
-    Mat LY, DY;
-    replay_lr(G, S, LY, DY);
-
-    // factored residual [G, F L, E L] blkdiag(S, [[0, D], [D, 0]]) [..]': its norm through the small matrix on the QR's basis
-    const double target = 100.0 * n * DBL_EPS + 10.0 * rtol;
-    Mat Rf, T;
-    auto residual = [&]() -> double {
-        const int p = LY.cols, w = r + 2 * p;
-        Rf = Mat(c, n, w);
-        Mat g = Rf.colsview(0, r);
-        copy_mat(c, G, g);
-        if (p > 0) {
-            Mat fl = Rf.colsview(r, p), el = Rf.colsview(r + p, p);
-            gemm(c, false, false, 1.0, F_, LY, 0.0, fl, nullptr, "signlr_gemm");
-            gemm(c, false, false, 1.0, E_, LY, 0.0, el, nullptr, "signlr_gemm");
-        }
-        T = Mat(c, w, w);
-        {
-            TimedScope ts(c, "signlr_small", 8.0 * w * w, 0.0);
-            hipLaunchKernelGGL(k_lr_res_t, dim3(grid_for((size_t)w * w)), dim3(256), 0, c->stream, r, (const double*)S.p, S.ld, p, (const double*)DY.p,
-                               DY.ld, T.p, T.ld);
-        }
-        comp.form(Rf, T);
-        const double nr = comp.norm();
-        return normR > 0.0 ? nr / normR : nr;
-    };
-    st.res0 = st.res = residual();
-    while (st.res > target && st.refinements < max_refine && std::isfinite(st.res)) {
-        std::vector<double> rv = comp.finish(Rf, rtol);          // the compressed residual factor, in the left columns of Rf
-        ++st.compressions;
-        const int pr = (int)rv.size();
-        if (pr == 0) break;
-        Mat Lr = Rf.colsview(0, pr), Dr = diag_mat(c, rv, 1.0), LdY, DdY;
-        replay_lr(Lr, Dr, LdY, DdY);
-        // Y <- Y + dY: append and compress
-        const int p = LY.cols, pd = LdY.cols, w = p + pd;
-        if (pd == 0) break;
-        Mat cat(c, n, w), Dc(c, w, w);
-        Mat a = cat.colsview(0, p), b = cat.colsview(p, pd);
-        copy_mat(c, LY, a);
-        copy_mat(c, LdY, b);
-        blkdiag(c, DY, 1.0, DdY, 1.0, Dc);
-        st.peak_width = std::max<long>(st.peak_width, w);
-        Compressor cx(c);
-        cx.form(cat, Dc);
-        std::vector<double> yv = cx.finish(cat, rtol);
-        ++st.compressions;
-        const int py = (int)yv.size();
-        LY = Mat(c, n, py);
-        if (py > 0) { Mat src = cat.colsview(0, py); copy_mat(c, src, LY); }
-        DY = diag_mat(c, yv, 1.0);
-        ++st.refinements;
-        st.res = residual();
-    }
-    DRE_HIP(hipGetLastError());
-    st.rank = LY.cols;
-    L = LY;
-    D = DY;
-    return st;
+    return solve_lr_impl(true, G, S, rtol, max_width, max_refine, L, D);
 }
 
 }  // namespace dre

@@ -1,4 +1,5 @@
-// Factored replay of a kept sign iteration (SignLyap::solve_lr): LDL' right-hand side in, LDL' solution out, no shifts.
+// Factored replay of a kept sign iteration (SignLyap::solve_lr, and solve_lr_t for the dual equation): LDL' right-hand side in, LDL' solution
+// out, no shifts.
 // See DESIGN.md §9.2.
 #pragma once
 #include "dense_sign.hpp"

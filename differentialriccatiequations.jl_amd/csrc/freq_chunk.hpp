@@ -1,5 +1,5 @@
-// Chunking of a frequency sweep (freq_response.hip) as plain host arithmetic: no HIP, no other header of the library, so that a host compiler
-// takes it alone (tests/test_freq_response_host.py compiles it and checks it against brute force).
+// Chunking of a frequency sweep (freq_sweep.hpp: the driver of freq_response.hip and transfer_eval.hip) as plain host arithmetic:
+// no HIP, no other header of the library, so that a host compiler takes it alone (tests/test_freq_response_host.py compiles it and checks it against brute force).
 #pragma once
 
 namespace dre {

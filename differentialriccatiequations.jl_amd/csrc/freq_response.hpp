@@ -22,6 +22,7 @@
 // E may be singular (descriptor systems of index 1 and above): nothing here inverts E, unlike the sign-function entry points.  A member whose
 // i w E - A is singular (w on a pole; exactly zero or non-finite pivot, a NaN in its system) gets ERR_SINGULAR in its status and NaN in its H;
 // the other members go on.  A member's result is bit for bit independent of the other members and of the chunk it falls in.
+// Validation, chunk plan, chunk loop, read-backs and per-member status are the driver's that transfer_eval shares (freq_sweep.hpp).
 #pragma once
 #include <vector>
 

@@ -13,7 +13,7 @@
 // The refinement step is there for the reason freq_response.hpp gives: the blocked inversion is accurate norm-wise only.
 // Cost per point: 8 n^3 real flops (n^3 complex multiply-adds; the real embedding of freq_response does 16 n^3), half as many panels of
 // half the height, and 2 n^2 doubles for the matrix instead of 4 n^2.  Failures, masks, chunks and the bit-for-bit independence of a
-// member are freq_response's.
+// member are freq_response's: both run on the one driver of freq_sweep.hpp.
 #pragma once
 #include <vector>
 
