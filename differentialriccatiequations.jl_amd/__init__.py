@@ -11,6 +11,7 @@ from .api import (ADI, ADISolver, Backslash, BlockLinearProblem, BlockLinearSolv
                   residual, solve, solve_gale, solve_gale_dense, solve_gale_factored_sign, solve_gale_pair, solve_gare, solve_gare_dense, solve_gdre, superlinear_forcing, svd_jacobi, sym_eigh,
                   balanced_truncation, hankel_singular_values, sym_eigh_batch, svd_jacobi_batch, balanced_truncation_batch,
                   freq_response, freq_response_batch, sigma_response, bt_error, transfer_function, transfer_function_batch,
+                  step_response, impulse_response, simulate,
                   LQGReducedModel, solve_gare_pair, lqg_balanced_truncation, lqg_characteristic_values, lqg_error)
 from .steel_profile import SIZES, initial_value, steel_profile
 

@@ -227,6 +227,7 @@ PROTOTYPES = {
     "dre_dense_invert_complex_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pi32, _pd, _pi32]),
     "dre_transfer_eval": (C.c_int, [_vp] * 5 + [C.c_int, _pd, _pd, C.c_int, _pd, _pd, _pi32, _pi64]),
     "dre_transfer_eval_batched": (C.c_int, [_vp, C.c_int] + [_pvp] * 4 + [C.c_int, _pd, _pd, C.c_int, _pd, _pd, _pi32, _pi64]),
+    "dre_time_response": (C.c_int, [_vp] * 5 + [C.c_int, C.c_double, C.c_int, C.c_int, _pd, C.c_int, _pd, C.c_int, _pd, _pi64]),
 }
 
 _lib = None

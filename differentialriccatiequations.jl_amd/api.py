@@ -1859,6 +1859,18 @@ class ReducedModel:
         and its keyword arguments (method="embedding" | "complex" among them)."""
         return freq_response(self.Er, self.Ar, self.Br, self.Cr, omega, D=D, **kw)
 
+    def step_response(self, dt, steps, D=None, **kw):
+        """the step response of the reduced model on t_k = k dt, (steps + 1, q, m), on the device: `step_response` with E_r = I and its keywords"""
+        return step_response(self.Er, self.Ar, self.Br, self.Cr, dt, steps, D=D, **kw)
+
+    def impulse_response(self, dt, steps, **kw):
+        """the impulse response of the reduced model, (steps + 1, q, m), on the device: `impulse_response` with E_r = I and its keywords"""
+        return impulse_response(self.Er, self.Ar, self.Br, self.Cr, dt, steps, **kw)
+
+    def simulate(self, u, dt, x0=None, D=None, **kw):
+        """the reduced model's output for the input samples u (x0 in reduced coordinates), on the device: `simulate` with E_r = I and its keywords"""
+        return simulate(self.Er, self.Ar, self.Br, self.Cr, u, dt, x0=x0, D=D, **kw)
+
 
 def _balance_check(name, E, A, B, C, alg, order, tol):
     if not isinstance(alg, (FactoredSign, MatrixSign)):
@@ -2372,6 +2384,142 @@ def bt_error(E, A, B, C, rom, omega, chunk=None, ctx=None, method="embedding"):
 
 
 # ------------------------------------------------------------------------------------------------
+# Time response: step, impulse, simulate                                    csrc/time_response.hip
+# ------------------------------------------------------------------------------------------------
+TIME_METHODS = ("tustin", "backward_euler")
+TIME_SIMULATE_MAX_Q, TIME_SIMULATE_MAX_QM = 256, 2048     # TR_CONV_MAX_Q, TR_CONV_MAX_QM of csrc/time_response.hpp
+
+
+def _time_check(name, E, A, B, C, dt, steps, D, method, block):
+    """the argument errors of the time-response calls, before anything runs on the device -> ((E, A, B, C), dt, D)"""
+    if method not in TIME_METHODS:
+        raise ValueError(f"{name}: method must be 'tustin' (order 2, A-stable) or 'backward_euler' (order 1, L-stable; the choice for a singular "
+                         f"E), got {method!r}; nothing was run on the device")
+    if isinstance(dt, (bool, np.bool_)) or not isinstance(dt, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{name}: dt must be a number, not {type(dt).__name__}; nothing was run on the device")
+    if not np.isfinite(dt) or dt <= 0:
+        raise ValueError(f"{name}: dt must be finite and positive, got {dt!r}; nothing was run on the device")
+    if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)):
+        raise TypeError(f"{name}: the number of steps must be an int, not {type(steps).__name__}; nothing was run on the device")
+    if steps < 1:
+        raise ValueError(f"{name}: at least one time step is needed, got {steps}; nothing was run on the device")
+    if block is not None and (isinstance(block, (bool, np.bool_)) or not isinstance(block, (int, np.integer)) or block < 1 or block & (block - 1)):
+        raise ValueError(f"{name}: block must be None (the default block length) or a power of two (1: plain sequential stepping), got {block!r}; "
+                         "nothing was run on the device")
+    ms = []
+    for nm, M in zip("EABC", (E, A, B, C)):
+        if not isinstance(M, (np.ndarray, LowRankUpdate, ScaledPencil)) and not sp.issparse(M):
+            raise TypeError(f"{name}: {nm} must be a matrix, not {type(M).__name__}; nothing was run on the device")
+        ms.append(_dense_f64(_dense_operator(M)))
+    Ed, Am, Bm, Cm = ms
+    n = Ed.shape[0] if Ed.ndim == 2 else 0
+    if Ed.ndim != 2 or Ed.shape != (n, n) or Am.shape != (n, n) or Bm.ndim != 2 or Bm.shape[0] != n or Cm.ndim != 2 or Cm.shape[1] != n \
+            or n < 1 or Bm.shape[1] < 1 or Cm.shape[0] < 1:
+        raise ValueError(f"{name}: E and A must be n x n, B n x m and C q x n (n, m, q >= 1); got {Ed.shape}, {Am.shape}, {Bm.shape}, {Cm.shape}; "
+                         "nothing was run on the device")
+    if D is not None:
+        D = np.asarray(D, dtype=float)
+        if D.shape != (Cm.shape[0], Bm.shape[1]):
+            raise ValueError(f"{name}: D must be q x m = {(Cm.shape[0], Bm.shape[1])}, got {D.shape}; nothing was run on the device")
+    return (Ed, Am, Bm, Cm), float(dt), D
+
+
+def _time_run(mats, method, dt, K, kind, U, X0, block, ctx):
+    """one dre_time_response call -> (Y flat, info)"""
+    ctx = ctx or dev.default_context()
+    n, m, q = mats[0].shape[0], mats[2].shape[1], mats[3].shape[0]
+    S = U.shape[0] if kind == 2 else 0
+    ups = [ctx.upload(M) for M in mats]
+    Y = np.zeros((S * (K + 1) * q) if kind == 2 else ((K + 1) * q * m))
+    info = (C.c_int64 * 4)()
+    pd = C.POINTER(C.c_double)
+    Up = np.ascontiguousarray(U, dtype=float).ctypes.data_as(pd) if kind == 2 else None        # (S, K+1, m) C-ordered: u_k[c] of s at s (K+1) m + k m + c
+    Xc = np.ascontiguousarray(X0, dtype=float) if X0 is not None else None                      # (S, n) C-ordered = n x S column-major
+    ctx.chk(ctx.lib.dre_time_response(ctx.ptr, *(u.ptr for u in ups), TIME_METHODS.index(method), dt, int(K), kind, Up, S,
+                                      Xc.ctypes.data_as(pd) if Xc is not None else None, int(block or 0), Y.ctypes.data_as(pd), info))
+    return Y, dict(block=int(info[0]), blocks=int(info[1]), squarings=int(info[2]), launches=int(info[3]), method=method, order=n)
+
+
+def step_response(E, A, B, C, dt, steps, D=None, method="tustin", block=None, ctx=None, return_info=False):
+    """The step response of the dense descriptor system E ẋ = A x + B u, y = C x + D u on t_k = k dt, k = 0 .. steps, on the device
+    (`dre_time_response`): a real array (steps + 1, q, m), entry [k, :, c] the output at t_k for a unit step on input channel c from x(0) = 0.
+    method="tustin" (default; order 2, A-stable): x_{k+1} = M x_k + N (u_k + u_{k+1}) with P = E − (dt/2) A, M = 2 P⁻¹E − I, N = (dt/2) P⁻¹B;
+    method="backward_euler" (order 1, L-stable): P = E − dt A, M = P⁻¹E, N = dt P⁻¹B, input u_{k+1}.  E may be singular; tustin then has the
+    eigenvalue −1 on the algebraic part (it never decays), so backward_euler is the method for a singular E.  The pencil need not be stable:
+    a growing response is a valid result.  The outputs come from the Markov sequence C Mʲ, built by doubling up to the block length and then
+    `block` samples per GEMM, not from `steps` dependent thin products; block=None: the power of two at which one such GEMM fills the device
+    (`tr_default_block` of csrc/time_response.hpp); block=1: plain sequential stepping.  D (q x m) is added on the host.  A call is bit for bit repeatable.  return_info=True appends dict(block,
+    blocks, squarings, launches, method, order).  A singular P (dt on a pole of the scheme, a NaN in E or A) is DREError(-4).  Wrong types and
+    shapes, a non-finite or non-positive dt, steps < 1, an unknown method and a block that is not a power of two are errors before anything
+    runs on the device."""
+    name = "step_response"
+    mats, dt, D = _time_check(name, E, A, B, C, dt, steps, D, method, block)
+    Y, info = _time_run(mats, method, dt, steps, 0, None, None, block, ctx)
+    Y = Y.reshape(steps + 1, mats[2].shape[1], mats[3].shape[0]).transpose(0, 2, 1)      # samples hold q x m column-major
+    Y = np.ascontiguousarray(Y) if D is None else Y + D
+    return (Y, info) if return_info else Y
+
+
+def impulse_response(E, A, B, C, dt, steps, method="tustin", block=None, ctx=None, return_info=False):
+    """The impulse response on t_k = k dt, k = 0 .. steps: a real array (steps + 1, q, m), the free response y_k = C Mᵏ E⁻¹B from
+    x(0+) = E⁻¹B under the one-step scheme `method` (see `step_response`, whose other arguments and errors this call shares).  E must be
+    regular: a singular E is DREError(-4).  A feedthrough D is not added: a Dirac impulse has no sample."""
+    name = "impulse_response"
+    mats, dt, _ = _time_check(name, E, A, B, C, dt, steps, None, method, block)
+    Y, info = _time_run(mats, method, dt, steps, 1, None, None, block, ctx)
+    Y = np.ascontiguousarray(Y.reshape(steps + 1, mats[2].shape[1], mats[3].shape[0]).transpose(0, 2, 1))
+    return (Y, info) if return_info else Y
+
+
+def simulate(E, A, B, C, u, dt, x0=None, D=None, method="tustin", block=None, ctx=None, return_info=False):
+    """The output of E ẋ = A x + B u, y = C x + D u for given input samples u_k = u(k dt) and initial state x0, on the device: u of shape
+    (K+1, m) -> (K+1, q); u of shape (S, K+1, m) -> (S, K+1, q), S input signals ("scenarios") in one call; x0 of shape (n,) (shared) or
+    (S, n), None: zero.  y_k = C Mᵏ x_0 + Σ_{j<k} h_j w_{k−1−j} + D u_k with h_j = C Mʲ N and w_k = u_k + u_{k+1} (tustin) or u_{k+1}
+    (backward_euler): a causal convolution with the Markov parameters, K² q m S / 2 multiply-adds beside the GEMMs of `step_response`, whose
+    other arguments and errors this call shares.  Limits: q <= 256 and q m <= 2048.  A non-finite u or x0 is an error before anything runs on
+    the device."""
+    name = "simulate"
+    if not isinstance(u, (np.ndarray, list, tuple)):
+        raise TypeError(f"{name}: u must be an array of input samples, not {type(u).__name__}; nothing was run on the device")
+    try:
+        ua = np.asarray(u, dtype=float)
+    except (TypeError, ValueError):
+        raise TypeError(f"{name}: u must be a real array of input samples; nothing was run on the device") from None
+    if ua.ndim not in (2, 3):
+        raise ValueError(f"{name}: u must have shape (K+1, m) or (S, K+1, m), got {ua.shape}; nothing was run on the device")
+    single = ua.ndim == 2
+    U = ua[None] if single else ua
+    S, K = U.shape[0], U.shape[1] - 1
+    mats, dt, D = _time_check(name, E, A, B, C, dt, K, D, method, block)
+    n, m, q = mats[0].shape[0], mats[2].shape[1], mats[3].shape[0]
+    if S < 1 or S > 65535 or U.shape[2] != m:
+        raise ValueError(f"{name}: u must have shape (K+1, m) or (S, K+1, m) with m = {m} and 1 <= S <= 65535, got {ua.shape}; nothing was run on "
+                         "the device")
+    if not np.isfinite(U).all():
+        raise ValueError(f"{name}: u has a non-finite entry; nothing was run on the device")
+    X0 = None
+    if x0 is not None:
+        try:
+            xa = np.asarray(x0, dtype=float)
+        except (TypeError, ValueError):
+            raise TypeError(f"{name}: x0 must be a real array; nothing was run on the device") from None
+        if xa.shape not in ((n,), (S, n)):
+            raise ValueError(f"{name}: x0 must have shape (n,) or (S, n) = {(n,)} or {(S, n)}, got {xa.shape}; nothing was run on the device")
+        if not np.isfinite(xa).all():
+            raise ValueError(f"{name}: x0 has a non-finite entry; nothing was run on the device")
+        X0 = np.broadcast_to(xa, (S, n))
+    if q > TIME_SIMULATE_MAX_Q or q * m > TIME_SIMULATE_MAX_QM:
+        raise ValueError(f"{name}: the convolution kernel takes q <= {TIME_SIMULATE_MAX_Q} outputs and q m <= {TIME_SIMULATE_MAX_QM}, got q = {q}, "
+                         f"m = {m}; nothing was run on the device")
+    Y, info = _time_run(mats, method, dt, K, 2, U, X0, block, ctx)
+    Y = Y.reshape(S, K + 1, q)
+    if D is not None:
+        Y = Y + U @ D.T
+    Y = Y[0] if single else Y
+    return (Y, info) if return_info else Y
+
+
+# ------------------------------------------------------------------------------------------------
 # LQG balanced truncation from one Hamiltonian sign iteration               csrc/dense_are.hip, csrc/balance.hip
 # ------------------------------------------------------------------------------------------------
 @dataclass
@@ -2404,6 +2552,18 @@ class LQGReducedModel:
         """H_r(iω) = Cr (iω I - Ar)⁻¹ Br (+ D) of the reduced model at every frequency of omega, on the device (as `ReducedModel.freq_response`;
         keywords as `freq_response`, method="embedding" | "complex" among them)."""
         return freq_response(self.Er, self.Ar, self.Br, self.Cr, omega, D=D, **kw)
+
+    def step_response(self, dt, steps, D=None, **kw):
+        """the step response of the reduced model on t_k = k dt, (steps + 1, q, m), on the device: `step_response` with E_r = I and its keywords"""
+        return step_response(self.Er, self.Ar, self.Br, self.Cr, dt, steps, D=D, **kw)
+
+    def impulse_response(self, dt, steps, **kw):
+        """the impulse response of the reduced model, (steps + 1, q, m), on the device: `impulse_response` with E_r = I and its keywords"""
+        return impulse_response(self.Er, self.Ar, self.Br, self.Cr, dt, steps, **kw)
+
+    def simulate(self, u, dt, x0=None, D=None, **kw):
+        """the reduced model's output for the input samples u (x0 in reduced coordinates), on the device: `simulate` with E_r = I and its keywords"""
+        return simulate(self.Er, self.Ar, self.Br, self.Cr, u, dt, x0=x0, D=D, **kw)
 
 
 def _lqg_check(name, E, A, B, C, alg, order, tol, Rinv=None, S=None):

@@ -19,6 +19,7 @@
 #include "engine.hpp"
 #include "dense_cgj.hpp"
 #include "freq_response.hpp"
+#include "time_response.hpp"
 #include "transfer_eval.hpp"
 #include "gemm_probe_check.hpp"
 #include "hostla.hpp"
@@ -87,7 +88,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 116; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 117; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -101,6 +102,7 @@ int dre_version(void) { return 116; }  // 101: dense path (dre_dense_gale_solve,
                                         // 115: complex Gauss-Jordan inversion and the transfer function at complex points (dre_dense_invert_complex_batched,
                                         //      dre_transfer_eval, dre_transfer_eval_batched)
                                         // 116: dre_adi_chain_probe (test surface of the dense-inverse ADI chain)
+                                        // 117: time response of dense descriptor systems: step, impulse, simulate (dre_time_response)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1785,6 +1787,17 @@ int dre_transfer_eval_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E,
 int dre_transfer_eval(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int K, const double* s_re,
                       const double* s_im, int chunk, double* H_re, double* H_im, int32_t* status, int64_t* info) {
     return dre_transfer_eval_batched(ctx, 1, &E, &A, &B, &C, K, s_re, s_im, chunk, H_re, H_im, status, info);
+}
+
+// ---- time response: step, impulse, simulate (time_response.hip) --------------------------------------------------------------------------
+int dre_time_response(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int method, double dt, int K,
+                      int kind, const double* U, int S, const double* X0, int block, double* Y, int64_t* info) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && B && C && Y, "dre_time_response: null argument");
+        const TimeResponse r = time_response(&ctx->c, E->m, A->m, B->m, C->m, method, dt, K, kind, U, S, X0, block);
+        std::memcpy(Y, r.Y.data(), r.Y.size() * sizeof(double));
+        if (info) { info[0] = r.block; info[1] = r.blocks; info[2] = r.squarings; info[3] = r.launches; }
+    });
 }
 
 int dre_dense_gale_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const* E, const dre_dense* const* F, const dre_dense* const* R,

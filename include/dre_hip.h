@@ -704,6 +704,33 @@ int dre_transfer_eval_batched(dre_ctx* ctx, int nsys, const dre_dense* const* E,
                               const dre_dense* const* C, int K, const double* s_re, const double* s_im, int chunk, double* H_re /* q*m*K*nsys */,
                               double* H_im /* q*m*K*nsys */, int32_t* status /* K*nsys */, int64_t* info /* 2, may be NULL */);
 
+/* ---- time response of dense descriptor systems: step, impulse, simulate (dre_version >= 117) ----------------------------------------------
+ * E x' = A x + B u, y = C x on the uniform grid t_k = k dt, k = 0 .. K, by one of two one-step schemes x_{k+1} = M x_k + N w_k:
+ *   method 0, tustin (order 2, A-stable):          P = E - (dt/2) A, M = 2 P^-1 E - I, N = (dt/2) P^-1 B, w_k = u_k + u_{k+1};
+ *   method 1, backward Euler (order 1, L-stable):  P = E - dt A,     M = P^-1 E,       N = dt P^-1 B,     w_k = u_{k+1}.
+ * kind 0, step response: y_k[:, c] for a unit step on input channel c from x_0 = 0, every channel;  kind 1, impulse response: the free
+ * response y_k = C M^k E^-1 B from x(0+) = E^-1 B (E must be regular; no feedthrough term);  kind 2, simulate: the outputs for S input
+ * signals ("scenarios") and initial states.  A feedthrough D u_k is the caller's to add.  The pencil need not be stable.  E may be singular
+ * for kinds 0 and 2; under tustin the algebraic part then has the eigenvalue -1 in M, and backward Euler is the method to use.
+ * The outputs are formed from the Markov sequence G_j = C M^j, which is built by doubling ([G_0 .. G_{2J-1}] = [O_J; O_J M^J]) up to the
+ * block length L and then L samples per GEMM: log2 L + ceil((K+1)/L) large GEMMs in place of K dependent thin ones.  block: L, a power of
+ * two (one beyond the power of two >= K + 1 is cut to it); 0: the smallest power of two at which the ceil(L q / 64) ceil(n / 64) output
+ * tiles of one such GEMM number 256, cut to the power of two >= K + 1 and halved while the stack would hold over 5/4 (K + 1) sample rows; 1: plain
+ * sequential stepping.
+ * U (kind 2; NULL otherwise): (K+1) m x S doubles on the host, u_k[c] of scenario s at s*(K+1)*m + k*m + c.  X0 (kind 2, may be NULL: zero):
+ * n x S doubles on the host, column-major.  S is read under kind 2 only.
+ * Y (host): kinds 0 and 1: (K+1)*q*m doubles, sample k at k*q*m, q x m column-major;  kind 2: S*(K+1)*q doubles, scenario s at s*(K+1)*q,
+ * sample k at k*q.  info (4, may be NULL): [0] L in force, [1] blocks = ceil((K+1)/L), [2] squarings of M, [3] launches (kernels, GEMM calls
+ * and inversions enqueued, a GEMM and an inversion counted as one each).  A call is bit for bit repeatable.
+ * DRE_ERR_INVALID, before any launch: a NULL argument, K < 1, dt not finite or <= 0, an unknown method or kind, mismatched shapes, S < 1 or
+ * U NULL under kind 2 (U or X0 given under another kind), a block that is negative or not a power of two, a stack of (K + 1 rounded up to L)
+ * q n elements beyond 2^31 - 1, and under kind 2 q > 256 or q m > 2048.  DRE_ERR_ALLOC, before any launch: the stack ((K + 1 rounded up to L)
+ * q n doubles), 4 n^2 and the thin operands do not fit the free device memory (there is no chunking over time).  DRE_ERR_SINGULAR: P has an
+ * exactly zero or non-finite pivot (dt on a pole of the scheme, a NaN in E or A), or E has one under kind 1; Y is not written. */
+int dre_time_response(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, int method, double dt, int K,
+                      int kind, const double* U /* (K+1)*m*S or NULL */, int S, const double* X0 /* n*S or NULL */, int block,
+                      double* Y, int64_t* info /* 4, may be NULL */);
+
 /* ---- test and diagnostic surface: the internal GEMM entry points one by one (dre_version >= 108) ----------------------------------------
  * dre_gemm_probe calls ONE entry point of the f64 MFMA GEMM family with arguments a public caller cannot form: operands that are views into
  * larger buffers, member masks, device-side counts, the `done` flag of an ADI control block.  It has no wrapper beyond the ctypes prototype
