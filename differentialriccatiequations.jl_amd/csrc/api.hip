@@ -1513,6 +1513,14 @@ int dre_dense_gale_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* F, c
         *X = out;
     });
 }
+// a dense driver's result (single, adaptive, one member of a batch) as the handle the result accessors read; d is emptied
+static dre_gdre_result* wrap_dense_result(DenseGdreResult& d, int n, int m) {
+    auto* r = new dre_gdre_result();
+    r->dense = true; r->n = n; r->m = m;
+    r->r.t = std::move(d.t); r->r.Kt = std::move(d.Kt);
+    r->Xd = std::move(d.X); r->solves = std::move(d.solves);
+    return r;
+}
 int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
                          double t0, double tf, double dt, int order, int save_state, int maxiters, double tol, int max_refine,
                          dre_gdre_result** out) {
@@ -1520,11 +1528,7 @@ int dre_dense_gdre_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, c
         Ctx* c = &ctx->c;
         DRE_REQUIRE(E && A && B && C && X0 && out, "dre_dense_gdre_solve: null argument");
         DenseGdreResult d = dense_gdre_solve(c, E->m, A->m, B->m, C->m, X0->m, t0, tf, dt, order, save_state != 0, maxiters, tol, max_refine);
-        auto* r = new dre_gdre_result();
-        r->dense = true; r->n = E->m.rows; r->m = B->m.cols;
-        r->r.t = std::move(d.t); r->r.Kt = std::move(d.Kt);
-        r->Xd = std::move(d.X); r->solves = std::move(d.solves);
-        *out = r;
+        *out = wrap_dense_result(d, E->m.rows, B->m.cols);
     });
 }
 int dre_dense_gdre_solve_adaptive(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* C, const dre_dense* X0,
@@ -1538,10 +1542,7 @@ int dre_dense_gdre_solve_adaptive(dre_ctx* ctx, const dre_dense* E, const dre_de
         sc.rtol = rtol; sc.atol = atol; sc.dt_min = dt_min; sc.dt_max = dt_max; sc.max_steps = (long)max_steps;
         sc.tstops.assign(tstops, tstops + ntstops);
         DenseAdaptiveResult d = dense_gdre_solve_adaptive(c, E->m, A->m, B->m, C->m, X0->m, t0, tf, dt0, order, sc, save_state != 0, maxiters, tol, max_refine);
-        auto* r = new dre_gdre_result();
-        r->dense = true; r->n = E->m.rows; r->m = B->m.cols;
-        r->r.t = std::move(d.r.t); r->r.Kt = std::move(d.r.Kt);
-        r->Xd = std::move(d.r.X); r->solves = std::move(d.r.solves);
+        dre_gdre_result* r = wrap_dense_result(d.r, E->m.rows, B->m.cols);
         r->adaptive = true; r->accepted = d.accepted; r->rejected = d.rejected; r->step_err = std::move(d.err);
         *out = r;
     });
@@ -1840,7 +1841,7 @@ int dre_dense_gdre_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const
         Ctx* c = &ctx->c;
         DRE_REQUIRE(E && A && B && C && X0 && out && status && batch >= 1 && E[0] && B[0] && C[0],
                     "dre_dense_gdre_solve_batched: null argument or batch < 1");
-        DRE_REQUIRE(order >= 1 && order <= 4, "dense path: order must be 1 .. 4");
+        dense_check_order(order);
         DRE_REQUIRE(order <= 2, "dre_dense_gdre_solve_batched: only Ros1 and Ros2 (order 1, 2) are batched; order " + std::to_string(order) +
                                     " runs through dre_dense_gdre_solve");
         const int n = E[0]->m.rows, m = B[0]->m.cols, q = C[0]->m.rows;
@@ -1850,10 +1851,8 @@ int dre_dense_gdre_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const
         check_members(batch, B, n, m, "dre_dense_gdre_solve_batched", "B");
         check_members(batch, C, q, n, "dre_dense_gdre_solve_batched", "C");
         check_members(batch, X0, n, n, "dre_dense_gdre_solve_batched", "X0");
-        DRE_REQUIRE(dt != 0.0 && std::isfinite(dt), "dense path: dt must be finite and nonzero");
+        const int nsteps = (int)dense_time_grid(t0, tf, dt).size() - 1;
         DRE_REQUIRE(maxiters >= 1 && maxiters <= 1000, "dense path: maxiters must be in 1 .. 1000");
-        const int nsteps = (int)std::floor((tf - t0) / dt + 1e-9);
-        DRE_REQUIRE(nsteps >= 0, "tspan and dt point in opposite directions");
         require_memory(c, dense_gdre_batched_doubles(batch, n, m, q, nsteps, order, save_state != 0, maxiters));
         for (int b = 0; b < batch; ++b) out[b] = nullptr;
         Mat Es = pack_stack(c, batch, E, n, n), As = pack_stack(c, batch, A, n, n), Bs = pack_stack(c, batch, B, n, m),
@@ -1861,14 +1860,7 @@ int dre_dense_gdre_solve_batched(dre_ctx* ctx, int batch, const dre_dense* const
         std::vector<DenseGdreResult> res;
         std::vector<BatchMemberStatus> st;
         dense_gdre_solve_batched(c, batch, Es, As, Bs, Cs, Xs, m, q, t0, tf, dt, order, save_state != 0, maxiters, tol, max_refine, res, st);
-        for (int b = 0; b < batch; ++b) {
-            auto* r = new dre_gdre_result();
-            DenseGdreResult& d = res[(size_t)b];
-            r->dense = true; r->n = n; r->m = m;
-            r->r.t = std::move(d.t); r->r.Kt = std::move(d.Kt);
-            r->Xd = std::move(d.X); r->solves = std::move(d.solves);
-            out[b] = r;
-        }
+        for (int b = 0; b < batch; ++b) out[b] = wrap_dense_result(res[(size_t)b], n, m);
         report_members(ctx, st, status);
     });
 }

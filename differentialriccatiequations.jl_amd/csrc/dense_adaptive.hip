@@ -1,6 +1,6 @@
 // Dense path with step-size control (GDREProblem{<:Matrix}, Ros2(MatrixSign()), adaptive = StepControl(...)):
 //   k_step_error, k_step_decide   the new state, the weighted error of the embedded 2(1) pair and the controller's factor, in two launches;
-//   dense_gdre_solve_adaptive     the Ros2 step of dense_gdre_solve (dense_sign.hip) inside an accept / reject loop on the host.
+//   dense_gdre_solve_adaptive     the Ros2 stages of dense_ros.hpp (the step of dense_gdre_solve) inside an accept / reject loop on the host.
 // One trial costs one sign factorisation of gamma tau (A - BK) - E/2, exactly like a step of the fixed grid: both stages replay it, and the
 // estimate D = Xnew - (X + tau K1) needs nothing beyond K1 and K2.  The host model of exactly this driver is tests/_adaptive_ros2_model.py.
 #include "dense_adaptive.hpp"
@@ -9,6 +9,7 @@
 
 #include "dense.hpp"
 #include "dense_device.hpp"
+#include "dense_ros.hpp"
 #include "profiling.hpp"
 
 namespace dre {
@@ -69,26 +70,21 @@ DenseAdaptiveResult dense_gdre_solve_adaptive(Ctx* ctx, const Mat& E, const Mat&
                                               double dt0, int order, const StepControl& sc, bool save_state, int maxiters, double tol, int max_refine) {
     const int n = E.rows, m = B.cols;
     check_control(t0, tf, dt0, order, sc);
-    DRE_REQUIRE(E.cols == n && A.rows == n && A.cols == n && B.rows == n && C.cols == n && X0.rows == n && X0.cols == n,
-                "adaptive dense path: E, A, X0 must be n x n, B n x m, C q x n");
+    dense_check_shapes("adaptive dense path", E, A, B, C, X0);
     DenseAdaptiveResult res;
     DenseGdreResult& out = res.r;
     // the fixed part: dense_gdre_solve's count with one state (the sign solver's (maxiters + 10) n^2, 16 n^2 of driver matrices, one state)
     // and Xnew; K(t) and the saved states grow in chunks
     SignLyap lyap(ctx, E, maxiters, tol, max_refine, 16 + 1 + 1);
+    DenseRosOps ops{ctx, lyap, out.solves};
     auto sq = [&] { return Mat(ctx, n, n); };
-    Mat X = sq(), Xnew = sq(), CtC = sq(), Acl = sq(), gF = sq(), T = sq(), AXE = sq(), Racc = sq(), Rs = sq(), K1 = sq(), K2 = sq();
-    Mat XB(ctx, n, m), V1(ctx, n, m);
+    Mat X = sq(), Xnew = sq(), CtC = sq();
+    RosWork<Mat> w{sq(), sq(), sq(), sq(), sq(), sq(), sq(), sq(), Mat(), Mat(), Mat(ctx, n, m), Mat(ctx, n, m), Mat()};    // (Ros2: no K3, K4, V2)
+    const RosOperands<Mat> p{E, A, B, CtC};
     DevArr<double> part(ctx, 2 * NORM_PARTS);
     DevArr<StepCtl> ctl(ctx, 1);
     copy_mat(ctx, X0, X);
-    gemm(ctx, true, false, 1.0, C, C, 0.0, CtC, nullptr, "dense_ros");
-    // V = E'(K B) = (B'KE)'  (K symmetric)
-    auto EtKB = [&](const Mat& K, Mat& V) {
-        gemm(ctx, false, false, 1.0, K, B, 0.0, XB, nullptr, "dense_ros");
-        gemm(ctx, true, false, 1.0, E, XB, 0.0, V, nullptr, "dense_ros");
-    };
-    const Ros2Ops ros2{E, A, B, CtC, Acl, gF, T, AXE, Racc, Rs, XB, V1};
+    ops.gemm(true, false, 1.0, C, C, 0.0, CtC);
     // the result grows by chunks: a failed growth names the step
     Mat Kchunk, Xchunk;
     int kfill = ADAPT_K_CHUNK, xfill = ADAPT_X_CHUNK;
@@ -114,14 +110,13 @@ DenseAdaptiveResult dense_gdre_solve_adaptive(Ctx* ctx, const Mat& E, const Mat&
     auto feedback = [&](const Mat& Xs) {
         grow(Kchunk, kfill, m, ADAPT_K_CHUNK, "K(t)");
         Mat Kt = Kchunk.colsview(kfill++ * m, m);
-        EtKB(Xs, Kt);
+        ros_EtKB(ops, p, w, Xs, Kt);
         return Kt;
     };
     save(X);
     Mat Kt = feedback(X);
     out.Kt.push_back(Kt);
     out.t.push_back(t0);
-    const double gamma2 = 1.0 + 1.0 / std::sqrt(2.0);
     const double dirn = tf > t0 ? 1.0 : -1.0;
     auto clamp_h = [&](double h) { return std::min(std::max(h, sc.dt_min), sc.dt_max); };
     std::vector<double> stops = sc.tstops;
@@ -141,11 +136,11 @@ DenseAdaptiveResult dense_gdre_solve_adaptive(Ctx* ctx, const Mat& E, const Mat&
             throw Error(ERR_STEP, "adaptive dense path: more than max_steps = " + std::to_string(sc.max_steps) + " trial steps (t = " + std::to_string(t) +
                                       ", " + std::to_string(res.accepted) + " accepted, " + std::to_string(res.rejected) + " rejected)");
         // one Ros2 step of dense_gdre_solve from (X, Kt) with step tau, up to its last combination
-        ros2_stages(ctx, lyap, ros2, X, Kt, tau, gamma2, K1, K2, out.solves);
+        ros_stages(ops, order, tau, p, X, Kt, w);
         {
             TimedScope ts(ctx, "dense_step_error", 32.0 * n * n, 0.0);
-            hipLaunchKernelGGL(k_step_error, dim3(NORM_PARTS), dim3(256), 0, ctx->stream, n, (const double*)X.p, (const double*)K1.p, (const double*)K2.p,
-                               Xnew.p, tau / 2.0, (tau / 2.0) * (4.0 - 1.0 / gamma2), tau, sc.rtol, sc.atol, part.p);
+            hipLaunchKernelGGL(k_step_error, dim3(NORM_PARTS), dim3(256), 0, ctx->stream, n, (const double*)X.p, (const double*)w.K1.p, (const double*)w.K2.p,
+                               Xnew.p, ros2_weight_k2(tau), ros2_weight_k1(tau), tau, sc.rtol, sc.atol, part.p);
             hipLaunchKernelGGL(k_step_decide, dim3(1), dim3(256), 0, ctx->stream, NORM_PARTS, (const double*)part.p, (double)n * n, ctl.p);
         }
         const StepCtl c = read_back(ctx, ctl.p);

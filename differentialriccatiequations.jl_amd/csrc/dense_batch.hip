@@ -2,7 +2,7 @@
 //   gj_invert_batched        the register-panel Gauss-Jordan inversion of dense_gj.hip on a stack (the bodies are dense_gj_body.hpp's, shared with dense_gj.hip);
 //   BatchedSignLyap          SignLyap on a stack of pencils, the iteration's decisions taken per member on the device (the element-wise bodies
 //                            and the stopping rule are dense_sign_body.hpp's, shared with dense_sign.hip);
-//   dense_gdre_solve_batched Ros1 / Ros2 of dense_sign.hip on stacks.
+//   dense_gdre_solve_batched Ros1 / Ros2 on stacks: the stage program of dense_ros.hpp behind a stack back end, and what is this driver's own.
 // The strided MFMA GEMM is gemm_strided of gemm.hip.  A member's arithmetic never looks at B, at its position or at another member's data.
 #include "dense_batch.hpp"
 
@@ -10,6 +10,7 @@
 
 #include "dense.hpp"
 #include "dense_gj_body.hpp"
+#include "dense_ros.hpp"
 #include "dense_sign_body.hpp"
 #include "profiling.hpp"
 
@@ -250,6 +251,29 @@ void scomb(Ctx* ctx, int batch, Stk& out, double a0, const Stk& M0, double a1, c
     comb_batched(ctx, batch, out.r, out.c, out.m.p, a0, M0.m.p, a1, M1 ? M1->m.p : nullptr, a2, M2 ? M2->m.p : nullptr, sym, mask);
 }
 void scopy(Ctx* ctx, int batch, const Stk& src, Stk& dst, BatchMask mask) { scomb(ctx, batch, dst, 1.0, src, 0.0, nullptr, 0.0, nullptr, false, mask); }
+
+// The stack back end of the stage program dense_ros.hpp, for dense_gdre_solve_batched: sgemm with the tag "batch_dense_ros", scomb, scopy
+// and lyap's factor / solve.  mask goes to every launch (the driver sets it); solves collects one statistics vector per solve.
+struct StkRosOps {
+    using M = Stk;
+    Ctx* ctx;
+    int batch;
+    BatchedSignLyap& lyap;
+    BatchMask mask;
+    std::vector<std::vector<SignStats>> solves;       // per solve, per member
+    void gemm(bool tA, bool tB, double alpha, const Stk& A, const Stk& B, double beta, Stk& C) {
+        sgemm(ctx, batch, tA, tB, alpha, A, B, beta, C, mask, "batch_dense_ros");
+    }
+    void comb(Stk& out, double a0, const Stk& M0, double a1, const Stk* M1, double a2, const Stk* M2, bool sym) {
+        scomb(ctx, batch, out, a0, M0, a1, M1, a2, M2, sym, mask);
+    }
+    void copy(const Stk& src, Stk& dst) { scopy(ctx, batch, src, dst, mask); }
+    void factor(const Stk& F) { lyap.factor(F.m); }
+    void solve(const Stk& R, Stk& X) {
+        solves.emplace_back();
+        lyap.solve(R.m, X.m, solves.back());
+    }
+};
 }  // namespace
 
 BatchedSignLyap::BatchedSignLyap(Ctx* ctx, int batch, const Mat& E, int maxiters, double tol, int max_refine, size_t extra_n2)
@@ -415,87 +439,37 @@ void dense_gdre_solve_batched(Ctx* ctx, int batch, const Mat& E, const Mat& A, c
     const int n = E.rows, B = batch;
     DRE_REQUIRE(order == 1 || order == 2, "batched dense path: only Ros1 and Ros2 (order 1, 2) are batched; order = " + std::to_string(order) +
                                               " runs through the single-problem call");
-    DRE_REQUIRE(dt != 0.0 && std::isfinite(dt), "dense path: dt must be finite and nonzero");
-    const int nsteps = (int)std::floor((tf - t0) / dt + 1e-9);
-    DRE_REQUIRE(nsteps >= 0, "tspan and dt point in opposite directions");
-    std::vector<double> t;
-    for (int i = 0; i <= nsteps; ++i) t.push_back(t0 + i * dt);
+    const std::vector<double> t = dense_time_grid(t0, tf, dt);
+    const int nsteps = (int)t.size() - 1;
     require_memory(ctx, dense_gdre_batched_doubles(B, n, m, q, nsteps, order, save_state, maxiters));
     BatchedSignLyap lyap(ctx, B, E, maxiters, tol, max_refine, gdre_extra_n2(nsteps, save_state));
+    StkRosOps ops{ctx, B, lyap, BatchMask{}, {}};       // before the first factorisation every member takes part (K(t_0) needs no solve)
     const Stk Es(E, n, n), As(A, n, n), Bs(Bm, n, m), Cs(C, q, n), X0s(X0, n, n);
     auto sq = [&] { return Stk(ctx, B, n, n); };
-    Stk X = sq(), CtC = sq(), Acl = sq(), gF = sq(), T = sq(), AXE = sq(), Racc = sq(), Rs = sq(), K1 = sq(), K2 = sq();
-    Stk XB(ctx, B, n, m), V1(ctx, B, n, m);
-    const char* tag = "batch_dense_ros";
-    BatchMask all{};                      // before the first factorisation every member takes part (K(t_0) needs no solve)
-    BatchMask mk = all;
-    scopy(ctx, B, X0s, X, all);
-    sgemm(ctx, B, true, false, 1.0, Cs, Cs, 0.0, CtC, all, tag);
-    // V = E'(K B) = (B'KE)'  (K symmetric)
-    auto EtKB = [&](const Stk& K, Stk& V) {
-        sgemm(ctx, B, false, false, 1.0, K, Bs, 0.0, XB, mk, tag);
-        sgemm(ctx, B, true, false, 1.0, Es, XB, 0.0, V, mk, tag);
-    };
+    Stk X = sq(), CtC = sq();
+    RosWork<Stk> w{sq(), sq(), sq(), sq(), sq(), sq(), sq(), sq(), Stk(), Stk(), Stk(ctx, B, n, m), Stk(ctx, B, n, m), Stk()};   // (Ros1, Ros2: no K3, K4, V2)
+    const RosOperands<Stk> p{Es, As, Bs, CtC};
+    ops.copy(X0s, X);
+    ops.gemm(true, false, 1.0, Cs, Cs, 0.0, CtC);
     auto feedback = [&](const Stk& Xs) {
         Stk Kt(ctx, B, n, m);
-        EtKB(Xs, Kt);
+        ros_EtKB(ops, p, w, Xs, Kt);
         return Kt;
     };
-    auto sym_rhs = [&] { scomb(ctx, B, Rs, 1.0, Racc, 0.0, nullptr, 0.0, nullptr, true, mk); };
-    // Y = E' M E
-    auto EtME = [&](const Stk& M, Stk& Y) {
-        sgemm(ctx, B, false, false, 1.0, M, Es, 0.0, T, mk, tag);
-        sgemm(ctx, B, true, false, 1.0, Es, T, 0.0, Y, mk, tag);
-    };
     std::vector<Stk> Kts, Xsaved;
-    std::vector<std::vector<SignStats>> solves;       // per solve, per member
     std::vector<int> steps_done((size_t)B, 0);
-    auto save = [&](const Stk& Xs) { Stk c = sq(); scopy(ctx, B, Xs, c, mk); Xsaved.push_back(c); };
-    auto solve = [&](const Stk& Rsym, Stk& Xout) {
-        std::vector<SignStats> s;
-        lyap.solve(Rsym.m, Xout.m, s);
-        solves.push_back(std::move(s));
-    };
+    auto save = [&](const Stk& Xs) { Stk c = sq(); ops.copy(Xs, c); Xsaved.push_back(c); };
     save(X);
     Stk Kt = feedback(X);
     Kts.push_back(Kt);
-    mk = lyap.live();
-    const double gamma2 = 1.0 + 1.0 / std::sqrt(2.0);
+    ops.mask = lyap.live();
     for (int i = 1; i <= nsteps; ++i) {
         bool any = false;
         for (int b = 0; b < B; ++b) any = any || lyap.alive(b);
         if (!any) break;
         const double tau = t[(size_t)i - 1] - t[(size_t)i];
-        // Acl = A - B K
-        scopy(ctx, B, As, Acl, mk);
-        sgemm(ctx, B, false, true, -1.0, Bs, Kt, 1.0, Acl, mk, tag);
-        if (order == 1) {
-            scomb(ctx, B, gF, 1.0, Acl, -1.0 / (2.0 * tau), &Es, 0.0, nullptr, false, mk);         // F = (A - BK) - E/(2 tau)
-            lyap.factor(gF.m);
-            scopy(ctx, B, CtC, Racc, mk);                                                          // R = C'C + K'K + E'XE / tau
-            sgemm(ctx, B, false, true, 1.0, Kt, Kt, 1.0, Racc, mk, tag);
-            EtME(X, K2);
-            scomb(ctx, B, Rs, 1.0, Racc, 1.0 / tau, &K2, 0.0, nullptr, true, mk);
-            solve(Rs, X);
-        } else {
-            scomb(ctx, B, gF, gamma2 * tau, Acl, -0.5, &Es, 0.0, nullptr, false, mk);              // gF = gamma tau (A - BK) - E/2
-            lyap.factor(gF.m);
-            // R of the first stage: C'C + A'XE + E'XA - K'K
-            sgemm(ctx, B, false, false, 1.0, X, Es, 0.0, T, mk, tag);
-            sgemm(ctx, B, true, false, 1.0, As, T, 0.0, AXE, mk, tag);
-            scopy(ctx, B, CtC, Racc, mk);
-            sgemm(ctx, B, false, true, -1.0, Kt, Kt, 1.0, Racc, mk, tag);
-            scomb(ctx, B, Racc, 1.0, Racc, 2.0, &AXE, 0.0, nullptr, false, mk);
-            sym_rhs();
-            solve(Rs, K1);
-            EtKB(K1, V1);
-            EtME(K1, Racc);
-            scomb(ctx, B, Racc, -(2.0 - 1.0 / gamma2), Racc, 0.0, nullptr, 0.0, nullptr, false, mk);
-            sgemm(ctx, B, false, true, -tau * tau, V1, V1, 1.0, Racc, mk, tag);
-            sym_rhs();
-            solve(Rs, K2);
-            scomb(ctx, B, X, 1.0, X, tau / 2.0, &K2, (tau / 2.0) * (4.0 - 1.0 / gamma2), &K1, false, mk);   // X + tau/2 (Kt2 + (4 - 1/gamma) K1)
-        }
+        ros_stages(ops, order, tau, p, X, Kt, w);
+        ros_combine(ops, order, tau, X, w);
         for (int b = 0; b < B; ++b)
             if (lyap.alive(b)) steps_done[(size_t)b] = i;
         if (save_state) save(X);
@@ -520,7 +494,7 @@ void dense_gdre_solve_batched(Ctx* ctx, int batch, const Mat& E, const Mat& A, c
         } else if (done > 0) {
             r.X.push_back(X.m.colsview(b * n, n));      // (a failed member's X was not touched after its last completed step)
         }
-        for (int j = 0; j < done * per_step; ++j) r.solves.push_back(solves[(size_t)j][(size_t)b]);
+        for (int j = 0; j < done * per_step; ++j) r.solves.push_back(ops.solves[(size_t)j][(size_t)b]);
     }
 }
 

@@ -2,13 +2,14 @@
 //   SignLyap         generalized matrix-sign-function solver of F'XE + E'XF = -R (Benner & Quintana-Orti 1999) on the Gauss-Jordan
 //                    inversion of dense_gj.hip, with the (P_k, c_k) sequence kept for further right-hand sides and for iterative
 //                    refinement by replay;
-//   dense_gdre_solve the Rosenbrock drivers Ros1..Ros4, device resident.
+//   dense_gdre_solve the fixed-grid Rosenbrock driver Ros1..Ros4, device resident (the stage program itself: dense_ros.hpp).
 // The host model of exactly this iteration is tests/_sign_model.py.
 #include "dense_sign.hpp"
 
 #include <cmath>
 
 #include "dense.hpp"
+#include "dense_ros.hpp"
 #include "dense_sign_body.hpp"
 #include "profiling.hpp"
 
@@ -255,154 +256,63 @@ double SignLyap::residual_t(const Mat& R, const Mat& Y) {
 
 SignStats SignLyap::solve_t(const Mat& R, Mat& Y) { return solve_impl(true, R, Y); }
 
-// ---- Rosenbrock drivers (dense_ros{1,2,3,4}.jl of the reference) ------------------------------------------------
-void ros2_stages(Ctx* ctx, SignLyap& lyap, const Ros2Ops& o, const Mat& X, const Mat& Kt, double tau, double gamma, Mat& K1, Mat& K2,
-                 std::vector<SignStats>& solves) {
-    const char* tag = "dense_ros";
-    copy_mat(ctx, o.A, o.Acl);
-    gemm(ctx, false, true, -1.0, o.B, Kt, 1.0, o.Acl, nullptr, tag);                    // Acl = A - B K
-    comb(ctx, o.gF, gamma * tau, o.Acl, -0.5, &o.E);                                    // gF = gamma tau (A - BK) - E/2
-    lyap.factor(o.gF);
-    gemm(ctx, false, false, 1.0, X, o.E, 0.0, o.T, nullptr, tag);                       // R = C'C + A'XE + E'XA - K'K
-    gemm(ctx, true, false, 1.0, o.A, o.T, 0.0, o.AXE, nullptr, tag);
-    copy_mat(ctx, o.CtC, o.Racc);
-    gemm(ctx, false, true, -1.0, Kt, Kt, 1.0, o.Racc, nullptr, tag);
-    comb(ctx, o.Racc, 1.0, o.Racc, 2.0, &o.AXE);                                        // sym(R + 2 A'XE) below
-    comb(ctx, o.Rs, 1.0, o.Racc, 0.0, nullptr, 0.0, nullptr, true);
-    solves.push_back(lyap.solve(o.Rs, K1));
-    gemm(ctx, false, false, 1.0, K1, o.B, 0.0, o.XB, nullptr, tag);                     // V1 = E'(K1 B)
-    gemm(ctx, true, false, 1.0, o.E, o.XB, 0.0, o.V1, nullptr, tag);
-    gemm(ctx, false, false, 1.0, K1, o.E, 0.0, o.T, nullptr, tag);                      // E' K1 E
-    gemm(ctx, true, false, 1.0, o.E, o.T, 0.0, o.Racc, nullptr, tag);
-    comb(ctx, o.Racc, -(2.0 - 1.0 / gamma), o.Racc);
-    gemm(ctx, false, true, -tau * tau, o.V1, o.V1, 1.0, o.Racc, nullptr, tag);
-    comb(ctx, o.Rs, 1.0, o.Racc, 0.0, nullptr, 0.0, nullptr, true);
-    solves.push_back(lyap.solve(o.Rs, K2));
+// ---- Rosenbrock drivers (dense_ros{1,2,3,4}.jl of the reference): the stage program is dense_ros.hpp's ------------------------------
+void DenseRosOps::gemm(bool tA, bool tB, double alpha, const Mat& A, const Mat& B, double beta, Mat& C) {
+    dre::gemm(ctx, tA, tB, alpha, A, B, beta, C, nullptr, "dense_ros");
+}
+void DenseRosOps::comb(Mat& out, double a0, const Mat& M0, double a1, const Mat* M1, double a2, const Mat* M2, bool sym) {
+    dre::comb(ctx, out, a0, M0, a1, M1, a2, M2, sym);
+}
+void DenseRosOps::copy(const Mat& src, Mat& dst) { copy_mat(ctx, src, dst); }
+
+void dense_check_order(int order) { DRE_REQUIRE(order >= 1 && order <= 4, "dense path: order must be 1 .. 4"); }
+
+void dense_check_shapes(const char* who, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X0) {
+    const int n = E.rows;
+    DRE_REQUIRE(E.cols == n && A.rows == n && A.cols == n && B.rows == n && C.cols == n && X0.rows == n && X0.cols == n,
+                std::string(who) + ": E, A, X0 must be n x n, B n x m, C q x n");
+}
+
+std::vector<double> dense_time_grid(double t0, double tf, double dt) {
+    DRE_REQUIRE(dt != 0.0 && std::isfinite(dt), "dense path: dt must be finite and nonzero");
+    const int nsteps = (int)std::floor((tf - t0) / dt + 1e-9);
+    DRE_REQUIRE(nsteps >= 0, "tspan and dt point in opposite directions");
+    std::vector<double> t;
+    for (int i = 0; i <= nsteps; ++i) t.push_back(t0 + i * dt);
+    return t;
 }
 
 DenseGdreResult dense_gdre_solve(Ctx* ctx, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X0, double t0, double tf, double dt,
                                  int order, bool save_state, int maxiters, double tol, int max_refine) {
     const int n = E.rows, m = B.cols;
-    DRE_REQUIRE(order >= 1 && order <= 4, "dense path: order must be 1 .. 4");
-    DRE_REQUIRE(E.cols == n && A.rows == n && A.cols == n && B.rows == n && C.cols == n && X0.rows == n && X0.cols == n,
-                "dense path: E, A, X0 must be n x n, B n x m, C q x n");
-    DRE_REQUIRE(dt != 0.0 && std::isfinite(dt), "dense path: dt must be finite and nonzero");
-    const int nsteps = (int)std::floor((tf - t0) / dt + 1e-9);
-    DRE_REQUIRE(nsteps >= 0, "tspan and dt point in opposite directions");
+    dense_check_order(order);
+    dense_check_shapes("dense path", E, A, B, C, X0);
     DenseGdreResult out;
-    for (int i = 0; i <= nsteps; ++i) out.t.push_back(t0 + i * dt);
+    out.t = dense_time_grid(t0, tf, dt);
+    const int nsteps = (int)out.t.size() - 1;
     // the sign solver's own (maxiters + 10) n^2, the driver's matrices (16 n^2 for Ros4) and the saved states
     SignLyap lyap(ctx, E, maxiters, tol, max_refine, 16 + (save_state ? (size_t)nsteps : 1));
+    DenseRosOps ops{ctx, lyap, out.solves};
     auto sq = [&] { return Mat(ctx, n, n); };
-    Mat X = sq(), CtC = sq(), Acl = sq(), gF = sq(), T = sq(), AXE = sq(), Racc = sq(), Rs = sq(), K1 = sq(), K2 = sq(), K3 = sq(), K4 = sq();
-    Mat XB(ctx, n, m), V1(ctx, n, m), V2(ctx, n, m);
+    Mat X = sq(), CtC = sq();
+    RosWork<Mat> w{sq(), sq(), sq(), sq(), sq(), sq(), sq(), sq(), sq(), sq(), Mat(ctx, n, m), Mat(ctx, n, m), Mat(ctx, n, m)};
+    const RosOperands<Mat> p{E, A, B, CtC};
     copy_mat(ctx, X0, X);
-    gemm(ctx, true, false, 1.0, C, C, 0.0, CtC, nullptr, "dense_ros");
-    // V = E'(K B) = (B'KE)'  (K symmetric)
-    auto EtKB = [&](const Mat& K, Mat& V) {
-        gemm(ctx, false, false, 1.0, K, B, 0.0, XB, nullptr, "dense_ros");
-        gemm(ctx, true, false, 1.0, E, XB, 0.0, V, nullptr, "dense_ros");
-    };
+    ops.gemm(true, false, 1.0, C, C, 0.0, CtC);
     // Kt = (B'XE)' = E'XB
     auto feedback = [&](const Mat& Xs) {
         Mat Kt(ctx, n, m);
-        EtKB(Xs, Kt);
+        ros_EtKB(ops, p, w, Xs, Kt);
         return Kt;
     };
-    auto sym_rhs = [&] { comb(ctx, Rs, 1.0, Racc, 0.0, nullptr, 0.0, nullptr, true); };      // Rs = sym(Racc)
     auto save = [&](const Mat& Xs) { Mat c = sq(); copy_mat(ctx, Xs, c); out.X.push_back(c); };
-    // Y = E' M E
-    auto EtME = [&](const Mat& M, Mat& Y) {
-        gemm(ctx, false, false, 1.0, M, E, 0.0, T, nullptr, "dense_ros");
-        gemm(ctx, true, false, 1.0, E, T, 0.0, Y, nullptr, "dense_ros");
-    };
-    auto solve = [&](const Mat& Rsym, Mat& Xout) { out.solves.push_back(lyap.solve(Rsym, Xout)); };
     save(X);
     Mat Kt = feedback(X);
     out.Kt.push_back(Kt);
-    const double gamma2 = 1.0 + 1.0 / std::sqrt(2.0);
-    const Ros2Ops ros2{E, A, B, CtC, Acl, gF, T, AXE, Racc, Rs, XB, V1};
     for (int i = 1; i <= nsteps; ++i) {
         const double tau = out.t[(size_t)i - 1] - out.t[(size_t)i];
-        // Acl = A - B K (Ros2: the first of ros2_stages)
-        auto closed_loop = [&] {
-            copy_mat(ctx, A, Acl);
-            gemm(ctx, false, true, -1.0, B, Kt, 1.0, Acl, nullptr, "dense_ros");
-        };
-        // R of the first stage (Ros2..4): C'C + A'XE + E'XA - K'K
-        auto first_rhs = [&]() {
-            gemm(ctx, false, false, 1.0, X, E, 0.0, T, nullptr, "dense_ros");
-            gemm(ctx, true, false, 1.0, A, T, 0.0, AXE, nullptr, "dense_ros");
-            copy_mat(ctx, CtC, Racc);
-            gemm(ctx, false, true, -1.0, Kt, Kt, 1.0, Racc, nullptr, "dense_ros");
-            comb(ctx, Racc, 1.0, Racc, 2.0, &AXE);        // sym(R + 2 A'XE) = C'C + A'XE + E'XA - K'K
-            sym_rhs();
-        };
-        if (order == 1) {
-            closed_loop();
-            comb(ctx, gF, 1.0, Acl, -1.0 / (2.0 * tau), &E);                                 // F = (A - BK) - E/(2 tau)
-            lyap.factor(gF);
-            copy_mat(ctx, CtC, Racc);                                                        // R = C'C + K'K + E'XE / tau
-            gemm(ctx, false, true, 1.0, Kt, Kt, 1.0, Racc, nullptr, "dense_ros");
-            EtME(X, K2);
-            comb(ctx, Rs, 1.0, Racc, 1.0 / tau, &K2, 0.0, nullptr, true);
-            solve(Rs, X);
-        } else if (order == 2) {
-            ros2_stages(ctx, lyap, ros2, X, Kt, tau, gamma2, K1, K2, out.solves);
-            comb(ctx, X, 1.0, X, tau / 2.0, &K2, (tau / 2.0) * (4.0 - 1.0 / gamma2), &K1);  // X + tau/2 (Kt2 + (4 - 1/gamma) K1)
-        } else if (order == 3) {
-            const double g = 7.886751345948129e-1, a21 = 1.267949192431123;
-            const double c21 = -1.607695154586736, c31 = -3.464101615137755, c32 = -1.732050807568877;
-            const double m1 = 2.0, m2 = 5.773502691896258e-1, m3 = 4.226497308103742e-1;
-            closed_loop();
-            comb(ctx, gF, 1.0, Acl, -1.0 / (2.0 * g * tau), &E);                            // gF = (A - BK) - E/(2 gamma tau)
-            lyap.factor(gF);
-            first_rhs();
-            solve(Rs, K1);
-            gemm(ctx, false, false, 1.0, K1, E, 0.0, T, nullptr, "dense_ros");              // RX = (A - BK)' K1 E
-            gemm(ctx, true, false, 1.0, Acl, T, 0.0, AXE, nullptr, "dense_ros");
-            EtME(K1, Racc);
-            comb(ctx, Rs, 2.0 * a21, AXE, c21 / tau, &Racc, 0.0, nullptr, true);           // sym(a21 (RX + RX') + c21/tau E'K1E)
-            solve(Rs, K2);                                                                   // K21
-            comb(ctx, K3, (c31 + c32) / tau, K1, c32 / tau, &K2);
-            EtME(K3, Racc);
-            comb(ctx, Rs, 2.0 * a21, AXE, 1.0, &Racc, 0.0, nullptr, true);
-            solve(Rs, K3);                                                                   // K31
-            comb(ctx, X, 1.0, X, m1 + m2 + m3, &K1, m2, &K2);
-            comb(ctx, X, 1.0, X, m3, &K3);
-        } else {
-            closed_loop();
-            comb(ctx, gF, tau / 2.0, Acl, -0.5, &E);                                         // gF = (tau (A - BK) - E)/2
-            lyap.factor(gF);
-            first_rhs();
-            solve(Rs, K1);
-            Mat EK1E = AXE;                                                                  // (A'XE is dead from here on)
-            EtME(K1, EK1E);
-            EtKB(K1, V1);
-            comb(ctx, Racc, -2.0, EK1E);
-            gemm(ctx, false, true, -tau * tau, V1, V1, 1.0, Racc, nullptr, "dense_ros");
-            sym_rhs();
-            solve(Rs, K2);                                                                   // K21
-            comb(ctx, K2, 1.0, K2, -1.0, &K1);                                               // K2 = K21 - K1
-            const double al = (24.0 / 25.0) * tau, be = (3.0 / 25.0) * tau;
-            EtME(K2, K4);                                                                    // EK2E (in K4 until K4 is formed)
-            EtKB(K2, V2);
-            comb(ctx, Racc, 245.0 / 25.0, EK1E, 36.0 / 25.0, &K4);
-            gemm(ctx, false, true, -(426.0 / 625.0) * tau * tau, V1, V1, 1.0, Racc, nullptr, "dense_ros");
-            gemm(ctx, false, true, -be * be, V2, V2, 1.0, Racc, nullptr, "dense_ros");
-            gemm(ctx, false, true, -2.0 * al * be, V2, V1, 1.0, Racc, nullptr, "dense_ros");   // -al be (TMP + TMP') under sym
-            sym_rhs();
-            solve(Rs, K3);                                                                   // K31
-            comb(ctx, K3, 1.0, K3, -17.0 / 25.0, &K1);                                       // K3 = K31 - 17/25 K1
-            comb(ctx, Racc, -981.0 / 125.0, EK1E, -177.0 / 125.0, &K4);
-            EtME(K3, Rs);
-            comb(ctx, Racc, 1.0, Racc, -0.2, &Rs);
-            sym_rhs();
-            solve(Rs, K4);                                                                   // K41
-            comb(ctx, K4, 1.0, K4, 1.0, &K3);                                                // K4 = K41 + K3
-            comb(ctx, X, 1.0, X, tau * 19.0 / 18.0, &K1, tau * 0.25, &K2);
-            comb(ctx, X, 1.0, X, tau * 25.0 / 216.0, &K3, tau * 125.0 / 216.0, &K4);
-        }
+        ros_stages(ops, order, tau, p, X, Kt, w);
+        ros_combine(ops, order, tau, X, w);
         if (save_state) save(X);
         Kt = feedback(X);
         out.Kt.push_back(Kt);

@@ -71,12 +71,25 @@ class SignLyap {
 // of the singular Z_k; dist: the last ||Z + E|| / ||E||.
 std::string sign_failure(int done, int k, double dist, int maxiters);
 
-// The stages of one Ros2 step from (X, Kt) with step tau, from Acl = A - BK through the solve for K2, for dense_gdre_solve (order 2) and
-// dense_gdre_solve_adaptive; the caller does its own last combination of X, K1 and K2.  o: the operands and the driver's work matrices
-// (n x n; XB, V1 n x m); both solves' statistics are appended to solves.
-struct Ros2Ops { const Mat &E, &A, &B, &CtC; Mat &Acl, &gF, &T, &AXE, &Racc, &Rs, &XB, &V1; };
-void ros2_stages(Ctx* ctx, SignLyap& lyap, const Ros2Ops& o, const Mat& X, const Mat& Kt, double tau, double gamma, Mat& K1, Mat& K2,
-                 std::vector<SignStats>& solves);
+// The single-problem back end of the stage program dense_ros.hpp, for dense_gdre_solve and dense_gdre_solve_adaptive: gemm with the tag
+// "dense_ros", comb, copy_mat and lyap's factor / solve; the statistics of every solve are appended to solves.
+struct DenseRosOps {
+    using M = Mat;
+    Ctx* ctx;
+    SignLyap& lyap;
+    std::vector<SignStats>& solves;
+    void gemm(bool tA, bool tB, double alpha, const Mat& A, const Mat& B, double beta, Mat& C);
+    void comb(Mat& out, double a0, const Mat& M0, double a1, const Mat* M1, double a2, const Mat* M2, bool sym);
+    void copy(const Mat& src, Mat& dst);
+    void factor(const Mat& F) { lyap.factor(F); }
+    void solve(const Mat& R, Mat& X) { solves.push_back(lyap.solve(R, X)); }
+};
+
+// The argument checks the dense drivers share, each in front of any device work: the order, the operands' shapes (who: "dense path",
+// "adaptive dense path"), and the fixed grid t0, t0 + dt, .. of floor((tf - t0) / dt) steps (dt finite, nonzero and pointing from t0 to tf).
+void dense_check_order(int order);
+void dense_check_shapes(const char* who, const Mat& E, const Mat& A, const Mat& B, const Mat& C, const Mat& X0);
+std::vector<double> dense_time_grid(double t0, double tf, double dt);
 
 struct DenseGdreResult {
     std::vector<double> t;
