@@ -740,7 +740,7 @@ int dre_sym_eig_probe(dre_ctx* ctx, const dre_dense* S, double tolfac, int want_
 }
 // ---- dre_adi_chain_probe: the dense-inverse ADI chain on caller-supplied operands (test and diagnostic surface) ----------------------------
 // Every launch goes through adi_fast_build, adi_fast_pack_r, adi_fast_iter, adi_group_pack or adi_group_iter; the loops are those of adi_advance
-// (engine.hip, fast branch) and of the dense-X time loop (gdre.hip, group branch).
+// (engine.hip, fast branch) and of the dense-X time loop (dense_x.hip, group branch).
 int dre_adi_chain_probe(dre_ctx* ctx, const dre_adi_chain_probe_args* args) {
     return guarded(ctx, [&] {
         DRE_REQUIRE(args, "dre_adi_chain_probe: null argument");

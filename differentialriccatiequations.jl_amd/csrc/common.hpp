@@ -164,7 +164,7 @@ struct Ctx {
     // Ros1, n <= 1536, no save_state: X is carried as "compressed warm start + ADI increments"; its compression runs on a second stream
     // beside the next time step (x_side_stream) or only every x_compress_every-th step (gdre.hip, gdre_solve)
     // Ros1 without save_state, real Cyclic shifts, n <= dense_x_max_n: X is carried as a dense symmetric n x n matrix between the time steps
-    // (gdre.hip, ros1_dense_step); 0 disables
+    // (dense_x.hip, ros1_dense_step); 0 disables
     int dense_x_max_n = 1536;
     // residual factors wider than this leave the dense-X loop for the factored path (0: the fast chain's own limit ADI_FAST_MAX_K); also the
     // switch the tests use to force that fallback in the middle of a run
@@ -172,7 +172,7 @@ struct Ctx {
     // a run that ends on the dense-X path hands its last X to the result as the dense matrix; the LDL' form (a band reduction of the full
     // n x n matrix, nothing K(t) depends on) is produced when a caller asks for that X (gdre.hip, gdre_result_x); 0: inside the solve
     int final_x_lazy = 1;
-    // group chain of the dense-X loop (dense.hip k_adi_group, gdre.hip group_ops_prepare): g ADI iterations per launch.  1 = auto (largest
+    // group chain of the dense-X loop (dense.hip k_adi_group, adi_cycle.hip group_ops_prepare): g ADI iterations per launch.  1 = auto (largest
     // divisor of the cycle length up to 5), 0 = off (one launch per iteration), g >= 2 = that group size if it divides the cycle length
     int adi_group = 1;
     int adi_group_max_n = 768;
@@ -207,7 +207,7 @@ struct Ctx {
     int recurrence_wide = 1;    // residual-recurrence loop: the increments of a solve may exceed the factor-form limit (c + 64 <= n); 0: round 4's in-loop compression
     int side_gate = 0;          // residual-recurrence loop: the parked thread enqueues the side stream only while the time loop's thread waits (launch gate below; measured at n = 5177: 85.1 ms with, 85.4 ms without — inside the noise, off)
     int side_prefetch = 0;      // (measured at n = 371: 18.3 against 17.8 ms per solve — the join in front of the chain costs more than the earlier start gains)
-    // dense-inverse path: factorisations, explicit inverses and stacks of a whole Cyclic list in shared launches (gdre.hip, cycle_setup_batched)
+    // dense-inverse path: factorisations, explicit inverses and stacks of a whole Cyclic list in shared launches (adi_cycle.hip, cycle_setup_batched)
     int setup_batched = 1;
     int xwarm_sx = 0;          // residual-recurrence loop: fresh sketch columns of the warm-started compression of X on the side stream (0 = by configuration: gdre.hip)
     // self-generated shift lists: the upcoming factorisations that are not in flight yet go out in shared launches (engine.hip, prefetch_ahead)
@@ -220,7 +220,7 @@ struct Ctx {
     std::unique_ptr<Ctx> side;
     hipEvent_t side_e1 = nullptr, side_e2 = nullptr;
     // helper contexts (own stream and pool each) for independent chains of small kernels that would otherwise queue up behind each other
-    // on one stream — the factorisations and dense inverses of the shifts of a cycle (gdre.hip, cycle_ops_prepare); created on first use
+    // on one stream — the factorisations and dense inverses of the shifts of a cycle (adi_cycle.hip, cycle_ops_prepare); created on first use
     std::vector<std::unique_ptr<Ctx>> helpers;
     std::vector<hipEvent_t> helper_ev;
     hipEvent_t helper_e0 = nullptr;
@@ -241,10 +241,10 @@ struct Ctx {
     std::shared_ptr<LaunchGate> gate;          // main context: owner;  side context: follower when gate_follow
     bool gate_follow = false;
     int gate_patience_us = 300;
-    // parked host threads of the time loops (gdre.hip, SideWorker): kept with the context — a thread per solve cost ~0.1 ms of creation and join
+    // parked host threads of the time loops (side_worker.hpp, SideWorker): kept with the context — a thread per solve cost ~0.1 ms of creation and join
     std::shared_ptr<void> parked_worker[3];
     std::shared_ptr<struct Buf> warm_tickets;    // arrival counters of the warm-started compression's ticket kernels (warm.hip), zeroed once
-    void* dense_land = nullptr;        // pinned landing zone of the dense-X time loop (gdre.hip, DenseXState): allocated once per context
+    void* dense_land = nullptr;        // pinned landing zone of the dense-X time loop (dense_x.hip, DenseXState): allocated once per context
     FetchZone* fetch_dev = nullptr;    // the same memory as the device sees it
     unsigned long long fetch_seq = 0;
     bool fetch_spin = true;            // false: ctx_fetch blocks in hipStreamSynchronize instead of spinning (the side context: its driver thread must not burn a core beside the main thread)

@@ -1351,7 +1351,7 @@ void adi_fast_iter(Ctx* ctx, const AdiFastArgs& a) {
 // Group ADI chain (round 3): g consecutive ADI iterations in ONE launch.
 //   R_i = Pi_i R_0,  V_i = Om_i R_0   with  Pi_i = P_{p+i-1} ... P_p,  P_s = I - 2 mu_s E' A_s,  Om_i = A_{p+i} Pi_i,  A_s = (F' + mu_s E')^-1
 // (perform_single_step!, adi.jl:149-179, applied g times: same iterates, the operator products are formed once per time step on the side
-// stream — gdre.hip, group_ops_prepare).  The launch-per-iteration chain at n = 371 is bound by the dependent kernel boundary and the
+// stream — adi_cycle.hip, group_ops_prepare).  The launch-per-iteration chain at n = 371 is bound by the dependent kernel boundary and the
 // memory round trips of a 6-us kernel, not by its 32 MFLOP; the group stack [Om_0 .. Om_{g-1}; Pi_1 .. Pi_g] (2 g blocks of n x n, packed in
 // the MFMA A-operand order like the single-iteration stack) turns g of those launches into one with 2 g times the tile workgroups.
 // Riders: the Gram matrices of the g residuals the PREVIOUS launch produced, and the norms + decisions (adi.jl:115-123, taken in iteration

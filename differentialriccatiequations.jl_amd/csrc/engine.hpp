@@ -203,7 +203,7 @@ struct GdreProblem {
     LDLtP X0;
     double t0 = 0, tf = 0;
 };
-// Final X of a run that ended on the dense-X path (gdre.hip, ros1_dense_step) with the option final_x_lazy: the dense symmetric matrix as the
+// Final X of a run that ended on the dense-X path (dense_x.hip, ros1_dense_step) with the option final_x_lazy: the dense symmetric matrix as the
 // time loop left it.  The result shares ownership of the buffer (it cannot go back to the pool while the result lives); the LDL' form is
 // produced by the first gdre_result_x that asks for it, on the stream of the context the solve ran on, and kept.
 struct FinalXDense {

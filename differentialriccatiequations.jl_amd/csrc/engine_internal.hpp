@@ -1,7 +1,7 @@
 // Declarations shared by the three translation units of the low-rank engine (not part of the interface in engine.hpp):
 //   ldlt.hip    LDL' objects, compress!, norms, the Lyapunov / Riccati residuals        (src/LDLt.jl, src/lyapunov/residual.jl)
 //   engine.hip  Sherman-Morrison-Woodbury pieces, shift strategies, factor cache, the ADI (src/lyapunov/adi.jl, src/shifts/*.jl, src/blocklinear/*.jl)
-//   gdre.hip    Rosenbrock drivers: dense-X loop, residual-recurrence loop, gdre_solve   (src/riccati/lowrank_ros1.jl, lowrank_ros2.jl)
+//   gdre.hip    Rosenbrock drivers: residual-recurrence loop, gdre_solve (dense-X step: dense_x.hip, adi_cycle.hip)   (src/riccati/lowrank_ros1.jl, lowrank_ros2.jl)
 #pragma once
 #include "engine.hpp"
 

@@ -1744,7 +1744,7 @@ __global__ void k_extract_band(int J, int b, int kred, const double* __restrict_
 struct BandTolJob { const double* parts; int nparts; double reltol, abstol, frac; double* out; };
 __global__ __launch_bounds__(64) void k_band_init(AdiState* st, double abs_tol, const double* __restrict__ abs_tol_dev, int floor_mode, BandTolJob job) {
     double at_dev = 0.0;
-    if (job.parts) {       // tolerances of the dense time loop's Lyapunov solve (gdre.hip, ros1_dense_step): adi.jl:61-62
+    if (job.parts) {       // tolerances of the dense time loop's Lyapunov solve (dense_x.hip, ros1_dense_step): adi.jl:61-62
         double s = 0.0;
         for (int i = threadIdx.x; i < job.nparts; i += 64) s += job.parts[i];
         s = wave_sum(s);

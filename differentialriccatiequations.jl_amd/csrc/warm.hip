@@ -1,4 +1,4 @@
-// Warm-started compression of the DENSE Riccati residual of the dense-X time loop (gdre.hip, ros1_dense_step): round 5.
+// Warm-started compression of the DENSE Riccati residual of the dense-X time loop (dense_x.hip, ros1_dense_step): round 5.
 //
 // The reference compresses the warm-start residual of every Lyapunov solve from scratch (lyapunov/residual.jl:3-31 -> compress!, LDLt.jl:204-225).
 // Rounds 1-4 did the same on the device: a two-sided band reduction of the n x n matrix Res, 3 dependent launches per 16 columns of rank

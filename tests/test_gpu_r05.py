@@ -208,7 +208,7 @@ def test_recurrence_with_and_without_the_factor_form_limit(ctx, wide):          
         assert np.linalg.norm(K @ w - g["K_w"][i]) <= 1e-7 * np.linalg.norm(g["K_w"][i]), i
 
 
-def test_one_step_runs_leave_no_worker_job_behind(ctx, rail371):          # gdre.hip: WorkerJoin (found by tools/option_matrix.sh, round 5)
+def test_one_step_runs_leave_no_worker_job_behind(ctx, rail371):          # dense_x.hip: ~DenseXState (found by tools/option_matrix.sh, round 5)
     """A run of ONE time step on the dense-X path: its first dense step used to hand the K-independent base of the group chain to the parked worker
     thread 'for the next step to join' — there is none, the worker outlives the solve (it lives with the context) and went on reading the dead
     frame: a heap corruption that surfaced in a later, unrelated call.  Thirty such runs in a row, each followed by host allocations, must give the
