@@ -102,12 +102,7 @@ static void cycle_setup_batched(Ctx* ctx, const GaleOperator& op, const std::vec
     const Pencil& P = *op.P;
     const int n = P.n, mm = op.has_lr ? op.U.cols : 0;
     if (!cache->enabled || !P.use_mfma_sweeps || n > ctx->dense_inv_max_n || ctx->setup_batched <= 0) return;
-    std::vector<double> todo;
-    for (auto& mu : values) {
-        bool dup = cache->real.count(std::make_tuple(op.tag, mu.real(), 0.0)) > 0;
-        for (double t : todo) dup = dup || t == mu.real();
-        if (!dup && (int)todo.size() < MF_ZMAX) todo.push_back(mu.real());
-    }
+    const std::vector<double> todo = distinct_real_shifts(values, MF_ZMAX, [&](size_t, double mu) { return cache->real.count(std::make_tuple(op.tag, mu, 0.0)) > 0; });
     const int g = (int)todo.size();
     if (g < 2) return;
     std::vector<std::shared_ptr<FactorEntry<double>>> fes;
@@ -168,15 +163,8 @@ bool cycle_ops_prepare(Ctx* ctx, const GaleOperator& op, const std::vector<std::
         for (auto& mu : values) if (!cache->enabled || !cache->real.count(std::make_tuple(op.tag, mu.real(), mu.imag()))) ++todo;
         const int nh = (cache->enabled && todo > 1) ? std::min(todo, std::max(0, ctx->setup_streams)) : 0;
         if (nh > 1) {
-            while ((int)ctx->helpers.size() < nh) {
-                auto hc = std::make_unique<Ctx>();
-                hc->device = ctx->device; hc->num_cus = ctx->num_cus;
-                hc->stream = create_stream(2);
-                hc->timer = std::make_unique<KernelTimer>();
-                hipEvent_t ev;
-                DRE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                ctx->helpers.push_back(std::move(hc)); ctx->helper_ev.push_back(ev);
-            }
+            helpers_grow(ctx, nh);
+            // (the look-ahead of the ADI, engine.hip Prefetcher::next_helper, also copies pivot_static onto its helpers; this list does not)
             if (!ctx->helper_e0) DRE_HIP(hipEventCreateWithFlags(&ctx->helper_e0, hipEventDisableTiming));
             DRE_HIP(hipEventRecord(ctx->helper_e0, ctx->stream));         // the operator's value arrays are ready here
             for (int h = 0; h < nh; ++h) {

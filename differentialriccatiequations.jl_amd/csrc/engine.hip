@@ -718,29 +718,6 @@ std::vector<std::complex<double>> heuristic_shift_values(Ctx* ctx, const GaleOpe
 // product + one decision launch for the group).  The coefficients grow when shifts of a group are close (~ mu / delta mu per pair): groups are cut so that max_j sum_s |c_js| stays
 // below fan_max_coef (the products W_s are accurate to ~eps cond, the combination amplifies that by the coefficient sum).
 // =============================================================================================
-static double fan_coefficients(const double* mu, int g, FanCoef* out) {
-    long double c[FAN_GMAX][FAN_GMAX] = {{0}}, d[FAN_GMAX][FAN_GMAX] = {{0}};
-    double worst = 0.0;
-    for (int j = 0; j < g; ++j) {
-        long double sum = 0.0L;
-        for (int s = 0; s <= j; ++s) {
-            long double num = 1.0L, den = 1.0L;
-            for (int i = 0; i < j; ++i) num *= -(long double)mu[s] - (long double)mu[i];
-            for (int i = 0; i <= j; ++i) if (i != s) den *= (long double)mu[i] - (long double)mu[s];
-            c[j][s] = num / den;
-            sum += fabsl(c[j][s]);
-        }
-        worst = std::max(worst, (double)sum);
-    }
-    for (int j = 0; j < g; ++j)
-        for (int s = 0; s <= j; ++s) {
-            long double acc = 0.0L;
-            for (int i = s; i <= j; ++i) acc += 2.0L * (long double)mu[i] * c[i][s];
-            d[j][s] = acc;
-        }
-    for (int j = 0; j < FAN_GMAX; ++j) for (int s = 0; s < FAN_GMAX; ++s) { out->c[j][s] = (double)c[j][s]; out->d[j][s] = (double)d[j][s]; }
-    return worst;
-}
 // SMW of the g solves of a fan group in one launch (blockIdx.z = solve): W_z <- W_z - W_U,z (Sinv_z small_z) in place;  W_z / small_z = columns
 // z k .. of the n x (g k) panel / of small = U' W  (smw.jl:36-43)
 struct SmwZ { const double* WU[MF_ZMAX]; const double* Sinv[MF_ZMAX]; int ldwu[MF_ZMAX]; };
@@ -781,9 +758,9 @@ __global__ __launch_bounds__(64) void k_sinv_z(int m, const double* __restrict__
     if (st && st->done) return;
     sinv_body<double>(m, small + (size_t)blockIdx.x * m * lds_, lds_, alpha, iz.out[blockIdx.x], err);
 }
-// helper context h of a context (own stream and pool), created on first use
-Ctx* helper_ctx(Ctx* ctx, int h) {
-    while ((int)ctx->helpers.size() <= h) {
+// at least nh helper contexts of a context (own stream, pool and event each), created on first use
+void helpers_grow(Ctx* ctx, int nh) {
+    while ((int)ctx->helpers.size() < nh) {
         auto hc = std::make_unique<Ctx>();
         hc->device = ctx->device; hc->num_cus = ctx->num_cus;
         hc->stream = create_stream(2);
@@ -792,6 +769,10 @@ Ctx* helper_ctx(Ctx* ctx, int h) {
         DRE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         ctx->helpers.push_back(std::move(hc)); ctx->helper_ev.push_back(ev);
     }
+}
+// helper context h of a context, with the timer switch and the swizzles of its parent
+Ctx* helper_ctx(Ctx* ctx, int h) {
+    helpers_grow(ctx, h + 1);
     Ctx* hc = ctx->helpers[(size_t)h].get();
     hc->timer->enabled = ctx->timer && ctx->timer->enabled;
     hc->gemm_swizzle = ctx->gemm_swizzle; hc->mf_swizzle = ctx->mf_swizzle;
@@ -839,7 +820,67 @@ void zero_increment_guard(Ctx* ctx, const Mat& V1, const Mat& V2, AdiState* st, 
     hipLaunchKernelGGL(k_zero_increment, dim3(nb), dim3(256), 0, ctx->stream, tot, V1.rows, V1.cols, (const double*)V1.p, V1.ld, (const double*)V2.p, V2.ld, st, nshifts);
     DRE_HIP(hipGetLastError());
 }
-struct StepRec { int iters_after; size_t nblocks; int nshifts; Mat Rafter; };      // Rafter: the residual factor after this iteration where it is NOT updated in place (fan groups)
+static bool trace_prefetch() { static const bool on = env_trace("prefetch"); return on; }
+typedef std::map<std::tuple<uint64_t, double, double>, std::shared_ptr<FactorEntry<double>>> RealStore;
+// Factorises the shifts `mus`, none of which has a factor yet, in shared launches on `where` (sparse.hip, mf_factor_batch: one launch per tree
+// level for the whole list) and enters them into the cache as fresh factors.  allow_topinv: 1 / 0 sets Factor::allow_topinv, -1 leaves it.
+template <typename T>
+static std::vector<std::shared_ptr<FactorEntry<T>>> factor_batch_into_cache(Ctx* where, const GaleOperator& op, FactorCache* cache,
+                                                                             std::map<std::tuple<uint64_t, double, double>, std::shared_ptr<FactorEntry<T>>>& store,
+                                                                             const std::vector<std::complex<double>>& mus, int allow_topinv) {
+    const Pencil& P = *op.P;
+    std::vector<std::shared_ptr<FactorEntry<T>>> fes;
+    std::vector<Factor<T>*> fp;
+    std::vector<T> ce;
+    for (auto& t : mus) { fes.push_back(std::make_shared<FactorEntry<T>>()); fp.push_back(&fes.back()->f); ce.push_back(make_scalar<T>(t.real(), t.imag())); }
+    mf_factor_batch<T>(where, P, op.valFt.p, P.valEt.p, make_scalar<T>(1.0, 0.0), ce.data(), fp.data(), (int)mus.size());
+    for (size_t z = 0; z < mus.size(); ++z) {
+        if (allow_topinv >= 0) fes[z]->f.allow_topinv = allow_topinv != 0;
+        const auto key = std::make_tuple(op.tag, mus[z].real(), std::is_same<T, double>::value ? 0.0 : mus[z].imag());
+        store[key] = fes[z]; cache->fresh.push_back(key); cache->nfactor++;
+    }
+    return fes;
+}
+static std::vector<std::complex<double>> as_complex(const std::vector<double>& v) { return std::vector<std::complex<double>>(v.begin(), v.end()); }
+
+struct AdiRun;
+// Single-use factors (Projection / per-solve Heuristic shifts) and the first pass through a Cyclic list on the multifrontal path: factorised
+// AHEAD on the helper streams while the current iteration solves (all shifts of a batch are known at once and their factorisations are
+// independent), checked lazily with their chunk.  Owns the events of the factorisations in flight.
+struct Prefetcher {
+    AdiRun& run;
+    std::map<std::pair<double, double>, hipEvent_t> in_flight;     // factor of this shift is being made on a helper stream: wait for the event before use
+    std::vector<hipEvent_t> ev_pool;
+    size_t rr = 0;
+    bool helpers_ready = false;
+    explicit Prefetcher(AdiRun& r) : run(r) {}
+    ~Prefetcher();
+    bool pending(std::complex<double> mu) const { return in_flight.count({mu.real(), mu.imag()}) > 0; }
+    hipEvent_t take_event();
+    void wait(std::complex<double> mu);
+    void wait_all();
+    void ahead(std::complex<double> cur, bool fan_call = false);
+private:
+    Ctx* next_helper(int nh);
+    void mark(Ctx* hc, std::complex<double> nx);
+    bool known(std::complex<double> mu) const;
+    void batch_ahead(const std::vector<std::complex<double>>& ups, std::complex<double> cur, bool fan_call, int nh);
+};
+typedef std::map<std::pair<double, double>, SmwCacheEntry> SmwCache;
+struct FanGroup;
+// What one call of adi_advance (outside the fast chain) enqueued speculatively since the last synchronisation, and what to go back to.
+struct AdiChunk {
+    ChunkLedger<Mat> ledger;          // payload: the residual factor after this iteration where it is NOT updated in place (fan groups)
+    int budget = 0, limit = 0;        // the caller's budget; the chunk length (< 512: ring of the norm history)
+    int lc_before = 0, iters_start = 0;
+    Mat R_start;
+    Mat hist_V, hist_R;               // keep_history: the chunk's V_j and R_j side by side
+    int since_sync = 0, shifts = 0;
+    std::chrono::steady_clock::time_point t0;
+    bool full(const AdiOptions& opt) const { return opt.compression ? shifts >= limit : since_sync >= std::min(10, limit); }
+};
+// The solver object of one Lyapunov solve: the frame of adi_begin (one member function per phase, in the order of the call), of adi_advance
+// (the fast-chain chunk, or a chunk of fan groups / real steps / complex pairs with its close) and of adi_finish.
 struct AdiRun {
     Ctx* ctx = nullptr;
     GaleOperator op;
@@ -855,7 +896,7 @@ struct AdiRun {
     std::unique_ptr<ShiftOracle> oracle;
     DevArr<AdiState> st;
     AdiState h0;
-    std::map<std::pair<double, double>, SmwCacheEntry> smw_cache;
+    SmwCache smw_cache;
     std::shared_ptr<LDLt> Xw;
     int iters_host = 0, last_compression = 0, chunk_limit = 10;
     std::vector<std::complex<double>> all_shifts;
@@ -875,14 +916,8 @@ struct AdiRun {
     // factorisation kernels only); the handles are dropped then, so single-use factors are freed chunk by chunk
     double max_growth = 0.0;         // largest pivot growth among the factorisations this solve used
     LDLt Crhs;                       // the right-hand side (shallow copy) for the true-residual verification after a growth warning
-    // single-use factors (Projection / per-solve Heuristic shifts): factorised AHEAD on the helper streams while the current iteration solves
-    // (all shifts of a batch are known at once and their factorisations are independent), checked lazily with their chunk
-    struct Prefetched { hipEvent_t ev; long ticket; };
-    std::map<std::pair<double, double>, Prefetched> prefetch_ev;     // factor of this shift is being made on a helper stream: wait for the event before use
-    std::vector<hipEvent_t> ev_pool;
+    Prefetcher pf{*this};
     bool check_now = false;           // a lazily checked factor turned out to have replaced pivots: from now on every new factor is checked at once
-    size_t prefetch_rr = 0;
-    bool helpers_ready = false;
     bool chunk_from_hint = false;
     hipEvent_t tol_event = nullptr;   // the tolerance is being formed on a helper stream: wait for this event, then decide iteration 0 (apply_tolerance)
     bool abstol_pending = false;      // the tolerance was formed on the device (AdiOptions::normC_build): the host copy follows with the first chunk
@@ -891,73 +926,278 @@ struct AdiRun {
     bool hist_ok = true;
     bool fan_off = false;             // the batched fan form does not apply to this solve's factors (sparse.hip, mf_solve_batch): one iteration at a time
     bool fan_smw_all = false;         // the SMW products of every cached shift of the cycle were formed with the first group's
-    void check_used() {
-        {   // the unchecked real factors with ONE synchronisation (the ten factorisations of a freshly factorised cycle: ten read-backs before)
-            std::vector<const Factor<double>*> fs; std::vector<FactorEntry<double>*> es;
-            for (auto& f : used_real) {
-                bool seen = false;
-                for (auto* e : es) seen = seen || e == f.get();
-                if (!f->checked && !seen) { fs.push_back(&f->f); es.push_back(f.get()); }
-            }
-            if (fs.size() >= 2) {
-                const std::vector<double> gr = mf_check_batch(ctx, fs);
-                for (size_t i = 0; i < es.size(); ++i) {
-                    es[i]->growth = gr[i]; es[i]->checked = true;
-                    if (es[i]->f.nperturbed > 0) { check_now = true; max_growth = std::max(max_growth, 1e300); }
-                }
-            }
-        }
-        for (auto& f : used_real) {
-            if (!f->checked) { f->growth = mf_check(ctx, f->f); f->checked = true; if (f->f.nperturbed > 0) { check_now = true; max_growth = std::max(max_growth, 1e300); } }
-            max_growth = std::max(max_growth, f->growth);
-        }
-        for (auto& f : used_cplx) {
-            if (!f->checked) { f->growth = mf_check(ctx, f->f); f->checked = true; if (f->f.nperturbed > 0) { check_now = true; max_growth = std::max(max_growth, 1e300); } }
-            max_growth = std::max(max_growth, f->growth);
-        }
-        used_real.clear(); used_cplx.clear();
+
+    int* serr() const { return &st.p->smw_singular; }      // lives in the control block: comes back with every chunk synchronisation
+    bool cyclic_in() const { return opt_in.shifts.kind == ShiftSpec::CYCLIC; }
+    bool single_use() const { return !cyclic_in() && !opt.inner_solve && cache->enabled; }
+    // Cyclic lists on the multifrontal path: the factorisations of the FIRST pass through the cycle (one workgroup per front: ~0.5 ms each at
+    // n = 5177, 1.4 ms at n = 20209, a handful of CUs busy) also run ahead on the helper streams instead of one after the other in front of
+    // their first use; from the second pass on every factor is cached and the look-ahead finds nothing to do.
+    bool cyc_ahead() const {
+        const bool sharded_la = ctx->comm && std::max(ctx->comm->nranks, ctx->comm->emulate) > 1;
+        return cyclic_in() && !opt.inner_solve && cache->enabled && n > ctx->dense_inv_max_n && !sharded_la;
     }
-    ~AdiRun() {
-        for (auto& kv : prefetch_ev) { if (ctx) (void)hipStreamWaitEvent(ctx->stream, kv.second.ev, 0); (void)hipEventDestroy(kv.second.ev); }
-        for (auto e : ev_pool) (void)hipEventDestroy(e);
-    }
+    bool lookahead() const { return single_use() || cyc_ahead(); }
+    int fan_ranks() const { return ctx->comm ? std::max(1, std::max(ctx->comm->nranks, ctx->comm->emulate)) : 1; }
+    int fan_max() const { return (cyclic_in() && !opt.inner_solve && cache->enabled && n > ctx->dense_inv_max_n) ? std::min(ctx->adi_fan, FAN_GMAX) : 0; }
+    // which ranks this process plays in a fan group: its own, or all of them one after the other (shard_emulate)
+    bool plays_rank(int r) const { return fan_ranks() == 1 || (ctx->comm && ctx->comm->emulate > 1) || r == (ctx->comm ? ctx->comm->rank : 0); }
+
+    // adi_begin, in this order
+    void resolve_heuristic();
+    void form_tolerance(LDLt& C, const LDLtP& initial_guess);
+    void initial_residual(LDLt& C, const LDLtP& initial_guess);
+    void make_oracle();
+    void upload_control_block();
+    void smw_setup_cached_cycle();
+    void factor_cycle_upfront();
+    void agree_on_fan();
+    void pick_chunk_limit();
+    void prepare_fast_chain();
+    // adi_advance
+    void advance_fast(int budget);
+    bool try_fan_group(AdiChunk& ck);
+    bool fan_select(AdiChunk& ck, FanGroup& G);
+    bool fan_solves(FanGroup& G);
+    bool fan_smw_setup(FanGroup& G, const std::vector<int>& pos, SmwZ& sz);
+    void fan_mix(AdiChunk& ck, FanGroup& G);
+    bool one_step(AdiChunk& ck);
+    Mat real_step(std::complex<double> mu, bool* norm_done, bool* rode);
+    Mat dense_inverse_step(double mu, FactorEntry<double>& fe, bool* rode);
+    Mat column_sharded_step(double mu, FactorEntry<double>& fe);
+    Mat sparse_step(std::complex<double> mu, FactorEntry<double>* fe);
+    void complex_pair(std::complex<double> mu, Mat& V1, Mat& V2);
+    void close_chunk(AdiChunk& ck);
+    void maybe_compress();
+    // shared pieces
+    void apply_tolerance();
+    void resolve_deferred();
+    template <typename T> SmwCache::iterator smw_capacitance(std::pair<double, double> key, const BufP& keep, T* WU, int ldwu, const T* S, int lds_);
+    template <typename T> void check_one(FactorEntry<T>& f);
+    void check_used();
 };
 
-std::shared_ptr<AdiRun> adi_begin(Ctx* ctx, const GaleOperator& op_in, LDLt& C, const LDLtP& initial_guess, const AdiOptions& opt_in,
-                                  FactorCache* cache) {
-    auto runp = std::make_shared<AdiRun>();
-    AdiRun& run = *runp;
-    run.ctx = ctx; run.op = op_in; run.opt_in = opt_in;
-    const GaleOperator& op = run.op;
-    const Pencil& P = *op.P;
-    const int n = P.n;
-    if (!cache) cache = &run.local;
-    run.cache = cache;
-    AdiResult& res = run.res;
-    AdiOptions opt_h;                           // Cyclic(Heuristic(...)): the values are recomputed from (E, F) for this solve (adi.jl:54)
-    const AdiOptions* optp = &opt_in;
-    if (opt_in.shifts.kind == ShiftSpec::HEURISTIC) {
-        opt_h = opt_in;
-        opt_h.shifts.kind = ShiftSpec::CYCLIC;
-        opt_h.shifts.values = heuristic_shift_values(ctx, op, opt_in.shifts.h_nshifts, opt_in.shifts.h_kplus, opt_in.shifts.h_kminus, &res.warnings);
-        optp = &opt_h;
+// ---- the look-ahead ------------------------------------------------------------------------------------------------------------------
+Prefetcher::~Prefetcher() {
+    for (auto& kv : in_flight) { if (run.ctx) (void)hipStreamWaitEvent(run.ctx->stream, kv.second, 0); (void)hipEventDestroy(kv.second); }
+    for (auto e : ev_pool) (void)hipEventDestroy(e);
+}
+hipEvent_t Prefetcher::take_event() {
+    hipEvent_t ev;
+    if (!ev_pool.empty()) { ev = ev_pool.back(); ev_pool.pop_back(); }
+    else DRE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return ev;
+}
+// the shift about to be used may have been factorised ahead on a helper stream: the main stream waits for that factorisation's event
+void Prefetcher::wait(std::complex<double> mu) {
+    auto it = in_flight.find({mu.real(), mu.imag()});
+    if (it == in_flight.end()) return;
+    DRE_HIP(hipStreamWaitEvent(run.ctx->stream, it->second, 0));
+    ev_pool.push_back(it->second);
+    in_flight.erase(it);
+}
+// look-ahead factorisations the solve did not get to use stay in a persistent cache (Cyclic lists): whatever runs on the main stream from
+// here on — the next Lyapunov solve finds them "known" — is ordered behind them
+void Prefetcher::wait_all() {
+    for (auto& kv : in_flight) (void)hipStreamWaitEvent(run.ctx->stream, kv.second, 0);
+}
+bool Prefetcher::known(std::complex<double> mu) const {
+    const auto ck = std::make_tuple(run.op.tag, mu.real(), mu.imag());
+    return mu.imag() != 0.0 ? run.cache->cplx_.count(ck) > 0 : run.cache->real.count(ck) > 0;
+}
+// The next helper context in turn.  At the first call of a solve the helper streams are brought up behind the main stream (the operator's
+// value arrays are ready there) with the context's options.  (adi_cycle.hip, cycle_ops_prepare, brings its helpers up the same way but does
+// not copy pivot_static: the two lists of option fields are left as they were.)
+Ctx* Prefetcher::next_helper(int nh) {
+    Ctx* ctx = run.ctx;
+    if (!helpers_ready) {
+        helpers_grow(ctx, nh);
+        if (!ctx->helper_e0) DRE_HIP(hipEventCreateWithFlags(&ctx->helper_e0, hipEventDisableTiming));
+        DRE_HIP(hipEventRecord(ctx->helper_e0, ctx->stream));         // the operator's value arrays are ready here
+        for (int h = 0; h < nh; ++h) {
+            Ctx* hc = ctx->helpers[(size_t)h].get();
+            hc->pivot_static = ctx->pivot_static; hc->pivot_growth_warn = ctx->pivot_growth_warn; hc->pivot_growth_fail = ctx->pivot_growth_fail;
+            hc->top_inverse_max_rows = ctx->top_inverse_max_rows; hc->dense_inv_max_n = ctx->dense_inv_max_n; hc->mf_subtree = ctx->mf_subtree;
+            hc->timer->enabled = ctx->timer && ctx->timer->enabled;
+            DRE_HIP(hipStreamWaitEvent(hc->stream, ctx->helper_e0, 0));
+        }
+        helpers_ready = true;
     }
-    run.opt = *optp;
-    const AdiOptions& opt = run.opt;
-    const double ctf = opt.compress_tolfac;
-    const bool cex = opt.compress_exact;
+    return ctx->helpers[rr++ % (size_t)nh].get();
+}
+void Prefetcher::mark(Ctx* hc, std::complex<double> nx) {
+    hipEvent_t ev = take_event();
+    DRE_HIP(hipEventRecord(ev, hc->stream));
+    in_flight[{nx.real(), nx.imag()}] = ev;
+}
+// Factorise the next few shifts of the batch on the helper streams (one workgroup per front: a factorisation uses a handful of CUs
+// for ~200 us at n = 371 — 45 % of the kernel time of a default-ADI run when it sits on the main stream).
+// Expects: `cur` was just taken from the oracle (fan_call: nothing was taken, the group's own shifts are still upcoming).  Leaves: the
+// factorisations enqueued on helper streams, their factors in the cache, one event each in `in_flight`; nothing on ctx->stream.
+void Prefetcher::ahead(std::complex<double> cur, bool fan_call) {
+    Ctx* ctx = run.ctx;
+    const int nh = ctx->setup_streams >= 1 ? std::max(8, ctx->setup_streams) : 0;
+    if (!run.lookahead() || nh < 1) return;
+    auto ups = run.oracle->peek((size_t)2 * nh + 3);
+    // `cur` was just taken; when it opens a conjugate pair its partner is still the FIRST upcoming shift (the double step takes it later,
+    // adi.jl:190) and must not be read as the start of a new pair — that shifted every later pair by one: the partners were factorised
+    // ahead (never used, their slots never freed) and the shifts really needed were factorised inline (round 3 finding: 88 % of the
+    // complex factorisations of a default-ADI run sat on the main stream).
+    if (cur.imag() != 0.0 && !ups.empty() && ups[0] == std::conj(cur)) ups.erase(ups.begin());
+    // slots whose shift is no longer ahead (never the case when the pairs are read correctly; cheap insurance against a leak)
+    for (auto it = in_flight.begin(); it != in_flight.end();) {
+        bool still = false;
+        for (auto& u : ups) still = still || (u.real() == it->first.first && u.imag() == it->first.second);
+        if (still) { ++it; continue; }
+        ev_pool.push_back(it->second);
+        it = in_flight.erase(it);
+    }
+    if (trace_prefetch()) {
+        long &calls = ctx->trace.pf_calls, &nups = ctx->trace.pf_nups, &pend = ctx->trace.pf_pend;
+        ++calls; nups += (long)ups.size(); pend += (long)in_flight.size();
+        if (calls % 500 == 0) std::fprintf(stderr, "[prefetch] %ld calls: %.2f upcoming shifts known per call, %.2f factorisations already in flight per call (depth %d)\n",
+                                           calls, (double)nups / calls, (double)pend / calls, nh);
+    }
+    // Self-generated shift lists (Projection: ~13 upcoming shifts are known at every call): the factorisations that are not yet in flight
+    // go out TOGETHER, one set of level launches per kind (real / complex) on one helper stream, instead of one chain of ~15 launches
+    // per shift — the host spends ~250 us of every iteration of such a run on launch calls, and a single factorisation (~370 us at
+    // n = 1357, one workgroup per front) leaves the device as idle as sixteen of them.
+    if (run.single_use() && !run.check_now && ctx->prefetch_batch > 0) {
+        // (refilled only when few are left in flight: the window of known shifts advances by one per iteration, so filling it at every call
+        // would again send the factorisations out one by one)
+        if ((int)in_flight.size() > ctx->prefetch_batch) return;
+        batch_ahead(ups, cur, fan_call, nh);
+    }
+    for (size_t i = 0; i < ups.size() && (int)in_flight.size() < nh; ++i) {
+        const std::complex<double> nx = ups[i];
+        const bool cx = nx.imag() != 0.0;
+        if (cx) ++i;                                   // the conjugate partner follows (adi.jl:190) and needs no factorisation of its own
+        if (known(nx)) continue;
+        // the shift the caller is about to use RIGHT NOW comes round again inside the horizon when the cycle is shorter than it: the
+        // caller factorises it inline on its own stream — handing it to a helper here would put an unfinished factor into the cache that
+        // the caller picks up without an event to wait for
+        if (nx == cur && !fan_call) continue;
+        Ctx* hc = next_helper(nh);
+        // (Issuing these factorisations from a host thread of their own was tried — the loop spends ~250 us of host time per iteration on
+        // launch calls: no gain, 3 230 against 3 250 it/s at n = 1357 Ros2; launches from two threads serialise inside the HIP runtime.)
+        if (cx) (void)get_factor<cplx>(hc, run.op, run.cache, run.cache->cplx_, nx, false, nullptr, run.check_now);
+        else {
+            auto fnew = get_factor<double>(hc, run.op, run.cache, run.cache->real, nx, false, nullptr, run.check_now);
+            // a Cyclic factor will be used in every time step: its dense top-of-tree inverse is built right behind the factorisation, on
+            // the helper stream (mf_solve would build it inside the third solve that uses the factor, on the critical path)
+            if (run.cyc_ahead()) mf_prepare_topinv(hc, *run.op.P, fnew->f);
+        }
+        mark(hc, nx);
+    }
+}
+// the batched look-ahead: every upcoming shift without a factor, at most MF_ZMAX in flight, one shared set of launches per kind
+void Prefetcher::batch_ahead(const std::vector<std::complex<double>>& ups, std::complex<double> cur, bool fan_call, int nh) {
+    std::vector<std::complex<double>> tr, tc;
+    const int room = MF_ZMAX - (int)in_flight.size();
+    // the shift in hand rides along when it has no factor yet (the first shift of a refilled batch: factorised inline on the main stream
+    // it was ~230 us of eight dependent launches per refill; in the batch it shares them with the next fifteen)
+    if (!fan_call && !known(cur) && !pending(cur)) (cur.imag() != 0.0 ? tc : tr).push_back(cur);
+    for (size_t i = 0; i < ups.size() && (int)(tr.size() + tc.size()) < room; ++i) {
+        const std::complex<double> nx = ups[i];
+        const bool cx = nx.imag() != 0.0;
+        if (cx) ++i;
+        if (known(nx) || (nx == cur && !fan_call)) continue;
+        auto& lst = cx ? tc : tr;
+        bool dup = false;
+        for (auto& t : lst) dup = dup || t == nx;
+        if (!dup) lst.push_back(nx);
+    }
+    if (tr.size() >= 2) {
+        Ctx* hc = next_helper(nh);
+        factor_batch_into_cache<double>(hc, run.op, run.cache, run.cache->real, tr, run.cache->enabled ? 1 : 0);
+        for (auto& t : tr) mark(hc, t);
+    }
+    if (tc.size() >= 2) {
+        Ctx* hc = next_helper(nh);
+        factor_batch_into_cache<cplx>(hc, run.op, run.cache, run.cache->cplx_, tc, -1);
+        for (auto& t : tc) mark(hc, t);
+    }
+}
+
+// ---- shared pieces -------------------------------------------------------------------------------------------------------------------
+template <typename T>
+void AdiRun::check_one(FactorEntry<T>& f) {
+    if (!f.checked) { f.growth = mf_check(ctx, f.f); f.checked = true; if (f.f.nperturbed > 0) { check_now = true; max_growth = std::max(max_growth, 1e300); } }
+    max_growth = std::max(max_growth, f.growth);
+}
+void AdiRun::check_used() {
+    {   // the unchecked real factors with ONE synchronisation (the ten factorisations of a freshly factorised cycle: ten read-backs before)
+        std::vector<const Factor<double>*> fs; std::vector<FactorEntry<double>*> es;
+        for (auto& f : used_real) {
+            bool seen = false;
+            for (auto* e : es) seen = seen || e == f.get();
+            if (!f->checked && !seen) { fs.push_back(&f->f); es.push_back(f.get()); }
+        }
+        if (fs.size() >= 2) {
+            const std::vector<double> gr = mf_check_batch(ctx, fs);
+            for (size_t i = 0; i < es.size(); ++i) {
+                es[i]->growth = gr[i]; es[i]->checked = true;
+                if (es[i]->f.nperturbed > 0) { check_now = true; max_growth = std::max(max_growth, 1e300); }
+            }
+        }
+    }
+    for (auto& f : used_real) check_one(*f);
+    for (auto& f : used_cplx) check_one(*f);
+    used_real.clear(); used_cplx.clear();
+}
+// the tolerance reltol ||C|| was not known when the solve began (AdiOptions::normC_dev): wait for it on this stream and take the decisions
+// of adi.jl:115-123 for everything recorded so far, in iteration order
+void AdiRun::apply_tolerance() {
+    if (!tol_event) return;
+    if (opt.normC_join) opt.normC_join();          // (`done` is recorded by then)
+    DRE_HIP(hipStreamWaitEvent(ctx->stream, tol_event, 0));
+    adi_decide_scan(ctx, st.p, 0, opt.normC_dev, reltol, -1.0);
+    tol_event = nullptr;
+}
+void AdiRun::resolve_deferred() {
+    apply_tolerance();
+    if (!defer) return;
+    if (opt.normC_wait) opt.normC_wait();
+    adi_decide_scan(ctx, st.p, iters_host, opt.normC_dev, reltol, opt.abstol);
+    defer = false;
+}
+// The SMW products of one shift enter the solve's cache: W_U = M^-1 Vt as it lies in `keep` (WU, ldwu), and the inverse of the capacitance
+// matrix alpha I + S, S = U' W_U (m x m at S, leading dimension lds_), formed by one launch on ctx->stream behind whatever wrote S.
+template <typename T>
+SmwCache::iterator AdiRun::smw_capacitance(std::pair<double, double> key, const BufP& keep, T* WU, int ldwu, const T* S, int lds_) {
+    SmwCacheEntry en;
+    en.keep = keep; en.WU = WU; en.ldwu = ldwu;
+    en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(T));
+    hipLaunchKernelGGL((k_sinv<T>), dim3(1), dim3(64), 0, ctx->stream, m, S, lds_, op.alpha, (T*)en.sinv->p, (const AdiState*)st.p, serr());
+    return smw_cache.emplace(key, en).first;
+}
+
+// ---- adi_begin: the phases, in the order of the call ----------------------------------------------------------------------------------
+// Cyclic(Heuristic(...)): the values are recomputed from (E, F) for this solve (adi.jl:54).  Leaves `opt`, the options the solve runs with.
+void AdiRun::resolve_heuristic() {
+    opt = opt_in;
+    if (opt_in.shifts.kind != ShiftSpec::HEURISTIC) return;
+    opt.shifts.kind = ShiftSpec::CYCLIC;
+    opt.shifts.values = heuristic_shift_values(ctx, op, opt_in.shifts.h_nshifts, opt_in.shifts.h_kplus, opt_in.shifts.h_kminus, &res.warnings);
+}
+// ||C|| and the tolerance (synchronises for the norm unless the residual is given).  Leaves C destructured, reltol, abstol and `defer`.
+void AdiRun::form_tolerance(LDLt& C, const LDLtP& initial_guess) {
+    ctf = opt.compress_tolfac;
+    cex = opt.compress_exact;
     const bool keep_blocks = !cex && n <= xblocks_max_n() && C.blocks.size() > 1 && initial_guess && !opt.ignore_initial_guess && !initial_guess->iszero();
     double normC = 0.0;
-    const bool defer = opt.given_residual && opt.abstol < 0 && opt.normC_dev != nullptr;      // ||C|| arrives in device memory, later
+    defer = opt.given_residual && opt.abstol < 0 && opt.normC_dev != nullptr;      // ||C|| arrives in device memory, later
     DRE_REQUIRE(!opt.given_residual || defer || opt.abstol >= 0, "ADI with a given residual needs abstol or a device-side ||C||");
     if (opt.given_residual) { /* no right-hand side object */ }
     else if (keep_blocks) normC = ldlt_norm_dense_small(ctx, C);       // the summands go into the residual as they are (gale_residual_blocks)
     else { ldlt_destructure(ctx, C, ctf, cex); normC = ldlt_norm(ctx, C); }
-    const double reltol = opt.reltol >= 0 ? opt.reltol : n * EPS;
-    const double abstol = defer ? -1.0 : (opt.abstol >= 0 ? opt.abstol : reltol * normC);      // (-1: no norm is ever at or below it — the kernels only record)
-    run.defer = defer; run.reltol = reltol;
-    LDLtP X = (opt.ignore_initial_guess || !initial_guess) ? ldlt_zero(n) : initial_guess;
-    LDLtP resid;
+    reltol = opt.reltol >= 0 ? opt.reltol : n * EPS;
+    abstol = defer ? -1.0 : (opt.abstol >= 0 ? opt.abstol : reltol * normC);      // (-1: no norm is ever at or below it — the kernels only record)
+}
+// The initial residual in factored form, one block (R, Tm, alpha_res), and iteration 0 of the record.  Expects the tolerance (the Krylov mode
+// truncates relative to it).  Leaves the compression / residual kernels on ctx->stream and, unless deferred, the host copy of the norm.
+void AdiRun::initial_residual(LDLt& C, const LDLtP& initial_guess) {
+    X = (opt.ignore_initial_guess || !initial_guess) ? ldlt_zero(n) : initial_guess;
     if (opt.given_residual) {
         // the caller knows the warm-start residual in factored form (Rosenbrock-1 recurrence): truncated at the PREVIOUS step's level while this
         // step's tolerance is still being formed; the solve returns the increment
@@ -985,18 +1225,17 @@ std::shared_ptr<AdiRun> adi_begin(Ctx* ctx, const GaleOperator& op_in, LDLt& C, 
             if (!done) ldlt_compress(ctx, *resid, ctf, false, lag > 0.0 ? opt.residual_abs_frac * lag : -1.0);
         }
     } else {
-    // Krylov mode: components of the warm-start residual far below the convergence tolerance are dropped
-    resid = gale_residual_impl(ctx, op, C, X, ctf, cex, cex ? -1.0 : opt.residual_abs_frac * abstol,
-                                     opt.warm_L.empty() ? nullptr : &opt.warm_L, opt.warm_EtL.empty() ? nullptr : &opt.warm_EtL,
-                                     opt.rhs_lead_blocks, opt.rhs_e_coeff);
+        // Krylov mode: components of the warm-start residual far below the convergence tolerance are dropped
+        resid = gale_residual_impl(ctx, op, C, X, ctf, cex, cex ? -1.0 : opt.residual_abs_frac * abstol,
+                                   opt.warm_L.empty() ? nullptr : &opt.warm_L, opt.warm_EtL.empty() ? nullptr : &opt.warm_EtL,
+                                   opt.rhs_lead_blocks, opt.rhs_e_coeff);
     }
     ldlt_destructure(ctx, *resid, ctf, cex);
     LBlock rb = resid->blocks[0];
-    Mat& R = run.R; Mat& Tm = run.Tm;
     R = rb.L; Tm = rb.D;
-    const double alpha_res = rb.alpha;
-    const int k = R.cols;
-    const bool tdiag = rb.diag;      // a numerically diagonal T that is not flagged takes the general (dense-T) kernels: same result
+    alpha_res = rb.alpha;
+    k = R.cols;
+    tdiag = rb.diag;      // a numerically diagonal T that is not flagged takes the general (dense-T) kernels: same result
     const double norm0 = defer ? 1e300 : ldlt_norm_host(ctx, R, Tm, alpha_res);      // deferred: formed on the device below, read with the first chunk
     res.abstol = abstol; res.initial_norm = norm0; res.rhs_cols = k;
     res.norms.push_back(norm0); res.norm_iters.push_back(0);
@@ -1004,13 +1243,12 @@ std::shared_ptr<AdiRun> adi_begin(Ctx* ctx, const GaleOperator& op_in, LDLt& C, 
     res.X = X;
     res.res_norm = norm0;
     DRE_REQUIRE(opt.maxiters >= 0 && opt.maxiters <= DRE_ADI_MAX_ITERS_LIMIT, "ADI: maxiters out of range (dre_hip.h, DRE_ADI_MAX_ITERS)");
-    run.X = X; run.resid = resid; run.alpha_res = alpha_res; run.abstol = abstol; run.ctf = ctf; run.cex = cex; run.tdiag = tdiag;
-    run.n = n; run.k = k; run.m = op.has_lr ? op.U.cols : 0;
-    run.Xw = std::make_shared<LDLt>(*X);        // the iterate: never mutate the caller's initial guess (adi.jl:174 builds a new list)
-    run.Crhs = C;
-    if (norm0 <= abstol || k == 0) { res.converged = true; run.finished = true; return runp; }
-
-    std::unique_ptr<ShiftOracle>& oracle = run.oracle;
+    m = op.has_lr ? op.U.cols : 0;
+    Xw = std::make_shared<LDLt>(*X);        // the iterate: never mutate the caller's initial guess (adi.jl:174 builds a new list)
+    Crhs = C;
+}
+// The shift strategy, fed with the initial residual.  Expects R.
+void AdiRun::make_oracle() {
     if (opt.shifts.kind == ShiftSpec::CYCLIC) {
         DRE_REQUIRE(!opt.shifts.values.empty(), "Cyclic shifts: empty list");
         auto o = std::make_unique<CyclicOracle>();
@@ -1028,139 +1266,130 @@ std::shared_ptr<AdiRun> adi_begin(Ctx* ctx, const GaleOperator& op_in, LDLt& C, 
         oracle = std::move(o);
     }
     oracle->update(R, {});
-
-    // device-resident control block
-    run.st = DevArr<AdiState>(ctx, 1);
-    DevArr<AdiState>& st = run.st;
+}
+// The device-resident control block.  Expects the oracle and iteration 0 of the record.  Leaves on ctx->stream the upload of the block and,
+// deferred, the norm of the initial residual as iteration 0; the tolerance may then be on its way on a stream of the caller's (tol_event).
+void AdiRun::upload_control_block() {
+    st = DevArr<AdiState>(ctx, 1);
     if (auto* po = dynamic_cast<ProjectionOracle*>(oracle.get())) po->st_dev = st.p;
     if (auto* uo = dynamic_cast<UserOracle*>(oracle.get())) uo->st_dev = st.p;
-    AdiState& h0 = run.h0;           // stays alive with the solver object (source of an asynchronous upload)
-    std::memset(&h0, 0, sizeof(h0));
-    h0.maxiters = opt.maxiters; h0.abstol = abstol; h0.res_norm = norm0; h0.norms[0] = norm0;
+    std::memset(&h0, 0, sizeof(h0));           // (h0 stays alive with the solver object: source of an asynchronous upload)
+    h0.maxiters = opt.maxiters; h0.abstol = abstol; h0.res_norm = res.initial_norm; h0.norms[0] = res.initial_norm;
     DRE_HIP(hipMemcpyAsync(st.p, &h0, sizeof(AdiState), hipMemcpyHostToDevice, ctx->stream));      // (whole block: the ticket of the fan groups' norm launch starts at 0)
-    if (defer) {
-        // norm of the initial residual as iteration 0 of the record, on the device (no host round trip)
-        Mat G0(ctx, k, k);
-        gemm(ctx, true, false, 1.0, R, R, 0.0, G0, nullptr, "gemm_gram");
-        ldlt_norm_update_state(ctx, G0, Tm, tdiag, alpha_res, st.p, 0);
-        if (opt.normC_build) {
-            // the tolerance is formed beside the SMW set-up and the first group's sweeps (a stream and a host thread of the caller's); this stream
-            // picks it up in front of its first decision, the host reads it with the first chunk
-            hipEvent_t e0 = aux_event(ctx, 0), e1 = aux_event(ctx, 1);
-            DRE_HIP(hipEventRecord(e0, ctx->stream));
-            opt.normC_build(e0, R, Tm, alpha_res, e1);
-            run.tol_event = e1;
-            run.defer = false; run.abstol_pending = true;
-        }
+    if (!defer) return;
+    // norm of the initial residual as iteration 0 of the record, on the device (no host round trip)
+    Mat G0(ctx, k, k);
+    gemm(ctx, true, false, 1.0, R, R, 0.0, G0, nullptr, "gemm_gram");
+    ldlt_norm_update_state(ctx, G0, Tm, tdiag, alpha_res, st.p, 0);
+    if (opt.normC_build) {
+        // the tolerance is formed beside the SMW set-up and the first group's sweeps (a stream and a host thread of the caller's); this stream
+        // picks it up in front of its first decision, the host reads it with the first chunk
+        hipEvent_t e0 = aux_event(ctx, 0), e1 = aux_event(ctx, 1);
+        DRE_HIP(hipEventRecord(e0, ctx->stream));
+        opt.normC_build(e0, R, Tm, alpha_res, e1);
+        tol_event = e1;
+        defer = false; abstol_pending = true;
     }
-    const int m = op.has_lr ? op.U.cols : 0;
+}
+// Dense-inverse path: the SMW products of ALL shifts of the cycle whose stacked inverses already exist (i.e. from the
+// second time step on) are formed up front — one batched GEMM, one batched capacitance inversion, one batched fold —
+// instead of three launches per shift inside the loop.  Expects the control block on ctx->stream; leaves the three launches there.
+void AdiRun::smw_setup_cached_cycle() {
     DRE_REQUIRE(m <= 32, "SMW: more than 32 low-rank columns not supported (dre_hip.h, DRE_SMW_MAX_RANK)");
-    auto& smw_cache = run.smw_cache;
-    int* const serr = &st.p->smw_singular;     // lives in the control block: comes back with every chunk synchronisation
-    if (op.has_lr && opt.shifts.kind == ShiftSpec::CYCLIC) {
-        // Dense-inverse path: the SMW products of ALL shifts of the cycle whose stacked inverses already exist (i.e. from the
-        // second time step on) are formed up front — one batched GEMM, one batched capacitance inversion, one batched fold —
-        // instead of three launches per shift inside the loop.
-        std::vector<GemmBatchDesc> descs;
-        std::vector<SmwBatch> hb;
-        std::vector<std::pair<double, SmwCacheEntry>> pending;
-        for (auto& mu : opt.shifts.values) {
-            if (mu.imag() != 0.0 || smw_cache.count({mu.real(), 0.0})) continue;
-            bool dup = false;
-            for (auto& pe : pending) dup = dup || pe.first == mu.real();
-            if (dup) continue;
-            auto it = cache->real.find(std::make_tuple(op.tag, mu.real(), 0.0));
-            if (it == cache->real.end()) continue;
-            auto& fe = it->second;
-            if (!fe->dense || fe->stack.empty() || fe->stack_U != (const void*)op.U.p || fe->stack_m != m) continue;
-            Mat WK(ctx, 2 * n + m, m), WKS(ctx, 2 * n, m);
-            SmwCacheEntry en;
-            en.keep = WKS.buf; en.WU = WKS.p; en.ldwu = WKS.ld;
-            en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(double));
-            en.keep2 = WK.buf;
-            descs.push_back({fe->stack.p, op.Vt.p, WK.p, nullptr, 1.0, 2 * n + m, m, n, fe->stack.ld, op.Vt.ld, WK.ld, 0});
-            hb.push_back({WK.p, (double*)en.sinv->p, WKS.p});
-            pending.push_back({mu.real(), en});
-        }
-        if (!descs.empty()) {
-            gemm_batched(ctx, descs, "gemm_dinv");
-            DevArr<SmwBatch> db(ctx, hb.size());
-            DRE_HIP(hipMemcpyAsync(db.p, hb.data(), hb.size() * sizeof(SmwBatch), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_sinv_batched, dim3((unsigned)hb.size()), dim3(64), 0, ctx->stream, n, m, 2 * n + m, op.alpha, (const SmwBatch*)db.p,
-                               (const AdiState*)st.p, serr);
-            hipLaunchKernelGGL(k_fold_sinv_batched, dim3(ceil_div(2 * n * m, 256), (unsigned)hb.size()), dim3(256), 0, ctx->stream, 2 * n, m, 2 * n + m,
-                               (const SmwBatch*)db.p, (const AdiState*)st.p);
-            for (auto& pe : pending) smw_cache.emplace(std::make_pair(pe.first, 0.0), pe.second);
-        }
+    if (!(op.has_lr && opt.shifts.kind == ShiftSpec::CYCLIC)) return;
+    auto stacked = [&](double mu) -> FactorEntry<double>* {
+        auto it = cache->real.find(std::make_tuple(op.tag, mu, 0.0));
+        if (it == cache->real.end()) return nullptr;
+        auto& fe = it->second;
+        return (!fe->dense || fe->stack.empty() || fe->stack_U != (const void*)op.U.p || fe->stack_m != m) ? nullptr : fe.get();
+    };
+    const std::vector<double> mus = distinct_real_shifts(opt.shifts.values, opt.shifts.values.size(),
+                                                         [&](size_t, double mu) { return smw_cache.count({mu, 0.0}) > 0 || !stacked(mu); });
+    if (mus.empty()) return;
+    std::vector<GemmBatchDesc> descs;
+    std::vector<SmwBatch> hb;
+    std::vector<SmwCacheEntry> pending;
+    for (double mu : mus) {
+        FactorEntry<double>* fe = stacked(mu);
+        Mat WK(ctx, 2 * n + m, m), WKS(ctx, 2 * n, m);
+        SmwCacheEntry en;
+        en.keep = WKS.buf; en.WU = WKS.p; en.ldwu = WKS.ld;
+        en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(double));
+        en.keep2 = WK.buf;
+        descs.push_back({fe->stack.p, op.Vt.p, WK.p, nullptr, 1.0, 2 * n + m, m, n, fe->stack.ld, op.Vt.ld, WK.ld, 0});
+        hb.push_back({WK.p, (double*)en.sinv->p, WKS.p});
+        pending.push_back(en);
     }
-
-    // General path, Cyclic real list, one rank: every shift of the cycle that has no factor yet is factorised NOW, all of them in shared
-    // launches (sparse.hip, mf_factor_batch: one launch per tree level for the whole list) together with their dense top inverses — round 3
-    // ran them as ten chains on five helper streams: 4 + 1.6 + 1.6 ms of the first time step at n = 5177 went into waiting for them.
-    // Sharded by shift (a communicator with real ranks): a rank owns the shifts at the list positions i = rank (mod P) — fixed for the run, whatever
-    // the group boundaries turn out to be — and factorises exactly those here, in shared launches, like the single rank does with the whole list
-    // (round 4 switched the batched set-up off in sharded mode: every rank factorised its shifts one by one inside the first groups).
-    if (opt.shifts.kind == ShiftSpec::CYCLIC && !opt.inner_solve && cache->enabled && n > ctx->dense_inv_max_n && ctx->adi_fan >= 2 && P.use_mfma_sweeps) {
-        const bool real_ranks = ctx->comm && ctx->comm->nranks > 1 && ctx->comm->emulate <= 1;
-        std::vector<double> todo;
+    gemm_batched(ctx, descs, "gemm_dinv");
+    DevArr<SmwBatch> db(ctx, hb.size());
+    DRE_HIP(hipMemcpyAsync(db.p, hb.data(), hb.size() * sizeof(SmwBatch), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_sinv_batched, dim3((unsigned)hb.size()), dim3(64), 0, ctx->stream, n, m, 2 * n + m, op.alpha, (const SmwBatch*)db.p,
+                       (const AdiState*)st.p, serr());
+    hipLaunchKernelGGL(k_fold_sinv_batched, dim3(ceil_div(2 * n * m, 256), (unsigned)hb.size()), dim3(256), 0, ctx->stream, 2 * n, m, 2 * n + m,
+                       (const SmwBatch*)db.p, (const AdiState*)st.p);
+    for (size_t z = 0; z < mus.size(); ++z) smw_cache.emplace(std::make_pair(mus[z], 0.0), pending[z]);
+}
+// General path, Cyclic real list, one rank: every shift of the cycle that has no factor yet is factorised NOW, all of them in shared
+// launches (sparse.hip, mf_factor_batch: one launch per tree level for the whole list) together with their dense top inverses — round 3
+// ran them as ten chains on five helper streams: 4 + 1.6 + 1.6 ms of the first time step at n = 5177 went into waiting for them.
+// Sharded by shift (a communicator with real ranks): a rank owns the shifts at the list positions i = rank (mod P) — fixed for the run, whatever
+// the group boundaries turn out to be — and factorises exactly those here, in shared launches, like the single rank does with the whole list
+// (round 4 switched the batched set-up off in sharded mode: every rank factorised its shifts one by one inside the first groups).
+// Leaves the factorisations on ctx->stream, unchecked (used_real: read back with the first chunk).
+void AdiRun::factor_cycle_upfront() {
+    const Pencil& P = *op.P;
+    if (!(opt.shifts.kind == ShiftSpec::CYCLIC && !opt.inner_solve && cache->enabled && n > ctx->dense_inv_max_n && ctx->adi_fan >= 2 && P.use_mfma_sweeps)) return;
+    const bool real_ranks = ctx->comm && ctx->comm->nranks > 1 && ctx->comm->emulate <= 1;
+    // (the rank's share by list position and the all-or-nothing rule on a complex shift belong to this site alone)
+    std::vector<double> todo = distinct_real_shifts(opt.shifts.values, MF_ZMAX, [&](size_t iv, double mu) {
+        if (real_ranks && (int)(iv % (size_t)ctx->comm->nranks) != ctx->comm->rank) return true;
+        return cache->real.count(std::make_tuple(op.tag, mu, 0.0)) > 0;
+    });
+    for (auto& mu : opt.shifts.values) if (mu.imag() != 0.0) { todo.clear(); break; }
+    if (todo.size() >= 2) {
+        auto fes = factor_batch_into_cache<double>(ctx, op, cache, cache->real, as_complex(todo), 1);
+        std::vector<Factor<double>*> fp;
+        for (auto& fe : fes) { fp.push_back(&fe->f); used_real.push_back(fe); }                 // pivots / growth are read back with the first chunk
+        mf_topinv_batch(ctx, P, fp.data(), (int)todo.size());
+    }
+    if (real_ranks) agree_on_fan();
+}
+// The batched solves refuse factors with replaced pivots (static pivoting) — a property of a rank's OWN shifts.  One rank leaving the
+// fan path alone would leave the others inside the group's all-gather, so the ranks agree once per operator: every
+// rank checks the factors it owns (one read-back) and the flags are summed across the communicator; any refusal switches the fan
+// groups off on ALL ranks for this operator (the column-sharded iterations take over).  Synchronises ctx->stream the first time.
+void AdiRun::agree_on_fan() {
+    auto ag = cache->fan_agreed.find(op.tag);
+    if (ag == cache->fan_agreed.end()) {
+        std::vector<const Factor<double>*> fs;
+        std::vector<std::shared_ptr<FactorEntry<double>>> mine_fe;
         for (size_t iv = 0; iv < opt.shifts.values.size(); ++iv) {
-            const auto& mu = opt.shifts.values[iv];
-            if (mu.imag() != 0.0) { todo.clear(); break; }
-            if (real_ranks && (int)(iv % (size_t)ctx->comm->nranks) != ctx->comm->rank) continue;
-            bool dup = cache->real.count(std::make_tuple(op.tag, mu.real(), 0.0)) > 0;
-            for (double t : todo) dup = dup || t == mu.real();
-            if (!dup && (int)todo.size() < MF_ZMAX) todo.push_back(mu.real());
+            if ((int)(iv % (size_t)ctx->comm->nranks) != ctx->comm->rank) continue;
+            auto itf = cache->real.find(std::make_tuple(op.tag, opt.shifts.values[iv].real(), 0.0));
+            if (itf == cache->real.end()) continue;
+            mine_fe.push_back(itf->second);
+            if (!itf->second->checked) fs.push_back(&itf->second->f);
         }
-        if (todo.size() >= 2) {
-            std::vector<std::shared_ptr<FactorEntry<double>>> fes;
-            std::vector<Factor<double>*> fp;
-            for (double t : todo) { (void)t; fes.push_back(std::make_shared<FactorEntry<double>>()); fp.push_back(&fes.back()->f); }
-            mf_factor_batch<double>(ctx, P, op.valFt.p, P.valEt.p, 1.0, todo.data(), fp.data(), (int)todo.size());
-            for (size_t z = 0; z < todo.size(); ++z) {
-                fes[z]->f.allow_topinv = true;
-                const auto key = std::make_tuple(op.tag, todo[z], 0.0);
-                cache->real[key] = fes[z]; cache->fresh.push_back(key); cache->nfactor++;
-                run.used_real.push_back(fes[z]);                 // pivots / growth are read back with the first chunk
-            }
-            mf_topinv_batch(ctx, P, fp.data(), (int)todo.size());
+        if (!fs.empty()) {
+            const std::vector<double> gr = mf_check_batch(ctx, fs);
+            size_t j = 0;
+            for (auto& fe : mine_fe) if (!fe->checked) { fe->growth = gr[j++]; fe->checked = true; }
         }
-        if (real_ranks) {
-            // The batched solves refuse factors with replaced pivots (static pivoting) — a property of a rank's OWN shifts.  One rank leaving the
-            // fan path alone would leave the others inside the group's all-gather, so the ranks agree once per operator: every
-            // rank checks the factors it owns (one read-back) and the flags are summed across the communicator; any refusal switches the fan
-            // groups off on ALL ranks for this operator (the column-sharded iterations take over).
-            auto ag = cache->fan_agreed.find(op.tag);
-            if (ag == cache->fan_agreed.end()) {
-                std::vector<const Factor<double>*> fs;
-                std::vector<std::shared_ptr<FactorEntry<double>>> mine_fe;
-                for (size_t iv = 0; iv < opt.shifts.values.size(); ++iv) {
-                    if ((int)(iv % (size_t)ctx->comm->nranks) != ctx->comm->rank) continue;
-                    auto itf = cache->real.find(std::make_tuple(op.tag, opt.shifts.values[iv].real(), 0.0));
-                    if (itf == cache->real.end()) continue;
-                    mine_fe.push_back(itf->second);
-                    if (!itf->second->checked) fs.push_back(&itf->second->f);
-                }
-                if (!fs.empty()) {
-                    const std::vector<double> gr = mf_check_batch(ctx, fs);
-                    size_t j = 0;
-                    for (auto& fe : mine_fe) if (!fe->checked) { fe->growth = gr[j++]; fe->checked = true; }
-                }
-                double flag = 0.0;
-                for (auto& fe : mine_fe) if (fe->f.nperturbed > 0) flag = 1.0;
-                DevArr<double> fl(ctx, 1);
-                DRE_HIP(hipMemcpyAsync(fl.p, &flag, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-                comm_allreduce_sum(ctx, *ctx->comm, fl.p, 1);
-                double tot = 0.0;
-                ctx_fetch(ctx, fl.p, sizeof(double), &tot);
-                ag = cache->fan_agreed.emplace(op.tag, tot > 0.0).first;
-            }
-            if (ag->second) run.fan_off = true;
-        }
+        double flag = 0.0;
+        for (auto& fe : mine_fe) if (fe->f.nperturbed > 0) flag = 1.0;
+        DevArr<double> fl(ctx, 1);
+        DRE_HIP(hipMemcpyAsync(fl.p, &flag, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        comm_allreduce_sum(ctx, *ctx->comm, fl.p, 1);
+        double tot = 0.0;
+        ctx_fetch(ctx, fl.p, sizeof(double), &tot);
+        ag = cache->fan_agreed.emplace(op.tag, tot > 0.0).first;
     }
-
-    // chunk length: compression_interval, or — where the intermediate compressions are deferred anyway — the iteration count of the
-    // previous solve (+2), so that a whole Lyapunov solve is enqueued before the first host synchronisation
-    run.chunk_limit = (!cex && n <= xblocks_max_n() && cache->iters_hint > 0) ? std::max(opt.compression_interval, cache->iters_hint + 2)
+    if (ag->second) fan_off = true;
+}
+// chunk length: compression_interval, or — where the intermediate compressions are deferred anyway — the iteration count of the
+// previous solve (+2), so that a whole Lyapunov solve is enqueued before the first host synchronisation.  Host arithmetic only.
+void AdiRun::pick_chunk_limit() {
+    chunk_limit = (!cex && n <= xblocks_max_n() && cache->iters_hint > 0) ? std::max(opt.compression_interval, cache->iters_hint + 2)
                                                                           : opt.compression_interval;
     // The same on the multifrontal path with a Cyclic list (fan groups): the intermediate compressions are deferred there as long as the factor
     // fits the factor form (adi_advance), so a whole solve of the previous length is enqueued before the first synchronisation — provided the
@@ -1173,837 +1402,676 @@ std::shared_ptr<AdiRun> adi_begin(Ctx* ctx, const GaleOperator& op_in, LDLt& C, 
         // in-loop compression and fell back to the reference's order, 6.4 instead of ~4 ms per step.)
         const bool free_form = opt.given_residual && opt.keep_history && !opt.final_compress && ctx->recurrence_wide != 0;
         const long room = free_form ? (1L << 20) : ((long)n - 64 - X->rank()) / k - 2L * opt.compression_interval - FAN_GMAX;
-        run.chunk_limit = (int)std::max<long>(opt.compression_interval, std::min<long>(cache->iters_hint + 1, room));
-        run.chunk_from_hint = true;       // exactly that many iterations: the last group of the chunk is cut short (a speculative group costs 14 launches)
+        chunk_limit = (int)std::max<long>(opt.compression_interval, std::min<long>(cache->iters_hint + 1, room));
+        chunk_from_hint = true;       // exactly that many iterations: the last group of the chunk is cut short (a speculative group costs 14 launches)
     }
-    // ---- fast chain (dense.hip, k_adi_fast): every shift of the cycle is real and already has its stacked dense inverse for the
-    // current low-rank factor (i.e. from the second time step of a run on) and the residual is at most 96 columns wide ----------
-    bool fast = !opt_in.inner_solve && opt_in.shifts.kind == ShiftSpec::CYCLIC && k >= 1 && k <= ADI_FAST_MAX_K && n <= ctx->dense_inv_max_n && cache->enabled;
-    auto& fast_fe = run.fast_fe;            // per position of the cycle
-    auto& fast_pack = run.fast_pack;
-    auto& fast_keep = run.fast_keep;
-    if (fast) {
-        const int mm = op.has_lr ? m : 0;
-        std::map<double, double*> by_mu;
-        std::vector<const double*> stacks, wks; std::vector<double*> outs;
-        for (auto& mu : opt.shifts.values) {
-            if (mu.imag() != 0.0) { fast = false; break; }
-            auto it = cache->real.find(std::make_tuple(op.tag, mu.real(), 0.0));
-            if (it == cache->real.end() || !it->second->dense || it->second->stack.empty() || it->second->stack_m != mm ||
-                (mm && it->second->stack_U != (const void*)op.U.p)) { fast = false; break; }
-            auto sc = smw_cache.find({mu.real(), 0.0});
-            if (mm && sc == smw_cache.end()) { fast = false; break; }
-            fast_fe.push_back(it->second);
-            auto bm = by_mu.find(mu.real());
-            if (bm == by_mu.end()) {
-                Mat pk(ctx, (int)adi_fast_pack_doubles(n) / 64, 64);
-                fast_keep.push_back(pk);
-                stacks.push_back(it->second->stack.p);
-                wks.push_back(mm ? (const double*)sc->second.WU : nullptr);
-                outs.push_back(pk.p);
-                bm = by_mu.emplace(mu.real(), pk.p).first;
-            }
-            fast_pack.push_back(bm->second);
+}
+// ---- fast chain (dense.hip, k_adi_fast): every shift of the cycle is real and already has its stacked dense inverse for the
+// current low-rank factor (i.e. from the second time step of a run on) and the residual is at most 96 columns wide ----------
+// Expects the SMW products of the cycle in smw_cache (smw_setup_cached_cycle); leaves the pack launches on ctx->stream and `fast`.
+void AdiRun::prepare_fast_chain() {
+    fast = !opt_in.inner_solve && cyclic_in() && k >= 1 && k <= ADI_FAST_MAX_K && n <= ctx->dense_inv_max_n && cache->enabled;
+    if (!fast) return;
+    const int mm = op.has_lr ? m : 0;
+    std::map<double, double*> by_mu;
+    std::vector<const double*> stacks, wks; std::vector<double*> outs;
+    for (auto& mu : opt.shifts.values) {          // fast_fe, fast_pack: per position of the cycle
+        if (mu.imag() != 0.0) { fast = false; break; }
+        auto it = cache->real.find(std::make_tuple(op.tag, mu.real(), 0.0));
+        if (it == cache->real.end() || !it->second->dense || it->second->stack.empty() || it->second->stack_m != mm ||
+            (mm && it->second->stack_U != (const void*)op.U.p)) { fast = false; break; }
+        auto sc = smw_cache.find({mu.real(), 0.0});
+        if (mm && sc == smw_cache.end()) { fast = false; break; }
+        fast_fe.push_back(it->second);
+        auto bm = by_mu.find(mu.real());
+        if (bm == by_mu.end()) {
+            Mat pk(ctx, (int)adi_fast_pack_doubles(n) / 64, 64);
+            fast_keep.push_back(pk);
+            stacks.push_back(it->second->stack.p);
+            wks.push_back(mm ? (const double*)sc->second.WU : nullptr);
+            outs.push_back(pk.p);
+            bm = by_mu.emplace(mu.real(), pk.p).first;
         }
-        if (fast) adi_fast_build(ctx, n, mm, stacks, 2 * n + mm, wks, 2 * n, outs);
+        fast_pack.push_back(bm->second);
     }
-    run.fast = fast;
+    if (fast) adi_fast_build(ctx, n, mm, stacks, 2 * n + mm, wks, 2 * n, outs);
+}
+
+std::shared_ptr<AdiRun> adi_begin(Ctx* ctx, const GaleOperator& op_in, LDLt& C, const LDLtP& initial_guess, const AdiOptions& opt_in,
+                                  FactorCache* cache) {
+    auto runp = std::make_shared<AdiRun>();
+    AdiRun& run = *runp;
+    run.ctx = ctx; run.op = op_in; run.opt_in = opt_in;
+    run.n = op_in.P->n;
+    run.cache = cache ? cache : &run.local;
+    run.resolve_heuristic();
+    run.form_tolerance(C, initial_guess);
+    run.initial_residual(C, initial_guess);
+    if (run.res.initial_norm <= run.abstol || run.k == 0) { run.res.converged = true; run.finished = true; return runp; }
+    run.make_oracle();
+    run.upload_control_block();
+    run.smw_setup_cached_cycle();
+    run.factor_cycle_upfront();
+    run.pick_chunk_limit();
+    run.prepare_fast_chain();
     return runp;
+}
+
+// ---- adi_advance: the fast-chain chunk -------------------------------------------------------------------------------------------------
+// One chunk of the fast chain: one launch per iteration, the norms and decisions two launches behind, one synchronisation.
+// Expects the packs of prepare_fast_chain; leaves nothing in flight (R, Xw, the norms and the counters are those of the accepted iterations).
+void AdiRun::advance_fast(int budget) {
+    const int nstrip = adi_fast_nstrip(n), kst = adi_fast_kst(n);
+    if (!fast_ready) {
+        Gm = Mat(ctx, k * k, 2);
+        nws = DevArr<double>(ctx, ADI_FAST_NWS);
+        DRE_HIP(hipMemsetAsync(nws.p, 0, (ADI_FAST_NWS) * sizeof(double), ctx->stream));
+        fast_ready = true;
+    }
+    const int base_it = iters_host;
+    // one more iteration than the previous solve needed; the two flush launches deliver the decisions of the last two
+    const int fast_chunk = cache->iters_hint > 0 ? std::max(opt.compression_interval, cache->iters_hint + 1) : chunk_limit;
+    const int nit = std::min(std::min(std::min(std::max(1, fast_chunk), std::max(1, budget)), opt.maxiters - iters_host), 480);
+    if (nit <= 0) { finished = true; resid->blocks[0].L = R; return; }
+    Mat Rring(ctx, n, k * nit), Vall(ctx, n, k * nit);
+    const size_t blocks_before = Xw->blocks.size();
+    const size_t cyc_before = cyc;                // cyc: position in the cycle
+    AdiFastArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n = n; a.k = k; a.nstrip = nstrip; a.kst = kst; adi_fast_pick(n, k, &a.mode, &a.nt);
+    a.T = Tm.p; a.ldt = Tm.ld; a.tdiag = tdiag ? 1 : 0; a.alpha = alpha_res; a.st = st.p; a.nws = nws.p;
+    // the residual also in the B-operand lane order (dense.hpp, AdiFastArgs::Rpc): slot 0 = the chunk's input, slot j = after iteration j
+    const bool use_pk = a.mode == 0;
+    const size_t rpd = adi_fast_rpack_doubles(n, k);
+    DevArr<double> Rpk(ctx, use_pk ? rpd * (size_t)(nit + 1) : 1);
+    if (use_pk) adi_fast_pack_r(ctx, n, k, R.p, R.ld, Rpk.p, st.p);
+    for (int j = 1; j <= nit; ++j) {
+        const std::complex<double> mu = opt.shifts.values[cyc % opt.shifts.values.size()];
+        all_shifts.push_back(mu);
+        used_real.push_back(fast_fe[cyc % fast_fe.size()]);
+        a.Apack = fast_pack[cyc % fast_pack.size()];
+        if (j == 1) { a.Rcur = R.p; a.ldr = R.ld; } else { a.Rcur = Rring.p + (size_t)(j - 2) * k * Rring.ld; a.ldr = Rring.ld; }
+        a.Rnext = Rring.p + (size_t)(j - 1) * k * Rring.ld; a.ldr_next = Rring.ld;
+        a.Rpc = use_pk ? Rpk.p + (size_t)(j - 1) * rpd : nullptr;
+        a.Rpn = use_pk ? Rpk.p + (size_t)j * rpd : nullptr;
+        Mat Vj = Vall.colsview((j - 1) * k, k);
+        a.V = Vj.p; a.ldv = Vj.ld;
+        a.two_mu = 2.0 * mu.real();
+        const int g = base_it + j;                                  // shifts consumed after this iteration
+        // this launch also forms the Gram matrix of its INPUT residual (iteration g - 1) and decides on iteration g - 2
+        a.G_prev = j >= 2 ? Gm.p + (size_t)((g - 1) & 1) * k * k : nullptr;
+        a.G_prev2 = j >= 3 ? Gm.p + (size_t)((g - 2) & 1) * k * k : nullptr;
+        a.it_prev2 = g - 2; a.do_strips = 1;
+        adi_fast_iter(ctx, a);
+        Xw->blocks.push_back({Vj, Tm, -2.0 * mu.real() * alpha_res, tdiag});
+        ++cyc; ++iters_host;
+    }
+    {   // drain the norm pipeline: Gram matrix of the last residual, decisions for the last two iterations of the chunk
+        const int g = base_it + nit;
+        a.do_strips = 0; a.Apack = nullptr; a.Rnext = nullptr; a.V = nullptr;
+        a.Rpc = use_pk ? Rpk.p + (size_t)nit * rpd : nullptr; a.Rpn = nullptr;
+        a.Rcur = Rring.p + (size_t)(nit - 1) * k * Rring.ld; a.ldr = Rring.ld;
+        a.G_prev = Gm.p + (size_t)(g & 1) * k * k;
+        a.G_prev2 = nit >= 2 ? Gm.p + (size_t)((g - 1) & 1) * k * k : nullptr;
+        a.it_prev2 = g - 1;
+        adi_fast_iter(ctx, a);
+        a.G_prev = nullptr;
+        a.G_prev2 = Gm.p + (size_t)(g & 1) * k * k;
+        a.it_prev2 = g;
+        adi_fast_iter(ctx, a);
+    }
+    AdiState h;
+    DRE_HIP(hipMemcpyAsync(&h, st.p, sizeof(AdiState), hipMemcpyDeviceToHost, ctx->stream));
+    DRE_HIP(hipStreamSynchronize(ctx->stream));
+    const int acc_it = std::min(std::max(h.iters - base_it, 0), nit);          // accepted iterations of this chunk
+    for (int j = 1; j <= acc_it; ++j) { res.norms.push_back(h.norms[(base_it + j) & 511]); res.norm_iters.push_back(base_it + j); }
+    Xw->blocks.resize(blocks_before + acc_it);
+    check_used();
+    if (acc_it > 0) R = Rring.colsview((acc_it - 1) * k, k);
+    iters_host = base_it + acc_it;
+    all_shifts.resize(iters_host);
+    cyc = cyc_before + acc_it;
+    last_compression += acc_it;
+    res.iters = h.iters;
+    res.res_norm = h.res_norm;
+    if (h.done || acc_it < nit) finished = true;
+    // (literal mode: the interval compression also runs after the LAST step, before the observer looks — adi.jl:111-119; it is the
+    // compression adi.jl:78-80 would do anyway)
+    if (opt.compression && last_compression >= opt.compression_interval && (!finished || cex)) {
+        const long rk = Xw->rank();
+        const bool put_off = !cex && (n <= 512 ? rk <= 16L * n : (n <= ctx->compress_direct_max_n && rk <= 16L * n));
+        if (!put_off) { ldlt_compress(ctx, *Xw, ctf, cex); last_compression = 0; }
+    }
+    resid->blocks[0].L = R;                 // the residual factor after the last accepted iteration
+}
+
+// ---- adi_advance: fan groups -----------------------------------------------------------------------------------------------------------
+// Fan groups (round 4: batched, and sharded over the ranks of a communicator BY SHIFT — north_star's "independent ADI shifts farmed across
+// the GPUs"): the g solves of a group are independent, so rank r takes the shifts at the LIST positions i = r (mod P), i.e. only ever factorises and
+// keeps the shifts it owns (the factor farm of SURVEY 8e-4 without shipping factors), writes its W_s into slab r of the gathered panel and
+// ONE in-place all-gather per GROUP (n g k doubles in all; round 3: one per iteration, columns sharded) completes it on every rank;
+// mixing, norms, decisions, compression and K(t) are replicated and bit-identical on all ranks.
+struct FanGroup {
+    int g = 0;
+    double mus[FAN_GMAX];
+    FanCoef co;
+    FanLayout lay;
+    std::vector<std::shared_ptr<FactorEntry<double>>> fes;      // by group position; only the positions of the ranks this process plays
+    Mat Wcat;                                                    // the gathered panel: slab r = rank r's solves side by side
+    std::chrono::steady_clock::time_point f0;
+};
+static bool trace_fan() { static const bool on = env_trace("fan"); return on; }
+static double us_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
+// The next g real shifts of the cycle at once (independent solves that share every launch).  true: a group was enqueued and recorded;
+// false: nothing was enqueued and nothing taken from the oracle — the caller goes on with one iteration.
+bool AdiRun::try_fan_group(AdiChunk& ck) {
+    if (fan_max() < 2 || fan_off) return false;
+    FanGroup G;
+    if (!fan_select(ck, G)) return false;
+    if (!fan_solves(G)) {
+        // (nothing was enqueued where the batched form does not apply — the same decision on every rank: it depends on the pencil and
+        // the context's options only — and this solve goes on one iteration at a time)
+        // (with real ranks the decision must not differ between them — it can only where a rank's own factors needed static pivots:
+        // fail loudly instead of leaving the other ranks inside a collective)
+        if (fan_ranks() > 1 && !(ctx->comm && ctx->comm->emulate > 1))
+            throw Error(ERR_INTERNAL, "sharded fan group: the batched solves do not apply to this rank's factors (static pivots); "
+                                      "run with adi_fan = 0 for this pencil");
+        fan_off = true;
+        return false;
+    }
+    fan_mix(ck, G);
+    return true;
+}
+// Which shifts the group takes, and their factors.  Expects nothing; leaves the look-ahead factorisations on the helper streams and, on
+// ctx->stream, the waits for (or the inline factorisations of) the factors of the ranks this process plays.
+bool AdiRun::fan_select(AdiChunk& ck, FanGroup& G) {
+    // (a group may cross the chunk limit — 3, 3, 3, 3 instead of 3, 3, 3, 1 iterations per chunk of 10 — unless the caller steps
+    // with a budget, the literal mode compresses at exact intervals or the chunk length is the previous solve's iteration count)
+    const bool strict = cex || ck.budget < (1 << 29) || chunk_from_hint;
+    const int room = std::min(std::min(fan_max(), opt.maxiters - iters_host), strict ? ck.limit - ck.shifts : fan_max());
+    const int gmin = opt.keep_history ? 1 : 2;          // with a history even a single iteration takes this path (its R_j stays in the slab)
+    const auto ups = room >= gmin ? oracle->peek((size_t)room) : std::vector<std::complex<double>>();
+    G.g = fan_pick(ups, room, gmin, ctx->adi_fan_max_coef, G.mus, &G.co);
+    if (G.g == 0) return false;
+    // ownership by the shift's position in the LIST (not in the group): the same shift always meets the same rank, so a rank factorises
+    // and keeps only its share of the list (adi_begin factorises that share up front)
+    G.lay = fan_layout(G.g, fan_ranks(), oracle->position(), oracle->list_size());
+    G.fes.resize((size_t)G.g);
+    const bool la = lookahead();
+    if (la) pf.ahead(std::complex<double>(0.0, 0.0), true);      // (first pass through the cycle: this group's and the next groups' factors; all waited for below)
+    for (int s_ = 0; s_ < G.g; ++s_) {
+        if (!plays_rank(G.lay.owner[s_])) continue;
+        if (la) pf.wait(std::complex<double>(G.mus[s_], 0.0));
+        auto fe = get_factor<double>(ctx, op, cache, cache->real, std::complex<double>(G.mus[s_], 0.0), true, nullptr, !la || check_now);
+        if (fe->dense) return false;              // the dense-inverse step has its own fused kernels
+        G.fes[(size_t)s_] = fe;
+    }
+    return true;
+}
+// SMW products of a rank's shifts (group positions `pos`) that this solve has not formed yet: W_U = M_s^-1 Vt for all of them in one batched
+// solve, the capacitance matrices inverted in one launch (smw.jl:19-28); at the first group of a solve (one rank) every
+// other shift of the cycle whose factor exists rides along, so that a time step pays this chain once.  Fills sz for the rank's solves.
+// false: the batched solve does not apply (nothing enqueued).
+bool AdiRun::fan_smw_setup(FanGroup& G, const std::vector<int>& pos, SmwZ& sz) {
+    const Pencil& P = *op.P;
+    const AdiState* dst = st.p;
+    std::vector<std::pair<double, std::shared_ptr<FactorEntry<double>>>> need;
+    for (int s_ : pos) if (!smw_cache.count({G.mus[s_], 0.0})) need.push_back({G.mus[s_], G.fes[(size_t)s_]});
+    if (!need.empty() && !fan_smw_all && fan_ranks() == 1) {
+        fan_smw_all = true;
+        for (auto& mv : opt.shifts.values) {
+            if (mv.imag() != 0.0 || (int)need.size() >= MF_ZMAX) continue;
+            bool dup = smw_cache.count({mv.real(), 0.0}) > 0;
+            for (auto& nd : need) dup = dup || nd.first == mv.real();
+            if (dup) continue;
+            auto itf = cache->real.find(std::make_tuple(op.tag, mv.real(), 0.0));
+            if (itf == cache->real.end() || itf->second->dense || pf.pending(mv)) continue;
+            need.push_back({mv.real(), itf->second});
+        }
+    }
+    if (!need.empty()) {
+        const int np = (int)need.size();
+        const Factor<double>* Fp[MF_ZMAX];
+        for (int z = 0; z < np; ++z) Fp[z] = &need[(size_t)z].second->f;
+        Mat WUcat(ctx, n, np * m);
+        if (!mf_solve_batch(ctx, P, Fp, np, op.Vt.p, op.Vt.ld, m, WUcat.p, WUcat.ld, m, dst)) return false;
+        Mat smu(ctx, m, np * m);
+        gemm(ctx, true, false, 1.0, op.U, WUcat, 0.0, smu, dst, "smw_small");
+        SinvZ iz; std::memset(&iz, 0, sizeof(iz));
+        for (int z = 0; z < np; ++z) {
+            SmwCacheEntry en;
+            en.keep = WUcat.buf; en.WU = WUcat.p + (size_t)z * m * WUcat.ld; en.ldwu = WUcat.ld;
+            en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(double));
+            iz.out[z] = (double*)en.sinv->p;
+            smw_cache.emplace(std::make_pair(need[(size_t)z].first, 0.0), en);
+            used_real.push_back(need[(size_t)z].second);
+        }
+        hipLaunchKernelGGL(k_sinv_z, dim3(np), dim3(64), 0, ctx->stream, m, (const double*)smu.p, smu.ld, op.alpha, iz, dst, serr());
+    }
+    for (size_t z = 0; z < pos.size(); ++z) {
+        const auto& en = smw_cache.find({G.mus[pos[z]], 0.0})->second;
+        sz.WU[z] = (const double*)en.WU; sz.ldwu[z] = en.ldwu; sz.Sinv[z] = (const double*)en.sinv->p;
+    }
+    return true;
+}
+// The g solves W_s = Z_s R of the group, SMW corrections included, rank by rank into the slabs of G.Wcat.  Expects R on ctx->stream and the
+// group's factors; leaves the pending norms flushed and the solves enqueued.  false: the batched form does not apply, nothing was enqueued.
+bool AdiRun::fan_solves(FanGroup& G) {
+    const Pencil& P = *op.P;
+    const AdiState* dst = st.p;
+    double* const ft = ctx->trace.fan_t;
+    G.f0 = std::chrono::steady_clock::now();
+    dense_norm_flush(ctx, k, Tm, tdiag, alpha_res, st.p, &npend);
+    const int gp = G.lay.gp;
+    G.Wcat = Mat(ctx, n, fan_ranks() * gp * k);
+    for (int r = 0; r < fan_ranks(); ++r) {
+        if (!plays_rank(r)) continue;
+        const std::vector<int>& pos = G.lay.pos[(size_t)r];            // this rank's group positions
+        const int gr = (int)pos.size();
+        if (gr == 0) continue;
+        SmwZ sz; std::memset(&sz, 0, sizeof(sz));
+        if (op.has_lr && !fan_smw_setup(G, pos, sz)) return false;
+        const Factor<double>* Fs[MF_ZMAX];
+        for (int z = 0; z < gr; ++z) Fs[z] = &G.fes[(size_t)pos[(size_t)z]]->f;
+        Mat Wr = G.Wcat.colsview(r * gp * k, gr * k);          // slab r: its solves side by side
+        const auto f1 = std::chrono::steady_clock::now();
+        const bool ok = mf_solve_batch(ctx, P, Fs, gr, R.p, R.ld, k, Wr.p, Wr.ld, k, dst);
+        if (trace_fan()) { ft[0] += us_between(G.f0, f1); ft[1] += us_between(f1, std::chrono::steady_clock::now()); }
+        if (!ok) return false;
+        for (int s_ : pos) used_real.push_back(G.fes[(size_t)s_]);
+        if (op.has_lr) {
+            // W_s <- W_s - W_U,s (S_s^-1 (U' W_s))  for the rank's solves: one product U' [W_s ...], one apply launch (in place)
+            Mat sm(ctx, m, gr * k);
+            gemm(ctx, true, false, 1.0, op.U, Wr, 0.0, sm, dst, "smw_small");
+            TimedScope ts(ctx, "smw_apply", 8.0 * n * gr * (2.0 * k + m), 2.0 * n * gr * (double)k * m, gr);
+            hipLaunchKernelGGL(k_smw_apply_z, dim3(ceil_div(n, 256), ceil_div(k, SMW_CB), gr), dim3(256), 0, ctx->stream, n, m, k, Wr.p, Wr.ld, sz,
+                               (const double*)sm.p, sm.ld, dst);
+        }
+    }
+    return true;
+}
+// Gather, mix and book: V_j = sum_s c_js W_s,  R_j = R_0 - sum_s d_js E' W_s  for the g iterations in one pass over E' and the panels, then
+// the g shifts are taken from the oracle and recorded, and the norms and decisions follow in iteration order.  Expects the solves of
+// fan_solves on ctx->stream; leaves R = R_g (a buffer of its own per iteration) and the group's norm launches.
+void AdiRun::fan_mix(AdiChunk& ck, FanGroup& G) {
+    const Pencil& P = *op.P;
+    const AdiState* dst = st.p;
+    const int g = G.g, fan_P = fan_ranks();
+    auto fnow = []() { return std::chrono::steady_clock::now(); };
+    if (fan_P > 1 && !(ctx->comm->emulate > 1)) {
+        TimedScope ts(ctx, "comm_allgather_w", 8.0 * n * (double)fan_P * G.lay.gp * k, 0.0);
+        comm_allgather_inplace(ctx, *ctx->comm, G.Wcat.p, (size_t)n * G.lay.gp * k);
+    }
+    const auto f2 = fnow();
+    Mat Vcat, Rcat;
+    if (opt.keep_history) {
+        // every iteration of the chunk side by side (the Rosenbrock-1 driver reads E'V_j = (R_{j-1} - R_j) / (2 mu_j) off these slabs)
+        const int cap = ck.limit + FAN_GMAX;
+        if (ck.hist_V.empty()) { ck.hist_V = Mat(ctx, n, cap * k); ck.hist_R = Mat(ctx, n, cap * k); }
+        if (ck.shifts + g <= cap) { Vcat = ck.hist_V.colsview(ck.shifts * k, g * k); Rcat = ck.hist_R.colsview(ck.shifts * k, g * k); }
+        else hist_ok = false;
+    }
+    if (Vcat.p == nullptr) { Vcat = Mat(ctx, n, g * k); Rcat = Mat(ctx, n, g * k); }
+    fan_spmm_mix(ctx, P, G.Wcat, R, Vcat, Rcat, g, k, G.co, G.lay.slots, dst);
+    const auto f3 = fnow();
+    for (int j = 0; j < g; ++j) {
+        const std::complex<double> muj = oracle->take(&res.warnings);
+        all_shifts.push_back(muj);
+        Mat Vj = Vcat.colsview(j * k, k), Rj = Rcat.colsview(j * k, k);
+        Xw->blocks.push_back({Vj, Tm, -2.0 * muj.real() * alpha_res, tdiag});
+        iters_host += 1; last_compression += 1;
+        oracle->update(Rj, {Vj});
+        ck.ledger.add(iters_host, Xw->blocks.size(), 1, Rj);
+        ++ck.since_sync; ++ck.shifts;
+    }
+    const auto f4 = fnow();
+    apply_tolerance();
+    residual_norm_group_diag(ctx, Rcat, g, k, Tm, tdiag, alpha_res, st.p, iters_host - g);
+    R = Rcat.colsview((g - 1) * k, k);
+    if (trace_fan()) {
+        double* const ft = ctx->trace.fan_t; long& fn_ = ctx->trace.fan_n;
+        const auto f5 = fnow();
+        ft[2] += us_between(f2, f3); ft[3] += us_between(f3, f4); ft[4] += us_between(f4, f5); ft[5] += us_between(G.f0, f5);
+        if (++fn_ % 128 == 0) std::fprintf(stderr, "[fan host, us per group] before the solves %.1f | batched solves %.1f | mix %.1f | bookkeeping %.1f | norms %.1f | total %.1f\n",
+                                           ft[0] / fn_, ft[1] / fn_, ft[2] / fn_, ft[3] / fn_, ft[4] / fn_, ft[5] / fn_);
+    }
+}
+
+// ---- adi_advance: one iteration at a time ------------------------------------------------------------------------------------------------
+// Dense-inverse step: one stacked GEMM + one fused apply (V and the residual recurrence).  Expects R on ctx->stream; leaves V and the updated
+// R there and, for k <= 96 (*rode), also the norm of this iteration riding on the step kernel (npend).
+Mat AdiRun::dense_inverse_step(double mu, FactorEntry<double>& fe, bool* rode) {
+    const Pencil& P = *op.P;
+    const AdiState* dst = st.p;
+    const auto key = std::make_pair(mu, 0.0);
+    auto sc = smw_cache.find(key);
+    const int mm = op.has_lr ? m : 0;
+    if (fe.stack.empty() || fe.stack_U != (const void*)op.U.p || fe.stack_m != mm) {
+        Mat stk(ctx, 2 * n + mm, n);
+        { Mat top = stk.view(0, 0, n, n); copy_mat(ctx, fe.dinv, top); }
+        { Mat mid = stk.view(n, 0, n, n); spmm(ctx, P, P.valEt.p, fe.dinv, mid, 1.0, 0.0, nullptr); }
+        if (mm) { Mat bot = stk.view(2 * n, 0, mm, n); gemm(ctx, true, false, 1.0, op.U, fe.dinv, 0.0, bot, nullptr, "gemm_dinv"); }
+        fe.stack = stk; fe.stack_U = (const void*)op.U.p; fe.stack_m = mm;
+    }
+    const int lds_ = 2 * n + mm;
+    Mat V1(ctx, n, k);
+    if (op.has_lr && sc == smw_cache.end()) {
+        Mat WK(ctx, lds_, m);
+        gemm(ctx, false, false, 1.0, fe.stack, op.Vt, 0.0, WK, dst, "gemm_dinv");
+        Mat WKS(ctx, 2 * n, m);
+        sc = smw_capacitance<double>(key, WKS.buf, WKS.p, WKS.ld, WK.p + 2 * (size_t)n, WK.ld);
+        hipLaunchKernelGGL(k_fold_sinv, dim3(ceil_div(2 * n * m, 256)), dim3(256), 0, ctx->stream, 2 * n, m, WK.p, WK.ld,
+                           (const double*)sc->second.sinv->p, WKS.p, WKS.ld, dst);
+    }
+    if (k <= 96) {
+        // split-K slabs of the stacked GEMM are consumed directly by the fused step kernel
+        int zs = 1;
+        BufP wpart = gemm_partials(ctx, false, false, lds_, k, n, fe.stack.p, fe.stack.ld, R.p, R.ld, &zs, dst, "gemm_dinv");
+        dense_adi_step(ctx, n, mm, k, zs, (const double*)wpart->p, op.has_lr ? (const double*)sc->second.WU : nullptr,
+                       op.has_lr ? sc->second.ldwu : 0, V1, R, 2.0 * mu, Tm, tdiag, alpha_res, st.p, iters_host + 1,
+                       &npend);
+        *rode = true;
+    } else {
+        Mat Wst(ctx, lds_, k);
+        gemm(ctx, false, false, 1.0, fe.stack, R, 0.0, Wst, dst, "gemm_dinv");
+        TimedScope ts(ctx, "dense_apply", 8.0 * n * (4.0 * k + 2.0 * m), 4.0 * n * k * m);
+        if (op.has_lr)
+            hipLaunchKernelGGL((k_dense_apply<true>), dim3(ceil_div(n, 64), ceil_div(k, 4)), dim3(256), 0, ctx->stream,
+                               n, m, k, Wst.p, Wst.ld, (const double*)sc->second.WU, sc->second.ldwu,
+                               V1.p, V1.ld, R.p, R.ld, 2.0 * mu, dst);
+        else
+            hipLaunchKernelGGL((k_dense_apply<false>), dim3(ceil_div(n, 64), ceil_div(k, 4)), dim3(256), 0, ctx->stream,
+                               n, 0, k, Wst.p, Wst.ld, (const double*)nullptr, 0,
+                               V1.p, V1.ld, R.p, R.ld, 2.0 * mu, dst);
+    }
+    return V1;
+}
+// ---- column-sharded step: V = (F' + mu E')^-1 R acts column by column (adi.jl:158-159), so rank g
+// solves its 16-column tiles of R only (multifrontal sweeps + SMW, both column local), writes them into its block of the
+// gathered panel and ONE in-place all-gather (RCCL, on this stream) completes V on every rank.  The m columns M^-1 Vt of
+// the SMW correction are computed by every rank that owns columns (replicated: m = 7 against k/P).
+// Expects R and the factor on ctx->stream; leaves V and the updated R (replicated) there.
+Mat AdiRun::column_sharded_step(double mu, FactorEntry<double>& fe) {
+    const Pencil& P = *op.P;
+    const AdiState* dst = st.p;
+    const auto key = std::make_pair(mu, 0.0);
+    Comm& cm = *ctx->comm;
+    const int Pn = std::max(cm.nranks, cm.emulate);
+    const ColBlocks cb(k, Pn);
+    Mat Vg(ctx, n, cb.padded());
+    auto local = [&](int g) {
+        const int c0 = cb.c0(g), kc = cb.c1(g) - c0;
+        if (kc <= 0) return;
+        auto scl = smw_cache.find(key);
+        const bool havel = op.has_lr && scl != smw_cache.end();
+        const int extra = (op.has_lr && !havel) ? m : 0;
+        Mat Vloc = Vg.colsview(c0, kc);
+        if (!op.has_lr) {
+            mf_solve_from(ctx, P, fe.f, R.p + (size_t)c0 * R.ld, R.ld, kc, Vloc.p, Vloc.ld, kc, dst);
+            return;
+        }
+        Mat W(ctx, n, kc + extra);
+        if (extra) { Mat d = W.colsview(kc, m); copy_mat(ctx, op.Vt, d, 1.0, dst); }
+        mf_solve_from(ctx, P, fe.f, R.p + (size_t)c0 * R.ld, R.ld, kc, W.p, W.ld, kc + extra, dst);
+        Mat small(ctx, m, kc + extra);
+        gemm(ctx, true, false, 1.0, op.U, W, 0.0, small, dst, "smw_small");
+        if (!havel) scl = smw_capacitance<double>(key, W.buf, W.p + (size_t)kc * W.ld, W.ld, small.p + (size_t)kc * small.ld, small.ld);
+        TimedScope ts(ctx, "smw_apply", 8.0 * n * (2.0 * kc + m), 2.0 * n * kc * m);
+        hipLaunchKernelGGL((k_smw_apply<double, true>), dim3(ceil_div(n, 256), ceil_div(kc, SMW_CB)), dim3(256), 0, ctx->stream,
+                           n, m, kc, W.p, W.ld, (const double*)scl->second.WU, scl->second.ldwu, (const double*)scl->second.sinv->p,
+                           small.p, small.ld, Vloc.p, Vloc.ld, (double*)nullptr, 0, 0.0, dst);
+    };
+    if (cm.emulate > 1) { for (int g = 0; g < Pn; ++g) local(g); }
+    else {
+        local(cm.rank);
+        TimedScope ts(ctx, "comm_allgather_v", 8.0 * n * (double)cb.padded(), 0.0);
+        comm_allgather_inplace(ctx, cm, Vg.p, (size_t)n * cb.width());
+    }
+    Mat V1 = Vg.colsview(0, k);
+    spmm(ctx, P, P.valEt.p, V1, R, -2.0 * mu, 1.0, dst);          // R <- R - 2 mu E' V   (adi.jl:171), replicated
+    return V1;
+}
+// The plain real step: multifrontal sweeps (fe) or the user's block solver (fe == nullptr), SMW correction, R <- R - 2 mu E' V.
+// Expects R on ctx->stream; leaves V and the updated R there.
+Mat AdiRun::sparse_step(std::complex<double> mu, FactorEntry<double>* fe) {
+    const Pencil& P = *op.P;
+    const AdiState* dst = st.p;
+    const auto key = std::make_pair(mu.real(), 0.0);
+    auto sc = smw_cache.find(key);
+    const bool have = op.has_lr && sc != smw_cache.end();
+    const int ncols = k + ((op.has_lr && !have) ? m : 0);
+    Mat V1, W(ctx, n, ncols);
+    if (!fe) { Mat d = W.colsview(0, k); copy_mat(ctx, R, d, 1.0, dst); }
+    if (op.has_lr && !have) { Mat d = W.colsview(k, m); copy_mat(ctx, op.Vt, d, 1.0, dst); }
+    if (!fe) user_block_solve(ctx, op, opt, mu, W, nullptr);
+    else mf_solve_from(ctx, P, fe->f, R.p, R.ld, k, W.p, W.ld, ncols, dst);     // the residual block is read where it is
+    if (op.has_lr) {
+        V1 = Mat(ctx, n, k);
+        // small = U' W: a skinny split-K MFMA GEMM (the one-workgroup-per-column kernel is latency bound at large n).  (Letting the
+        // SMW kernels sum the slabs themselves saves the reduction launch and is neutral at n = 5177, but every one of the 1264
+        // workgroups of the apply kernel then sums its 56 entries over 80 slabs at n = 20209: 59 us against 20 + 10 — reverted.)
+        Mat small(ctx, m, ncols);
+        gemm(ctx, true, false, 1.0, op.U, W, 0.0, small, dst, "smw_small");
+        if (!have) sc = smw_capacitance<double>(key, W.buf, W.p + (size_t)k * W.ld, W.ld, small.p + (size_t)k * small.ld, small.ld);
+        TimedScope ts(ctx, "smw_apply", 8.0 * n * (2.0 * k + m), 2.0 * n * k * m);
+        hipLaunchKernelGGL((k_smw_apply<double, true>), dim3(ceil_div(n, 256), ceil_div(k, SMW_CB)), dim3(256), 0, ctx->stream,
+                           n, m, k, W.p, W.ld, (const double*)sc->second.WU, sc->second.ldwu, (const double*)sc->second.sinv->p,
+                           small.p, small.ld, V1.p, V1.ld, (double*)nullptr, 0, 0.0, dst);
+    } else {
+        V1 = W;
+    }
+    // R <- R - 2 mu E' V   (adi.jl:171)
+    spmm(ctx, P, P.valEt.p, V1, R, -2.0 * mu.real(), 1.0, dst);
+    return V1;
+}
+// One real shift (adi.jl:157-174): the factor, then the dense-inverse, the column-sharded or the plain step.  Expects R and the look-ahead's
+// event for mu waited for on ctx->stream; leaves the step's kernels there, the increment in Xw and the oracle updated.
+Mat AdiRun::real_step(std::complex<double> mu, bool* norm_done, bool* rode) {
+    // dense inverses pay off only for shift lists that persist across Lyapunov solves (user-given Cyclic values)
+    const bool user_inner = opt.inner_solve != nullptr;
+    std::shared_ptr<FactorEntry<double>> fe;
+    if (!user_inner) {
+        if (single_use() && trace_prefetch()) {
+            long &hit = ctx->trace.rl_hit, &miss = ctx->trace.rl_miss;
+            (cache->real.count(std::make_tuple(op.tag, mu.real(), 0.0)) ? hit : miss)++;
+            if ((hit + miss) % 500 == 0) std::fprintf(stderr, "[prefetch] real shifts: %ld found ready, %ld factorised inline\n", hit, miss);
+        }
+        fe = get_factor<double>(ctx, op, cache, cache->real, mu, cyclic_in(), nullptr, !lookahead() || check_now);
+        used_real.push_back(fe);
+    }
+    Mat V1;
+    if (fe && fe->dense) {
+        V1 = dense_inverse_step(mu.real(), *fe, rode);
+        *norm_done = *rode;
+    } else if (!user_inner && ctx->comm && std::max(ctx->comm->nranks, ctx->comm->emulate) > 1 && k >= ctx->shard_min_cols) {
+        V1 = column_sharded_step(mu.real(), *fe);
+    } else {
+        V1 = sparse_step(mu, fe.get());
+    }
+    Xw->blocks.push_back({V1, Tm, -2.0 * mu.real() * alpha_res, tdiag});
+    iters_host += 1; last_compression += 1;
+    oracle->update(R, {V1});
+    return V1;
+}
+// A conjugate pair as one double step (adi.jl:190-220); mu was taken, its partner is taken here.  Expects R on ctx->stream; leaves V1, V2 and
+// the updated R there, both increments in Xw and the oracle updated.
+void AdiRun::complex_pair(std::complex<double> mu, Mat& V1, Mat& V2) {
+    const Pencil& P = *op.P;
+    const AdiState* dst = st.p;
+    std::complex<double> mu2 = oracle->take(&res.warnings);
+    all_shifts.push_back(mu2);
+    DRE_REQUIRE(std::abs(mu2 - std::conj(mu)) <= 1e-8 * std::abs(mu), "complex shifts must come in conjugate pairs (adi.jl:190)");
+    V1 = Mat(ctx, n, k);
+    V2 = Mat(ctx, n, k);
+    const bool user_inner = opt.inner_solve != nullptr;
+    std::shared_ptr<FactorEntry<cplx>> fe;
+    if (!user_inner) {
+        if (single_use() && trace_prefetch()) {
+            long &hit = ctx->trace.cx_hit, &miss = ctx->trace.cx_miss;
+            (cache->cplx_.count(std::make_tuple(op.tag, mu.real(), mu.imag())) ? hit : miss)++;
+            if ((hit + miss) % 500 == 0) std::fprintf(stderr, "[prefetch] complex pairs: %ld found ready, %ld factorised inline\n", hit, miss);
+        }
+        fe = get_factor<cplx>(ctx, op, cache, cache->cplx_, mu, true, nullptr, !lookahead() || check_now);
+        used_cplx.push_back(fe);
+    }
+    auto key = std::make_pair(mu.real(), mu.imag());
+    auto sc = smw_cache.find(key);
+    const bool have = op.has_lr && sc != smw_cache.end();
+    const int ncols = k + ((op.has_lr && !have) ? m : 0);
+    auto Wb = std::make_shared<Buf>(ctx, (size_t)n * ncols * sizeof(cplx));
+    cplx* W = (cplx*)Wb->p;
+    {
+        size_t tot = (size_t)n * k;
+        hipLaunchKernelGGL(k_real_to_cplx, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, n, k, R.p, R.ld, W, n, dst);
+        if (op.has_lr && !have) {
+            tot = (size_t)n * m;
+            hipLaunchKernelGGL(k_real_to_cplx, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, n, m, op.Vt.p, op.Vt.ld, W + (size_t)k * n, n, dst);
+        }
+    }
+    if (user_inner) {
+        // the real right-hand side [R, Vt] goes to the user's solver; the complex solution comes back interleaved
+        Mat Wr(ctx, n, ncols);
+        { Mat d = Wr.colsview(0, k); copy_mat(ctx, R, d, 1.0, dst); }
+        if (op.has_lr && !have) { Mat d = Wr.colsview(k, m); copy_mat(ctx, op.Vt, d, 1.0, dst); }
+        user_block_solve(ctx, op, opt, mu, Wr, W);
+    } else mf_solve<cplx>(ctx, P, fe->f, W, n, ncols, dst);
+    const double delta = mu.real() / mu.imag();
+    if (op.has_lr) {
+        auto sb = std::make_shared<Buf>(ctx, (size_t)m * ncols * sizeof(cplx));
+        cplx* small = (cplx*)sb->p;
+        hipLaunchKernelGGL((k_smw_small<cplx>), dim3(ncols), dim3(256), 0, ctx->stream, n, m, op.U.p, op.U.ld, W, n, small, m, dst);
+        if (!have) sc = smw_capacitance<cplx>(key, Wb, W + (size_t)k * n, n, small + (size_t)k * m, m);
+        hipLaunchKernelGGL((k_smw_apply<cplx, true>), dim3(ceil_div(n, 256), ceil_div(k, SMW_CB)), dim3(256), 0, ctx->stream,
+                           n, m, k, W, n, (const cplx*)sc->second.WU, sc->second.ldwu, (const cplx*)sc->second.sinv->p,
+                           small, m, V1.p, V1.ld, V2.p, V2.ld, delta, dst);
+    } else {
+        hipLaunchKernelGGL((k_smw_apply<cplx, false>), dim3(ceil_div(n, 256), ceil_div(k, SMW_CB)), dim3(256), 0, ctx->stream,
+                           n, 0, k, W, n, (const cplx*)nullptr, 0, (const cplx*)nullptr, (const cplx*)nullptr, 0,
+                           V1.p, V1.ld, V2.p, V2.ld, delta, dst);
+    }
+    zero_increment_guard(ctx, V1, V2, st.p, 2);       // adi.jl:200-204
+    // R <- R - 2 sqrt2 Re(mu) E' V1   (adi.jl:217)
+    spmm(ctx, P, P.valEt.p, V1, R, -2.0 * 1.4142135623730951 * mu.real(), 1.0, dst);
+    Xw->blocks.push_back({V1, Tm, -2.0 * mu.real() * alpha_res, tdiag});
+    Xw->blocks.push_back({V2, Tm, -2.0 * mu.real() * alpha_res, tdiag});
+    iters_host += 2; last_compression += 2;
+    oracle->update(R, {V1, V2});
+}
+// One iteration outside the fan path: a real shift or a conjugate pair, with its norm and its record.  Expects R on ctx->stream.  false: the
+// chunk closes first (nothing was enqueued; a shift the oracle handed out while stopping is dropped with the chunk).
+bool AdiRun::one_step(AdiChunk& ck) {
+    apply_tolerance();
+    if (defer) {
+        // an iteration outside the fan path while the tolerance is still on its way: close the chunk first (its end resolves the tolerance)
+        if (!ck.ledger.empty()) return false;
+        resolve_deferred();
+    }
+    hist_ok = false;                  // (its residual factor is updated in place: no history of this solve)
+    std::complex<double> mu;
+    { RoctxRange rr("shifts"); mu = oracle->take(&res.warnings); }        // adi.jl:101
+    // (a refill that found the solve converged: the rest of the chunk would be early-exit launches with a synchronisation per refill)
+    if (oracle->stopped() && !ck.ledger.empty()) return false;
+    all_shifts.push_back(mu);
+    const bool is_real = (mu.imag() == 0.0);
+    RoctxRange roctx_solve(is_real ? "solve (real)" : "solve (complex)");        // adi.jl:157,196 (the range covers the whole step)
+    if (lookahead()) { pf.wait(mu); pf.ahead(mu); pf.wait(mu); }        // (the batch may carry the shift in hand: its event is waited for behind it)
+    Mat V1, V2;
+    bool norm_done = false, rode = false;
+    if (is_real) V1 = real_step(mu, &norm_done, &rode);
+    else complex_pair(mu, V1, V2);
+    // residual norm through the Gram matrix, convergence decision on the device
+    if (!rode) dense_norm_flush(ctx, k, Tm, tdiag, alpha_res, st.p, &npend);     // a step of another kind: norms stay in order
+    if (!norm_done) residual_norm_step(ctx, R, Tm, tdiag, alpha_res, st.p, iters_host);
+    ck.ledger.add(iters_host, Xw->blocks.size(), is_real ? 1 : 2, R);
+    ++ck.since_sync; ck.shifts += is_real ? 1 : 2;
+    return true;
+}
+// Synchronise once per chunk and find out how far the device really got: flush the norms, resolve the tolerance, fetch the control block,
+// replay the ledger, record the history, raise errors and warnings.  Expects the chunk's iterations on ctx->stream; leaves the stream idle and
+// R, Xw, the norms and the counters at the last accepted iteration.
+void AdiRun::close_chunk(AdiChunk& ck) {
+    static const int chunk_timing = (env_trace("chunk") ? 1 : 0);
+    dense_norm_flush(ctx, k, Tm, tdiag, alpha_res, st.p, &npend);
+    const bool was_deferred = defer;
+    resolve_deferred();
+    AdiState h;
+    const auto ct1 = std::chrono::steady_clock::now();
+    ctx_fetch(ctx, st.p, sizeof(AdiState), &h);
+    if (was_deferred || abstol_pending) {
+        abstol = h.abstol; res.abstol = h.abstol; res.initial_norm = h.norms[0];
+        if (!res.norms.empty()) res.norms[0] = h.norms[0];
+        abstol_pending = false;
+    }
+    if (chunk_timing) {
+        double &enq = ctx->trace.ch_enq, &wait = ctx->trace.ch_wait; long &nch = ctx->trace.ch_n, &nit_ = ctx->trace.ch_it;
+        const auto ct2 = std::chrono::steady_clock::now();
+        enq += us_between(ck.t0, ct1); wait += us_between(ct1, ct2);
+        nit_ += (long)ck.ledger.size();
+        if (++nch % 64 == 0) std::fprintf(stderr, "[chunk timing] %ld chunks, %ld iterations: host enqueue %.1f us / iteration, wait at the synchronisation %.1f us / iteration\n",
+                                          nch, nit_, enq / nit_, wait / nit_);
+    }
+    const auto rp = ck.ledger.replay(h.iters);
+    R = rp.last ? *rp.last : ck.R_start;                  // (fan groups leave every residual in a buffer of its own)
+    for (int it : rp.accepted) { res.norms.push_back(h.norms[it & 511]); res.norm_iters.push_back(it); }
+    Xw->blocks.resize(rp.nblocks);
+    check_used();
+    last_compression = ck.lc_before + rp.nshifts;
+    res.iters = h.iters;
+    res.res_norm = h.res_norm;
+    if (opt.keep_history && hist_ok) {
+        const int acc = std::max(0, std::min(h.iters, iters_host) - ck.iters_start);        // accepted iterations of this chunk
+        if (acc > 0 && !ck.hist_V.empty()) {
+            AdiHistChunk hc;
+            hc.R0 = ck.R_start; hc.Rs = ck.hist_R.colsview(0, acc * k); hc.Vs = ck.hist_V.colsview(0, acc * k);
+            for (int j = 0; j < acc; ++j) hc.mu.push_back(all_shifts[(size_t)ck.iters_start + j].real());
+            res.hist.push_back(std::move(hc));
+        } else if (acc > 0) hist_ok = false;
+    }
+    if (h.smw_singular) throw Error(ERR_SINGULAR, "SMW: capacitance matrix is singular");
+    if (h.collapsed == 2) res.warnings |= 2;          // DRE_WARN_ZERO_INCREMENT: the iteration collapsed (adi.jl:134-137)
+    if (h.done || ck.ledger.empty()) finished = true;
+}
+// The interval compression of adi.jl:72-76, where it is due and not put off.  Expects a closed chunk (stream idle).
+void AdiRun::maybe_compress() {
+    if (!(opt.compression && last_compression >= opt.compression_interval && (!finished || cex))) return;
+    // Small n: the compression works on the n x n matrix L D L' whatever the number of columns, and the increments
+    // never depend on X, so the intermediate compressions of adi.jl:72-76 are deferred to the final one
+    // (adi.jl:78-80) as long as the uncompressed factor stays small.
+    // The same holds for the direct form up to compress_direct_max_n (one GEMM over all columns) and for the factor form
+    // (panel steps ~ rank, GEMM traffic ~ columns: one late compression costs the GEMMs of two early ones and half the
+    // panels) while the factor still fits the factor-form limit c + 64 <= n after the next chunk.
+    const long rk = Xw->rank(), next = (long)std::max(opt.compression_interval * 2, chunk_limit + FAN_GMAX) * k;
+    const bool free_form = opt.given_residual && opt.keep_history && !opt.final_compress && ctx->recurrence_wide != 0 && hist_ok;
+    const bool put_off = free_form || (!cex && (n <= 512 ? rk <= 16L * n
+                               : ((n <= ctx->compress_direct_max_n && rk <= 16L * n) ||
+                                  (n >= ctx->compress_factor_min_n && rk + next + 64 <= n))));
+    if (!put_off) {
+        ldlt_compress(ctx, *Xw, ctf, cex);
+        last_compression = 0;
+        hist_ok = false;              // (the increments are no longer the V_j)
+    }
 }
 
 // One chunk: up to `budget` shifts are enqueued speculatively (at least one; a conjugate pair counts two and is never split), then one
 // synchronisation tells how far the device got.  budget = 1 is the reference's step! (adi.jl:97-128).
 void adi_advance(AdiRun& run, int budget) {
-    static const bool trace_prefetch = env_trace("prefetch");
     if (run.finished) return;
-    Ctx* ctx = run.ctx;
-    const GaleOperator& op = run.op;
-    const Pencil& P = *op.P;
-    const int n = run.n, k = run.k, m = run.m;
-    FactorCache* cache = run.cache;
-    AdiResult& res = run.res;
-    const AdiOptions& opt = run.opt;
-    const AdiOptions& opt_in = run.opt_in;
-    const double ctf = run.ctf, alpha_res = run.alpha_res;
-    const bool cex = run.cex, tdiag = run.tdiag;
-    Mat& R = run.R; Mat& Tm = run.Tm;
-    auto& oracle = run.oracle;
-    auto& st = run.st;
-    auto& smw_cache = run.smw_cache;
-    int* const serr = &st.p->smw_singular;     // lives in the control block: comes back with every chunk synchronisation
-    auto& Xw = run.Xw;
-    int& iters_host = run.iters_host; int& last_compression = run.last_compression;
-    auto& all_shifts = run.all_shifts;
-    bool& finished = run.finished;
-    auto& used_real = run.used_real; auto& used_cplx = run.used_cplx;
-    auto& npend = run.npend;
-    auto& resid = run.resid;
-    const int chunk_limit = std::max(1, std::min(std::min(run.chunk_limit, budget), 480));     // (< 512: ring of the norm history)
-    auto check_used = [&]() { run.check_used(); };
-    (void)P; (void)opt_in; (void)serr;
-    if (run.fast) {
-        const int nstrip = adi_fast_nstrip(n), kst = adi_fast_kst(n);
-        if (!run.fast_ready) {
-            run.Gm = Mat(ctx, k * k, 2);
-            run.nws = DevArr<double>(ctx, ADI_FAST_NWS);
-            DRE_HIP(hipMemsetAsync(run.nws.p, 0, (ADI_FAST_NWS) * sizeof(double), ctx->stream));
-            run.fast_ready = true;
-        }
-        Mat& Gm = run.Gm; auto& nws = run.nws;
-        size_t& cyc = run.cyc;                // position in the cycle
-        auto& fast_fe = run.fast_fe; auto& fast_pack = run.fast_pack;
-        {
-            const int base_it = iters_host;
-            // one more iteration than the previous solve needed; the two flush launches deliver the decisions of the last two
-            const int fast_chunk = cache->iters_hint > 0 ? std::max(opt.compression_interval, cache->iters_hint + 1) : run.chunk_limit;
-            const int nit = std::min(std::min(std::min(std::max(1, fast_chunk), std::max(1, budget)), opt.maxiters - iters_host), 480);
-            if (nit <= 0) { finished = true; resid->blocks[0].L = R; return; }
-            Mat Rring(ctx, n, k * nit), Vall(ctx, n, k * nit);
-            const size_t blocks_before = Xw->blocks.size();
-            const size_t cyc_before = cyc;
-            AdiFastArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.n = n; a.k = k; a.nstrip = nstrip; a.kst = kst; adi_fast_pick(n, k, &a.mode, &a.nt);
-            a.T = Tm.p; a.ldt = Tm.ld; a.tdiag = tdiag ? 1 : 0; a.alpha = alpha_res; a.st = st.p; a.nws = nws.p;
-            // the residual also in the B-operand lane order (dense.hpp, AdiFastArgs::Rpc): slot 0 = the chunk's input, slot j = after iteration j
-            const bool use_pk = a.mode == 0;
-            const size_t rpd = adi_fast_rpack_doubles(n, k);
-            DevArr<double> Rpk(ctx, use_pk ? rpd * (size_t)(nit + 1) : 1);
-            if (use_pk) adi_fast_pack_r(ctx, n, k, R.p, R.ld, Rpk.p, st.p);
-            for (int j = 1; j <= nit; ++j) {
-                const std::complex<double> mu = opt.shifts.values[cyc % opt.shifts.values.size()];
-                all_shifts.push_back(mu);
-                used_real.push_back(fast_fe[cyc % fast_fe.size()]);
-                a.Apack = fast_pack[cyc % fast_pack.size()];
-                if (j == 1) { a.Rcur = R.p; a.ldr = R.ld; } else { a.Rcur = Rring.p + (size_t)(j - 2) * k * Rring.ld; a.ldr = Rring.ld; }
-                a.Rnext = Rring.p + (size_t)(j - 1) * k * Rring.ld; a.ldr_next = Rring.ld;
-                a.Rpc = use_pk ? Rpk.p + (size_t)(j - 1) * rpd : nullptr;
-                a.Rpn = use_pk ? Rpk.p + (size_t)j * rpd : nullptr;
-                Mat Vj = Vall.colsview((j - 1) * k, k);
-                a.V = Vj.p; a.ldv = Vj.ld;
-                a.two_mu = 2.0 * mu.real();
-                const int g = base_it + j;                                  // shifts consumed after this iteration
-                // this launch also forms the Gram matrix of its INPUT residual (iteration g - 1) and decides on iteration g - 2
-                a.G_prev = j >= 2 ? Gm.p + (size_t)((g - 1) & 1) * k * k : nullptr;
-                a.G_prev2 = j >= 3 ? Gm.p + (size_t)((g - 2) & 1) * k * k : nullptr;
-                a.it_prev2 = g - 2; a.do_strips = 1;
-                adi_fast_iter(ctx, a);
-                Xw->blocks.push_back({Vj, Tm, -2.0 * mu.real() * alpha_res, tdiag});
-                ++cyc; ++iters_host;
-            }
-            {   // drain the norm pipeline: Gram matrix of the last residual, decisions for the last two iterations of the chunk
-                const int g = base_it + nit;
-                a.do_strips = 0; a.Apack = nullptr; a.Rnext = nullptr; a.V = nullptr;
-                a.Rpc = use_pk ? Rpk.p + (size_t)nit * rpd : nullptr; a.Rpn = nullptr;
-                a.Rcur = Rring.p + (size_t)(nit - 1) * k * Rring.ld; a.ldr = Rring.ld;
-                a.G_prev = Gm.p + (size_t)(g & 1) * k * k;
-                a.G_prev2 = nit >= 2 ? Gm.p + (size_t)((g - 1) & 1) * k * k : nullptr;
-                a.it_prev2 = g - 1;
-                adi_fast_iter(ctx, a);
-                a.G_prev = nullptr;
-                a.G_prev2 = Gm.p + (size_t)(g & 1) * k * k;
-                a.it_prev2 = g;
-                adi_fast_iter(ctx, a);
-            }
-            AdiState h;
-            DRE_HIP(hipMemcpyAsync(&h, st.p, sizeof(AdiState), hipMemcpyDeviceToHost, ctx->stream));
-            DRE_HIP(hipStreamSynchronize(ctx->stream));
-            const int acc_it = std::min(std::max(h.iters - base_it, 0), nit);          // accepted iterations of this chunk
-            for (int j = 1; j <= acc_it; ++j) { res.norms.push_back(h.norms[(base_it + j) & 511]); res.norm_iters.push_back(base_it + j); }
-            Xw->blocks.resize(blocks_before + acc_it);
-            check_used();
-            if (acc_it > 0) R = Rring.colsview((acc_it - 1) * k, k);
-            iters_host = base_it + acc_it;
-            all_shifts.resize(iters_host);
-            cyc = cyc_before + acc_it;
-            last_compression += acc_it;
-            res.iters = h.iters;
-            res.res_norm = h.res_norm;
-            if (h.done || acc_it < nit) finished = true;
-            // (literal mode: the interval compression also runs after the LAST step, before the observer looks — adi.jl:111-119; it is the
-            // compression adi.jl:78-80 would do anyway)
-            if (opt.compression && last_compression >= opt.compression_interval && (!finished || cex)) {
-                const long rk = Xw->rank();
-                const bool defer = !cex && (n <= 512 ? rk <= 16L * n : (n <= ctx->compress_direct_max_n && rk <= 16L * n));
-                if (!defer) { ldlt_compress(ctx, *Xw, ctf, cex); last_compression = 0; }
-            }
-        }
-        resid->blocks[0].L = R;                 // the residual factor after the last accepted iteration
-        return;
+    if (run.fast) { run.advance_fast(budget); return; }
+    AdiChunk ck;
+    ck.budget = budget;
+    ck.limit = std::max(1, std::min(std::min(run.chunk_limit, budget), 480));     // (< 512: ring of the norm history)
+    ck.ledger.blocks_before = run.Xw->blocks.size();
+    ck.lc_before = run.last_compression;
+    ck.iters_start = run.iters_host;
+    ck.R_start = run.R;
+    ck.t0 = std::chrono::steady_clock::now();
+    while (run.iters_host < run.opt.maxiters) {
+        if (!run.try_fan_group(ck) && !run.one_step(ck)) break;
+        if (ck.full(run.opt)) break;
     }
-    {
-        std::vector<StepRec> recs;
-        const size_t blocks_before = Xw->blocks.size();
-        const int lc_before = last_compression;
-        const Mat R_chunk_start = R;
-        Mat hist_V, hist_R;                       // keep_history: the chunk's V_j and R_j side by side
-        const int iters_chunk_start = iters_host;
-        // the tolerance reltol ||C|| was not known when the solve began (AdiOptions::normC_dev): wait for it on this stream and take the decisions
-        // of adi.jl:115-123 for everything recorded so far, in iteration order
-        auto apply_tolerance = [&]() {
-            if (!run.tol_event) return;
-            if (opt.normC_join) opt.normC_join();          // (`done` is recorded by then)
-            DRE_HIP(hipStreamWaitEvent(ctx->stream, run.tol_event, 0));
-            adi_decide_scan(ctx, st.p, 0, opt.normC_dev, run.reltol, -1.0);
-            run.tol_event = nullptr;
-        };
-        auto resolve_deferred = [&]() {
-            apply_tolerance();
-            if (!run.defer) return;
-            if (opt.normC_wait) opt.normC_wait();
-            adi_decide_scan(ctx, st.p, iters_host, opt.normC_dev, run.reltol, opt.abstol);
-            run.defer = false;
-        };
-        static const int chunk_timing = (env_trace("chunk") ? 1 : 0);
-        const auto ct0 = std::chrono::steady_clock::now();
-        int since_sync = 0, chunk_shifts = 0;
-        const bool single_use = opt_in.shifts.kind != ShiftSpec::CYCLIC && !opt.inner_solve && cache->enabled;
-        // Cyclic lists on the multifrontal path: the factorisations of the FIRST pass through the cycle (one workgroup per front: ~0.5 ms each at
-        // n = 5177, 1.4 ms at n = 20209, a handful of CUs busy) also run ahead on the helper streams instead of one after the other in front of
-        // their first use; from the second pass on every factor is cached and the look-ahead finds nothing to do.
-        const bool sharded_la = ctx->comm && std::max(ctx->comm->nranks, ctx->comm->emulate) > 1;
-        const bool cyc_ahead = opt_in.shifts.kind == ShiftSpec::CYCLIC && !opt.inner_solve && cache->enabled && n > ctx->dense_inv_max_n && !sharded_la;
-        const bool lookahead = single_use || cyc_ahead;
-        // the shift about to be used may have been factorised ahead on a helper stream: the main stream waits for that factorisation's event
-        auto wait_prefetched = [&](std::complex<double> mu) {
-            auto it = run.prefetch_ev.find({mu.real(), mu.imag()});
-            if (it == run.prefetch_ev.end()) return;
-            DRE_HIP(hipStreamWaitEvent(ctx->stream, it->second.ev, 0));
-            run.ev_pool.push_back(it->second.ev);
-            run.prefetch_ev.erase(it);
-        };
-        // factorise the next few shifts of the batch on the helper streams (one workgroup per front: a factorisation uses a handful of CUs
-        // for ~200 us at n = 371 — 45 % of the kernel time of a default-ADI run when it sits on the main stream)
-        auto prefetch_ahead = [&](std::complex<double> cur, bool fan_call = false) {
-            const int nh = ctx->setup_streams >= 1 ? std::max(8, ctx->setup_streams) : 0;
-            if (!lookahead || nh < 1) return;
-            auto ups = oracle->peek((size_t)2 * nh + 3);
-            // `cur` was just taken; when it opens a conjugate pair its partner is still the FIRST upcoming shift (the double step takes it later,
-            // adi.jl:190) and must not be read as the start of a new pair — that shifted every later pair by one: the partners were factorised
-            // ahead (never used, their slots never freed) and the shifts really needed were factorised inline (round 3 finding: 88 % of the
-            // complex factorisations of a default-ADI run sat on the main stream).
-            if (cur.imag() != 0.0 && !ups.empty() && ups[0] == std::conj(cur)) ups.erase(ups.begin());
-            // slots whose shift is no longer ahead (never the case when the pairs are read correctly; cheap insurance against a leak)
-            for (auto it = run.prefetch_ev.begin(); it != run.prefetch_ev.end();) {
-                bool ahead = false;
-                for (auto& u : ups) ahead = ahead || (u.real() == it->first.first && u.imag() == it->first.second);
-                if (ahead) { ++it; continue; }
-                run.ev_pool.push_back(it->second.ev);
-                it = run.prefetch_ev.erase(it);
-            }
-            int scheduled = (int)run.prefetch_ev.size();
-            static const bool trace_pf = env_trace("prefetch");
-            if (trace_pf) {
-                long &calls = ctx->trace.pf_calls, &nups = ctx->trace.pf_nups, &pend = ctx->trace.pf_pend;
-                ++calls; nups += (long)ups.size(); pend += scheduled;
-                if (calls % 500 == 0) std::fprintf(stderr, "[prefetch] %ld calls: %.2f upcoming shifts known per call, %.2f factorisations already in flight per call (depth %d)\n",
-                                                   calls, (double)nups / calls, (double)pend / calls, nh);
-            }
-            auto helpers_up = [&]() {
-                if (run.helpers_ready) return;
-                while ((int)ctx->helpers.size() < nh) {
-                    auto hc = std::make_unique<Ctx>();
-                    hc->device = ctx->device; hc->num_cus = ctx->num_cus;
-                    hc->stream = create_stream(2);
-                    hc->timer = std::make_unique<KernelTimer>();
-                    hipEvent_t ev;
-                    DRE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                    ctx->helpers.push_back(std::move(hc)); ctx->helper_ev.push_back(ev);
-                }
-                if (!ctx->helper_e0) DRE_HIP(hipEventCreateWithFlags(&ctx->helper_e0, hipEventDisableTiming));
-                DRE_HIP(hipEventRecord(ctx->helper_e0, ctx->stream));         // the operator's value arrays are ready here
-                for (int h = 0; h < nh; ++h) {
-                    Ctx* hc = ctx->helpers[(size_t)h].get();
-                    hc->pivot_static = ctx->pivot_static; hc->pivot_growth_warn = ctx->pivot_growth_warn; hc->pivot_growth_fail = ctx->pivot_growth_fail;
-                    hc->top_inverse_max_rows = ctx->top_inverse_max_rows; hc->dense_inv_max_n = ctx->dense_inv_max_n; hc->mf_subtree = ctx->mf_subtree;
-                    hc->timer->enabled = ctx->timer && ctx->timer->enabled;
-                    DRE_HIP(hipStreamWaitEvent(hc->stream, ctx->helper_e0, 0));
-                }
-                run.helpers_ready = true;
-            };
-            // Self-generated shift lists (Projection: ~13 upcoming shifts are known at every call): the factorisations that are not yet in flight
-            // go out TOGETHER, one set of level launches per kind (real / complex) on one helper stream, instead of one chain of ~15 launches
-            // per shift — the host spends ~250 us of every iteration of such a run on launch calls, and a single factorisation (~370 us at
-            // n = 1357, one workgroup per front) leaves the device as idle as sixteen of them.
-            if (single_use && !run.check_now && ctx->prefetch_batch > 0) {
-                // (refilled only when few are left in flight: the window of known shifts advances by one per iteration, so filling it at every call
-                // would again send the factorisations out one by one)
-                if (scheduled > ctx->prefetch_batch) return;
-                std::vector<std::complex<double>> tr, tc;
-                const int room = MF_ZMAX - scheduled;
-                // the shift in hand rides along when it has no factor yet (the first shift of a refilled batch: factorised inline on the main stream
-                // it was ~230 us of eight dependent launches per refill; in the batch it shares them with the next fifteen)
-                if (!fan_call) {
-                    const bool ccx = cur.imag() != 0.0;
-                    const auto cck = std::make_tuple(op.tag, cur.real(), cur.imag());
-                    const bool cknown = ccx ? cache->cplx_.count(cck) > 0 : cache->real.count(cck) > 0;
-                    if (!cknown && !run.prefetch_ev.count({cur.real(), cur.imag()})) (ccx ? tc : tr).push_back(cur);
-                }
-                for (size_t i = 0; i < ups.size() && (int)(tr.size() + tc.size()) < room; ++i) {
-                    const std::complex<double> nx = ups[i];
-                    const bool cx = nx.imag() != 0.0;
-                    const auto ck = std::make_tuple(op.tag, nx.real(), nx.imag());
-                    const bool known = cx ? cache->cplx_.count(ck) > 0 : cache->real.count(ck) > 0;
-                    if (cx) ++i;
-                    if (known || (nx == cur && !fan_call)) continue;
-                    auto& lst = cx ? tc : tr;
-                    bool dup = false;
-                    for (auto& t : lst) dup = dup || t == nx;
-                    if (!dup) lst.push_back(nx);
-                }
-                auto mark = [&](Ctx* hc, std::complex<double> nx) {
-                    hipEvent_t ev;
-                    if (!run.ev_pool.empty()) { ev = run.ev_pool.back(); run.ev_pool.pop_back(); }
-                    else DRE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                    DRE_HIP(hipEventRecord(ev, hc->stream));
-                    run.prefetch_ev[{nx.real(), nx.imag()}] = AdiRun::Prefetched{ev, 0};
-                    ++scheduled;
-                };
-                if (tr.size() >= 2) {
-                    helpers_up();
-                    Ctx* hc = ctx->helpers[run.prefetch_rr++ % (size_t)nh].get();
-                    std::vector<std::shared_ptr<FactorEntry<double>>> fes;
-                    std::vector<Factor<double>*> fp;
-                    std::vector<double> ce;
-                    for (auto& t : tr) { fes.push_back(std::make_shared<FactorEntry<double>>()); fp.push_back(&fes.back()->f); ce.push_back(t.real()); }
-                    mf_factor_batch<double>(hc, P, op.valFt.p, P.valEt.p, 1.0, ce.data(), fp.data(), (int)tr.size());
-                    for (size_t z = 0; z < tr.size(); ++z) {
-                        fes[z]->f.allow_topinv = cache->enabled;
-                        const auto key = std::make_tuple(op.tag, tr[z].real(), 0.0);
-                        cache->real[key] = fes[z]; cache->fresh.push_back(key); cache->nfactor++;
-                        mark(hc, tr[z]);
-                    }
-                }
-                if (tc.size() >= 2) {
-                    helpers_up();
-                    Ctx* hc = ctx->helpers[run.prefetch_rr++ % (size_t)nh].get();
-                    std::vector<std::shared_ptr<FactorEntry<cplx>>> fes;
-                    std::vector<Factor<cplx>*> fp;
-                    std::vector<cplx> ce;
-                    for (auto& t : tc) { fes.push_back(std::make_shared<FactorEntry<cplx>>()); fp.push_back(&fes.back()->f); ce.push_back(make_scalar<cplx>(t.real(), t.imag())); }
-                    mf_factor_batch<cplx>(hc, P, op.valFt.p, P.valEt.p, make_scalar<cplx>(1.0, 0.0), ce.data(), fp.data(), (int)tc.size());
-                    for (size_t z = 0; z < tc.size(); ++z) {
-                        const auto key = std::make_tuple(op.tag, tc[z].real(), tc[z].imag());
-                        cache->cplx_[key] = fes[z]; cache->fresh.push_back(key); cache->nfactor++;
-                        mark(hc, tc[z]);
-                    }
-                }
-            }
-            for (size_t i = 0; i < ups.size() && scheduled < nh; ++i) {
-                const std::complex<double> nx = ups[i];
-                const bool cx = nx.imag() != 0.0;
-                const auto ck = std::make_tuple(op.tag, nx.real(), nx.imag());
-                const bool known = cx ? cache->cplx_.count(ck) > 0 : cache->real.count(ck) > 0;
-                if (cx) ++i;                                   // the conjugate partner follows (adi.jl:190) and needs no factorisation of its own
-                if (known) continue;
-                // the shift the caller is about to use RIGHT NOW comes round again inside the horizon when the cycle is shorter than it: the
-                // caller factorises it inline on its own stream — handing it to a helper here would put an unfinished factor into the cache that
-                // the caller picks up without an event to wait for
-                if (nx == cur && !fan_call) continue;
-                helpers_up();
-                Ctx* hc = ctx->helpers[run.prefetch_rr++ % (size_t)nh].get();
-                hipEvent_t ev;
-                if (!run.ev_pool.empty()) { ev = run.ev_pool.back(); run.ev_pool.pop_back(); }
-                else DRE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                // (Issuing these factorisations from a host thread of their own was tried — the loop spends ~250 us of host time per iteration on
-                // launch calls: no gain, 3 230 against 3 250 it/s at n = 1357 Ros2; launches from two threads serialise inside the HIP runtime.)
-                if (cx) (void)get_factor<cplx>(hc, op, cache, cache->cplx_, nx, false, nullptr, run.check_now);
-                else {
-                    auto fnew = get_factor<double>(hc, op, cache, cache->real, nx, false, nullptr, run.check_now);
-                    // a Cyclic factor will be used in every time step: its dense top-of-tree inverse is built right behind the factorisation, on
-                    // the helper stream (mf_solve would build it inside the third solve that uses the factor, on the critical path)
-                    if (cyc_ahead) mf_prepare_topinv(hc, *op.P, fnew->f);
-                }
-                DRE_HIP(hipEventRecord(ev, hc->stream));
-                const long ticket = 0;
-                run.prefetch_ev[{nx.real(), nx.imag()}] = AdiRun::Prefetched{ev, ticket};
-                ++scheduled;
-            }
-        };
-        // Fan groups (round 4: batched, and sharded over the ranks of a communicator BY SHIFT — north_star's "independent ADI shifts farmed across
-        // the GPUs"): the g solves of a group are independent, so rank r takes the shifts at the LIST positions i = r (mod P), i.e. only ever factorises and
-        // keeps the shifts it owns (the factor farm of SURVEY 8e-4 without shipping factors), writes its W_s into slab r of the gathered panel and
-        // ONE in-place all-gather per GROUP (n g k doubles in all; round 3: one per iteration, columns sharded) completes it on every rank;
-        // mixing, norms, decisions, compression and K(t) are replicated and bit-identical on all ranks.
-        const int fan_P = ctx->comm ? std::max(1, std::max(ctx->comm->nranks, ctx->comm->emulate)) : 1;
-        const int fan_max = (opt_in.shifts.kind == ShiftSpec::CYCLIC && !opt.inner_solve && cache->enabled && n > ctx->dense_inv_max_n)
-                                ? std::min(ctx->adi_fan, FAN_GMAX) : 0;
-        while (iters_host < opt.maxiters) {
-            // ---- fan group: the next g real shifts of the cycle at once (independent solves that share every launch) -------------------------
-            if (fan_max >= 2 && !run.fan_off) {
-                // (a group may cross the chunk limit — 3, 3, 3, 3 instead of 3, 3, 3, 1 iterations per chunk of 10 — unless the caller steps
-                // with a budget, the literal mode compresses at exact intervals or the chunk length is the previous solve's iteration count)
-                const bool strict = cex || budget < (1 << 29) || run.chunk_from_hint;
-                const int room = std::min(std::min(fan_max, opt.maxiters - iters_host), strict ? chunk_limit - chunk_shifts : fan_max);
-                const int gmin = opt.keep_history ? 1 : 2;          // with a history even a single iteration takes this path (its R_j stays in the slab)
-                const auto ups = room >= gmin ? oracle->peek((size_t)room) : std::vector<std::complex<double>>();
-                int g = 0;
-                double mus[FAN_GMAX];
-                while (g < (int)ups.size() && g < room && ups[(size_t)g].imag() == 0.0) {
-                    bool dup = false;
-                    for (int i = 0; i < g; ++i) dup = dup || mus[i] == ups[(size_t)g].real();
-                    if (dup) break;
-                    mus[g] = ups[(size_t)g].real(); ++g;
-                }
-                FanCoef co;
-                while (g >= 2 && fan_coefficients(mus, g, &co) > ctx->adi_fan_max_coef) --g;
-                if (g == 1) (void)fan_coefficients(mus, 1, &co);
-                if (g < gmin) g = 0;
-                // which ranks this process plays: its own, or all of them one after the other (shard_emulate)
-                const bool emu = ctx->comm && ctx->comm->emulate > 1;
-                const int my_rank = ctx->comm ? ctx->comm->rank : 0;
-                // ownership by the shift's position in the LIST (not in the group): the same shift always meets the same rank, so a rank factorises
-                // and keeps only its share of the list (adi_begin factorises that share up front)
-                const size_t pos0 = oracle->position(), lsz = oracle->list_size();
-                auto owner = [&](int s_) { return (int)((lsz ? (pos0 + (size_t)s_) % lsz : (size_t)s_) % (size_t)fan_P); };
-                auto mine = [&](int s_) { return fan_P == 1 || emu || owner(s_) == my_rank; };
-                std::vector<std::shared_ptr<FactorEntry<double>>> fes((size_t)std::max(g, 0));
-                if (lookahead && g >= gmin) prefetch_ahead(std::complex<double>(0.0, 0.0), true);      // (first pass through the cycle: this group's and the next groups' factors; all waited for below)
-                for (int s_ = 0; s_ < g && g >= gmin; ++s_) {
-                    if (!mine(s_)) continue;
-                    if (lookahead) wait_prefetched(std::complex<double>(mus[s_], 0.0));
-                    auto fe = get_factor<double>(ctx, op, cache, cache->real, std::complex<double>(mus[s_], 0.0), true, nullptr, !lookahead || run.check_now);
-                    if (fe->dense) { g = 0; break; }              // the dense-inverse step has its own fused kernels
-                    fes[(size_t)s_] = fe;
-                }
-                if (g >= gmin) {
-                    static const bool fht = env_trace("fan");
-                    double* const ft = ctx->trace.fan_t; long& fn_ = ctx->trace.fan_n;
-                    auto fnow = []() { return std::chrono::steady_clock::now(); };
-                    auto fus = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-                    const auto f0 = fnow();
-                    const AdiState* dst = st.p;
-                    dense_norm_flush(ctx, k, Tm, tdiag, alpha_res, st.p, &npend);
-                    // group positions per rank (a group that wraps around the end of the list may give one rank more than g / P); W_s lives in slab
-                    // owner(s), in the owner's order
-                    int gp = 0;
-                    FanSlots slots; std::memset(&slots, 0, sizeof(slots));
-                    {
-                        int seen[64] = {0};
-                        for (int s_ = 0; s_ < g; ++s_) gp = std::max(gp, ++seen[owner(s_) & 63]);
-                        std::memset(seen, 0, sizeof(seen));
-                        for (int s_ = 0; s_ < g; ++s_) { const int o = owner(s_); slots.s[s_] = o * gp + seen[o & 63]++; }
-                    }
-                    Mat Wcat(ctx, n, fan_P * gp * k);
-                    bool ok = true;
-                    for (int r = 0; r < fan_P && ok; ++r) {
-                        if (!(fan_P == 1 || emu || r == my_rank)) continue;
-                        std::vector<int> pos;                          // this rank's group positions
-                        for (int s_ = 0; s_ < g; ++s_) if (owner(s_) == r) pos.push_back(s_);
-                        const int gr = (int)pos.size();
-                        if (gr == 0) continue;
-                        SmwZ sz; std::memset(&sz, 0, sizeof(sz));
-                        if (op.has_lr) {
-                            // SMW products of this rank's shifts that this solve has not formed yet: W_U = M_s^-1 Vt for all of them in one batched
-                            // solve, the capacitance matrices inverted in one launch (smw.jl:19-28); at the first group of a solve (one rank) every
-                            // other shift of the cycle whose factor exists rides along, so that a time step pays this chain once
-                            std::vector<std::pair<double, std::shared_ptr<FactorEntry<double>>>> need;
-                            for (int s_ : pos) if (!smw_cache.count({mus[s_], 0.0})) need.push_back({mus[s_], fes[(size_t)s_]});
-                            if (!need.empty() && !run.fan_smw_all && fan_P == 1) {
-                                run.fan_smw_all = true;
-                                for (auto& mv : opt.shifts.values) {
-                                    if (mv.imag() != 0.0 || (int)need.size() >= MF_ZMAX) continue;
-                                    bool dup = smw_cache.count({mv.real(), 0.0}) > 0;
-                                    for (auto& nd : need) dup = dup || nd.first == mv.real();
-                                    if (dup) continue;
-                                    auto itf = cache->real.find(std::make_tuple(op.tag, mv.real(), 0.0));
-                                    if (itf == cache->real.end() || itf->second->dense || run.prefetch_ev.count({mv.real(), 0.0})) continue;
-                                    need.push_back({mv.real(), itf->second});
-                                }
-                            }
-                            if (!need.empty()) {
-                                const int np = (int)need.size();
-                                const Factor<double>* Fp[MF_ZMAX];
-                                for (int z = 0; z < np; ++z) Fp[z] = &need[(size_t)z].second->f;
-                                Mat WUcat(ctx, n, np * m);
-                                ok = mf_solve_batch(ctx, P, Fp, np, op.Vt.p, op.Vt.ld, m, WUcat.p, WUcat.ld, m, dst);
-                                if (!ok) break;
-                                Mat smu(ctx, m, np * m);
-                                gemm(ctx, true, false, 1.0, op.U, WUcat, 0.0, smu, dst, "smw_small");
-                                SinvZ iz; std::memset(&iz, 0, sizeof(iz));
-                                for (int z = 0; z < np; ++z) {
-                                    SmwCacheEntry en;
-                                    en.keep = WUcat.buf; en.WU = WUcat.p + (size_t)z * m * WUcat.ld; en.ldwu = WUcat.ld;
-                                    en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(double));
-                                    iz.out[z] = (double*)en.sinv->p;
-                                    smw_cache.emplace(std::make_pair(need[(size_t)z].first, 0.0), en);
-                                    used_real.push_back(need[(size_t)z].second);
-                                }
-                                hipLaunchKernelGGL(k_sinv_z, dim3(np), dim3(64), 0, ctx->stream, m, (const double*)smu.p, smu.ld, op.alpha, iz, dst, serr);
-                            }
-                            for (int z = 0; z < gr; ++z) {
-                                const auto& en = smw_cache.find({mus[pos[(size_t)z]], 0.0})->second;
-                                sz.WU[z] = (const double*)en.WU; sz.ldwu[z] = en.ldwu; sz.Sinv[z] = (const double*)en.sinv->p;
-                            }
-                        }
-                        const Factor<double>* Fs[MF_ZMAX];
-                        for (int z = 0; z < gr; ++z) Fs[z] = &fes[(size_t)pos[(size_t)z]]->f;
-                        Mat Wr = Wcat.colsview(r * gp * k, gr * k);          // slab r: its solves side by side
-                        const auto f1 = fnow();
-                        ok = mf_solve_batch(ctx, P, Fs, gr, R.p, R.ld, k, Wr.p, Wr.ld, k, dst);
-                        if (fht) { ft[0] += fus(f0, f1); ft[1] += fus(f1, fnow()); }
-                        if (!ok) break;
-                        for (int s_ : pos) used_real.push_back(fes[(size_t)s_]);
-                        if (op.has_lr) {
-                            // W_s <- W_s - W_U,s (S_s^-1 (U' W_s))  for the rank's solves: one product U' [W_s ...], one apply launch (in place)
-                            Mat sm(ctx, m, gr * k);
-                            gemm(ctx, true, false, 1.0, op.U, Wr, 0.0, sm, dst, "smw_small");
-                            TimedScope ts(ctx, "smw_apply", 8.0 * n * gr * (2.0 * k + m), 2.0 * n * gr * (double)k * m, gr);
-                            hipLaunchKernelGGL(k_smw_apply_z, dim3(ceil_div(n, 256), ceil_div(k, SMW_CB), gr), dim3(256), 0, ctx->stream, n, m, k, Wr.p, Wr.ld, sz,
-                                               (const double*)sm.p, sm.ld, dst);
-                        }
-                    }
-                    // (nothing was enqueued where the batched form does not apply — the same decision on every rank: it depends on the pencil and
-                    // the context's options only — and this solve goes on one iteration at a time)
-                    if (!ok) {
-                        // (with real ranks the decision must not differ between them — it can only where a rank's own factors needed static pivots:
-                        // fail loudly instead of leaving the other ranks inside a collective)
-                        if (fan_P > 1 && !emu) throw Error(ERR_INTERNAL, "sharded fan group: the batched solves do not apply to this rank's factors (static pivots); "
-                                                                         "run with adi_fan = 0 for this pencil");
-                        run.fan_off = true; continue;
-                    }
-                    if (fan_P > 1 && !emu) {
-                        TimedScope ts(ctx, "comm_allgather_w", 8.0 * n * (double)fan_P * gp * k, 0.0);
-                        comm_allgather_inplace(ctx, *ctx->comm, Wcat.p, (size_t)n * gp * k);
-                    }
-                    const auto f2 = fnow();
-                    // V_j = sum_s c_js W_s,  R_j = R_0 - sum_s d_js E' W_s  for the g iterations: one pass over E' and the panels
-                    Mat Vcat, Rcat;
-                    if (opt.keep_history) {
-                        // every iteration of the chunk side by side (the Rosenbrock-1 driver reads E'V_j = (R_{j-1} - R_j) / (2 mu_j) off these slabs)
-                        const int cap = chunk_limit + FAN_GMAX;
-                        if (hist_V.empty()) { hist_V = Mat(ctx, n, cap * k); hist_R = Mat(ctx, n, cap * k); }
-                        if (chunk_shifts + g <= cap) { Vcat = hist_V.colsview(chunk_shifts * k, g * k); Rcat = hist_R.colsview(chunk_shifts * k, g * k); }
-                        else run.hist_ok = false;
-                    }
-                    if (Vcat.p == nullptr) { Vcat = Mat(ctx, n, g * k); Rcat = Mat(ctx, n, g * k); }
-                    fan_spmm_mix(ctx, P, Wcat, R, Vcat, Rcat, g, k, co, slots, dst);
-                    const auto f3 = fnow();
-                    for (int j = 0; j < g; ++j) {
-                        const std::complex<double> muj = oracle->take(&res.warnings);
-                        all_shifts.push_back(muj);
-                        Mat Vj = Vcat.colsview(j * k, k), Rj = Rcat.colsview(j * k, k);
-                        Xw->blocks.push_back({Vj, Tm, -2.0 * muj.real() * alpha_res, tdiag});
-                        iters_host += 1; last_compression += 1;
-                        oracle->update(Rj, {Vj});
-                        recs.push_back({iters_host, Xw->blocks.size(), 1, Rj});
-                        ++since_sync; ++chunk_shifts;
-                    }
-                    const auto f4 = fnow();
-                    apply_tolerance();
-                    residual_norm_group_diag(ctx, Rcat, g, k, Tm, tdiag, alpha_res, st.p, iters_host - g);
-                    R = Rcat.colsview((g - 1) * k, k);
-                    if (fht) {
-                        const auto f5 = fnow();
-                        ft[2] += fus(f2, f3); ft[3] += fus(f3, f4); ft[4] += fus(f4, f5); ft[5] += fus(f0, f5);
-                        if (++fn_ % 128 == 0) std::fprintf(stderr, "[fan host, us per group] before the solves %.1f | batched solves %.1f | mix %.1f | bookkeeping %.1f | norms %.1f | total %.1f\n",
-                                                           ft[0] / fn_, ft[1] / fn_, ft[2] / fn_, ft[3] / fn_, ft[4] / fn_, ft[5] / fn_);
-                    }
-                    if (opt.compression && chunk_shifts >= chunk_limit) break;
-                    if (!opt.compression && since_sync >= std::min(10, chunk_limit)) break;
-                    continue;
-                }
-            }
-            apply_tolerance();
-            if (run.defer) {
-                // an iteration outside the fan path while the tolerance is still on its way: close the chunk first (its end resolves the tolerance)
-                if (!recs.empty()) break;
-                resolve_deferred();
-            }
-            run.hist_ok = false;                  // (its residual factor is updated in place: no history of this solve)
-            std::complex<double> mu;
-            { RoctxRange rr("shifts"); mu = oracle->take(&res.warnings); }        // adi.jl:101
-            // (a refill that found the solve converged: the rest of the chunk would be early-exit launches with a synchronisation per refill)
-            if (oracle->stopped() && !recs.empty()) break;
-            all_shifts.push_back(mu);
-            const bool is_real = (mu.imag() == 0.0);
-            RoctxRange roctx_solve(is_real ? "solve (real)" : "solve (complex)");        // adi.jl:157,196 (the range covers the whole step)
-            const AdiState* dst = st.p;
-            if (lookahead) { wait_prefetched(mu); prefetch_ahead(mu); wait_prefetched(mu); }        // (the batch may carry the shift in hand: its event is waited for behind it)
-            Mat V1, V2;
-            bool norm_done = false, rode = false;
-            if (is_real) {
-                // dense inverses pay off only for shift lists that persist across Lyapunov solves (user-given Cyclic values)
-                const bool user_inner = opt.inner_solve != nullptr;
-                std::shared_ptr<FactorEntry<double>> fe;
-                if (!user_inner) {
-                    if (single_use && trace_prefetch) {
-                        long &hit = ctx->trace.rl_hit, &miss = ctx->trace.rl_miss;
-                        (cache->real.count(std::make_tuple(op.tag, mu.real(), 0.0)) ? hit : miss)++;
-                        if ((hit + miss) % 500 == 0) std::fprintf(stderr, "[prefetch] real shifts: %ld found ready, %ld factorised inline\n", hit, miss);
-                    }
-                    fe = get_factor<double>(ctx, op, cache, cache->real, mu, opt_in.shifts.kind == ShiftSpec::CYCLIC, nullptr, !lookahead || run.check_now);
-                    used_real.push_back(fe);
-                }
-                auto key = std::make_pair(mu.real(), 0.0);
-                auto sc = smw_cache.find(key);
-                const bool have = op.has_lr && sc != smw_cache.end();
-                const int ncols = k + ((op.has_lr && !have) ? m : 0);
-                if (fe && fe->dense) {
-                    // dense-inverse step: one stacked GEMM + one fused apply (V and the residual recurrence)
-                    const int mm = op.has_lr ? m : 0;
-                    if (fe->stack.empty() || fe->stack_U != (const void*)op.U.p || fe->stack_m != mm) {
-                        Mat stk(ctx, 2 * n + mm, n);
-                        { Mat top = stk.view(0, 0, n, n); copy_mat(ctx, fe->dinv, top); }
-                        { Mat mid = stk.view(n, 0, n, n); spmm(ctx, P, P.valEt.p, fe->dinv, mid, 1.0, 0.0, nullptr); }
-                        if (mm) { Mat bot = stk.view(2 * n, 0, mm, n); gemm(ctx, true, false, 1.0, op.U, fe->dinv, 0.0, bot, nullptr, "gemm_dinv"); }
-                        fe->stack = stk; fe->stack_U = (const void*)op.U.p; fe->stack_m = mm;
-                    }
-                    const int lds_ = 2 * n + mm;
-                    V1 = Mat(ctx, n, k);
-                    if (op.has_lr && !have) {
-                        Mat WK(ctx, lds_, m);
-                        gemm(ctx, false, false, 1.0, fe->stack, op.Vt, 0.0, WK, dst, "gemm_dinv");
-                        SmwCacheEntry en;
-                        Mat WKS(ctx, 2 * n, m);
-                        en.keep = WKS.buf; en.WU = WKS.p; en.ldwu = WKS.ld;
-                        en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(double));
-                        hipLaunchKernelGGL((k_sinv<double>), dim3(1), dim3(64), 0, ctx->stream, m, WK.p + 2 * (size_t)n, WK.ld, op.alpha, (double*)en.sinv->p, dst, serr);
-                        hipLaunchKernelGGL(k_fold_sinv, dim3(ceil_div(2 * n * m, 256)), dim3(256), 0, ctx->stream, 2 * n, m, WK.p, WK.ld,
-                                           (const double*)en.sinv->p, WKS.p, WKS.ld, dst);
-                        sc = smw_cache.emplace(key, en).first;
-                    }
-                    if (k <= 96) {
-                        // split-K slabs of the stacked GEMM are consumed directly by the fused step kernel
-                        int zs = 1;
-                        BufP wpart = gemm_partials(ctx, false, false, lds_, k, n, fe->stack.p, fe->stack.ld, R.p, R.ld, &zs, dst, "gemm_dinv");
-                        dense_adi_step(ctx, n, mm, k, zs, (const double*)wpart->p, op.has_lr ? (const double*)sc->second.WU : nullptr,
-                                       op.has_lr ? sc->second.ldwu : 0, V1, R, 2.0 * mu.real(), Tm, tdiag, alpha_res, st.p, iters_host + 1,
-                                       &npend);
-                        norm_done = true; rode = true;
-                    } else {
-                        Mat Wst(ctx, lds_, k);
-                        gemm(ctx, false, false, 1.0, fe->stack, R, 0.0, Wst, dst, "gemm_dinv");
-                        TimedScope ts(ctx, "dense_apply", 8.0 * n * (4.0 * k + 2.0 * m), 4.0 * n * k * m);
-                        if (op.has_lr)
-                            hipLaunchKernelGGL((k_dense_apply<true>), dim3(ceil_div(n, 64), ceil_div(k, 4)), dim3(256), 0, ctx->stream,
-                                               n, m, k, Wst.p, Wst.ld, (const double*)sc->second.WU, sc->second.ldwu,
-                                               V1.p, V1.ld, R.p, R.ld, 2.0 * mu.real(), dst);
-                        else
-                            hipLaunchKernelGGL((k_dense_apply<false>), dim3(ceil_div(n, 64), ceil_div(k, 4)), dim3(256), 0, ctx->stream,
-                                               n, 0, k, Wst.p, Wst.ld, (const double*)nullptr, 0,
-                                               V1.p, V1.ld, R.p, R.ld, 2.0 * mu.real(), dst);
-                    }
-                } else if (!user_inner && ctx->comm && std::max(ctx->comm->nranks, ctx->comm->emulate) > 1 && k >= ctx->shard_min_cols) {
-                    // ---- column-sharded step: V = (F' + mu E')^-1 R acts column by column (adi.jl:158-159), so rank g
-                    // solves its 16-column tiles of R only (multifrontal sweeps + SMW, both column local), writes them into its block of the
-                    // gathered panel and ONE in-place all-gather (RCCL, on this stream) completes V on every rank.  The m columns M^-1 Vt of
-                    // the SMW correction are computed by every rank that owns columns (replicated: m = 7 against k/P).
-                    Comm& cm = *ctx->comm;
-                    const int Pn = std::max(cm.nranks, cm.emulate);
-                    const ColBlocks cb(k, Pn);
-                    Mat Vg(ctx, n, cb.padded());
-                    auto local = [&](int g) {
-                        const int c0 = cb.c0(g), kc = cb.c1(g) - c0;
-                        if (kc <= 0) return;
-                        auto scl = smw_cache.find(key);
-                        const bool havel = op.has_lr && scl != smw_cache.end();
-                        const int extra = (op.has_lr && !havel) ? m : 0;
-                        Mat Vloc = Vg.colsview(c0, kc);
-                        if (!op.has_lr) {
-                            mf_solve_from(ctx, P, fe->f, R.p + (size_t)c0 * R.ld, R.ld, kc, Vloc.p, Vloc.ld, kc, dst);
-                            return;
-                        }
-                        Mat W(ctx, n, kc + extra);
-                        if (extra) { Mat d = W.colsview(kc, m); copy_mat(ctx, op.Vt, d, 1.0, dst); }
-                        mf_solve_from(ctx, P, fe->f, R.p + (size_t)c0 * R.ld, R.ld, kc, W.p, W.ld, kc + extra, dst);
-                        Mat small(ctx, m, kc + extra);
-                        gemm(ctx, true, false, 1.0, op.U, W, 0.0, small, dst, "smw_small");
-                        if (!havel) {
-                            SmwCacheEntry en;
-                            en.keep = W.buf; en.WU = W.p + (size_t)kc * W.ld; en.ldwu = W.ld;
-                            en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(double));
-                            hipLaunchKernelGGL((k_sinv<double>), dim3(1), dim3(64), 0, ctx->stream, m, small.p + (size_t)kc * small.ld, small.ld, op.alpha, (double*)en.sinv->p, dst, serr);
-                            scl = smw_cache.emplace(key, en).first;
-                        }
-                        TimedScope ts(ctx, "smw_apply", 8.0 * n * (2.0 * kc + m), 2.0 * n * kc * m);
-                        hipLaunchKernelGGL((k_smw_apply<double, true>), dim3(ceil_div(n, 256), ceil_div(kc, SMW_CB)), dim3(256), 0, ctx->stream,
-                                           n, m, kc, W.p, W.ld, (const double*)scl->second.WU, scl->second.ldwu, (const double*)scl->second.sinv->p,
-                                           small.p, small.ld, Vloc.p, Vloc.ld, (double*)nullptr, 0, 0.0, dst);
-                    };
-                    if (cm.emulate > 1) { for (int g = 0; g < Pn; ++g) local(g); }
-                    else {
-                        local(cm.rank);
-                        TimedScope ts(ctx, "comm_allgather_v", 8.0 * n * (double)cb.padded(), 0.0);
-                        comm_allgather_inplace(ctx, cm, Vg.p, (size_t)n * cb.width());
-                    }
-                    V1 = Vg.colsview(0, k);
-                    spmm(ctx, P, P.valEt.p, V1, R, -2.0 * mu.real(), 1.0, dst);          // R <- R - 2 mu E' V   (adi.jl:171), replicated
-                } else {
-                    Mat W(ctx, n, ncols);
-                    if (user_inner) { Mat d = W.colsview(0, k); copy_mat(ctx, R, d, 1.0, dst); }
-                    if (op.has_lr && !have) { Mat d = W.colsview(k, m); copy_mat(ctx, op.Vt, d, 1.0, dst); }
-                    if (user_inner) user_block_solve(ctx, op, opt, mu, W, nullptr);
-                    else mf_solve_from(ctx, P, fe->f, R.p, R.ld, k, W.p, W.ld, ncols, dst);     // the residual block is read where it is
-                    if (op.has_lr) {
-                        V1 = Mat(ctx, n, k);
-                        // small = U' W: a skinny split-K MFMA GEMM (the one-workgroup-per-column kernel is latency bound at large n).  (Letting the
-                        // SMW kernels sum the slabs themselves saves the reduction launch and is neutral at n = 5177, but every one of the 1264
-                        // workgroups of the apply kernel then sums its 56 entries over 80 slabs at n = 20209: 59 us against 20 + 10 — reverted.)
-                        Mat small(ctx, m, ncols);
-                        gemm(ctx, true, false, 1.0, op.U, W, 0.0, small, dst, "smw_small");
-                        if (!have) {
-                            SmwCacheEntry en;
-                            en.keep = W.buf; en.WU = W.p + (size_t)k * W.ld; en.ldwu = W.ld;
-                            en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(double));
-                            hipLaunchKernelGGL((k_sinv<double>), dim3(1), dim3(64), 0, ctx->stream, m, small.p + (size_t)k * small.ld, small.ld, op.alpha, (double*)en.sinv->p, dst, serr);
-                            sc = smw_cache.emplace(key, en).first;
-                        }
-                        TimedScope ts(ctx, "smw_apply", 8.0 * n * (2.0 * k + m), 2.0 * n * k * m);
-                        hipLaunchKernelGGL((k_smw_apply<double, true>), dim3(ceil_div(n, 256), ceil_div(k, SMW_CB)), dim3(256), 0, ctx->stream,
-                                           n, m, k, W.p, W.ld, (const double*)sc->second.WU, sc->second.ldwu, (const double*)sc->second.sinv->p,
-                                           small.p, small.ld, V1.p, V1.ld, (double*)nullptr, 0, 0.0, dst);
-                    } else {
-                        V1 = W;
-                    }
-                    // R <- R - 2 mu E' V   (adi.jl:171)
-                    spmm(ctx, P, P.valEt.p, V1, R, -2.0 * mu.real(), 1.0, dst);
-                }
-                Xw->blocks.push_back({V1, Tm, -2.0 * mu.real() * alpha_res, tdiag});
-                iters_host += 1; last_compression += 1;
-                oracle->update(R, {V1});
-            } else {
-                std::complex<double> mu2 = oracle->take(&res.warnings);
-                all_shifts.push_back(mu2);
-                DRE_REQUIRE(std::abs(mu2 - std::conj(mu)) <= 1e-8 * std::abs(mu), "complex shifts must come in conjugate pairs (adi.jl:190)");
-                V1 = Mat(ctx, n, k);
-                V2 = Mat(ctx, n, k);
-                const bool user_inner = opt.inner_solve != nullptr;
-                std::shared_ptr<FactorEntry<cplx>> fe;
-                if (!user_inner) {
-                    if (single_use && trace_prefetch) {
-                        long &hit = ctx->trace.cx_hit, &miss = ctx->trace.cx_miss;
-                        (cache->cplx_.count(std::make_tuple(op.tag, mu.real(), mu.imag())) ? hit : miss)++;
-                        if ((hit + miss) % 500 == 0) std::fprintf(stderr, "[prefetch] complex pairs: %ld found ready, %ld factorised inline\n", hit, miss);
-                    }
-                    fe = get_factor<cplx>(ctx, op, cache, cache->cplx_, mu, true, nullptr, !lookahead || run.check_now);
-                    used_cplx.push_back(fe);
-                }
-                auto key = std::make_pair(mu.real(), mu.imag());
-                auto sc = smw_cache.find(key);
-                const bool have = op.has_lr && sc != smw_cache.end();
-                const int ncols = k + ((op.has_lr && !have) ? m : 0);
-                auto Wb = std::make_shared<Buf>(ctx, (size_t)n * ncols * sizeof(cplx));
-                cplx* W = (cplx*)Wb->p;
-                {
-                    size_t tot = (size_t)n * k;
-                    hipLaunchKernelGGL(k_real_to_cplx, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, n, k, R.p, R.ld, W, n, dst);
-                    if (op.has_lr && !have) {
-                        tot = (size_t)n * m;
-                        hipLaunchKernelGGL(k_real_to_cplx, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, n, m, op.Vt.p, op.Vt.ld, W + (size_t)k * n, n, dst);
-                    }
-                }
-                if (user_inner) {
-                    // the real right-hand side [R, Vt] goes to the user's solver; the complex solution comes back interleaved
-                    Mat Wr(ctx, n, ncols);
-                    { Mat d = Wr.colsview(0, k); copy_mat(ctx, R, d, 1.0, dst); }
-                    if (op.has_lr && !have) { Mat d = Wr.colsview(k, m); copy_mat(ctx, op.Vt, d, 1.0, dst); }
-                    user_block_solve(ctx, op, opt, mu, Wr, W);
-                } else mf_solve<cplx>(ctx, P, fe->f, W, n, ncols, dst);
-                const double delta = mu.real() / mu.imag();
-                if (op.has_lr) {
-                    auto sb = std::make_shared<Buf>(ctx, (size_t)m * ncols * sizeof(cplx));
-                    cplx* small = (cplx*)sb->p;
-                    hipLaunchKernelGGL((k_smw_small<cplx>), dim3(ncols), dim3(256), 0, ctx->stream, n, m, op.U.p, op.U.ld, W, n, small, m, dst);
-                    if (!have) {
-                        SmwCacheEntry en;
-                        en.keep = Wb; en.WU = W + (size_t)k * n; en.ldwu = n;
-                        en.sinv = std::make_shared<Buf>(ctx, (size_t)m * m * sizeof(cplx));
-                        hipLaunchKernelGGL((k_sinv<cplx>), dim3(1), dim3(64), 0, ctx->stream, m, small + (size_t)k * m, m, op.alpha, (cplx*)en.sinv->p, dst, serr);
-                        sc = smw_cache.emplace(key, en).first;
-                    }
-                    hipLaunchKernelGGL((k_smw_apply<cplx, true>), dim3(ceil_div(n, 256), ceil_div(k, SMW_CB)), dim3(256), 0, ctx->stream,
-                                       n, m, k, W, n, (const cplx*)sc->second.WU, sc->second.ldwu, (const cplx*)sc->second.sinv->p,
-                                       small, m, V1.p, V1.ld, V2.p, V2.ld, delta, dst);
-                } else {
-                    hipLaunchKernelGGL((k_smw_apply<cplx, false>), dim3(ceil_div(n, 256), ceil_div(k, SMW_CB)), dim3(256), 0, ctx->stream,
-                                       n, 0, k, W, n, (const cplx*)nullptr, 0, (const cplx*)nullptr, (const cplx*)nullptr, 0,
-                                       V1.p, V1.ld, V2.p, V2.ld, delta, dst);
-                }
-                zero_increment_guard(ctx, V1, V2, st.p, 2);       // adi.jl:200-204
-                // R <- R - 2 sqrt2 Re(mu) E' V1   (adi.jl:217)
-                spmm(ctx, P, P.valEt.p, V1, R, -2.0 * 1.4142135623730951 * mu.real(), 1.0, dst);
-                Xw->blocks.push_back({V1, Tm, -2.0 * mu.real() * alpha_res, tdiag});
-                Xw->blocks.push_back({V2, Tm, -2.0 * mu.real() * alpha_res, tdiag});
-                iters_host += 2; last_compression += 2;
-                oracle->update(R, {V1, V2});
-            }
-            // residual norm through the Gram matrix, convergence decision on the device
-            if (!rode) dense_norm_flush(ctx, k, Tm, tdiag, alpha_res, st.p, &npend);     // a step of another kind: norms stay in order
-            if (!norm_done) residual_norm_step(ctx, R, Tm, tdiag, alpha_res, st.p, iters_host);
-            recs.push_back({iters_host, Xw->blocks.size(), is_real ? 1 : 2, R});
-            ++since_sync; chunk_shifts += is_real ? 1 : 2;
-            if (opt.compression && chunk_shifts >= chunk_limit) break;
-            if (!opt.compression && since_sync >= std::min(10, chunk_limit)) break;
-        }
-        // synchronise once per chunk and find out how far the device really got
-        dense_norm_flush(ctx, k, Tm, tdiag, alpha_res, st.p, &npend);
-        const bool was_deferred = run.defer;
-        resolve_deferred();
-        AdiState h;
-        const auto ct1 = std::chrono::steady_clock::now();
-        ctx_fetch(ctx, st.p, sizeof(AdiState), &h);
-        if (was_deferred || run.abstol_pending) {
-            run.abstol = h.abstol; res.abstol = h.abstol; res.initial_norm = h.norms[0];
-            if (!res.norms.empty()) res.norms[0] = h.norms[0];
-            run.abstol_pending = false;
-        }
-        if (chunk_timing) {
-            double &enq = ctx->trace.ch_enq, &wait = ctx->trace.ch_wait; long &nch = ctx->trace.ch_n, &nit_ = ctx->trace.ch_it;
-            const auto ct2 = std::chrono::steady_clock::now();
-            enq += std::chrono::duration<double, std::micro>(ct1 - ct0).count(); wait += std::chrono::duration<double, std::micro>(ct2 - ct1).count();
-            nit_ += (long)recs.size();
-            if (++nch % 64 == 0) std::fprintf(stderr, "[chunk timing] %ld chunks, %ld iterations: host enqueue %.1f us / iteration, wait at the synchronisation %.1f us / iteration\n",
-                                              nch, nit_, enq / nit_, wait / nit_);
-        }
-        size_t nblocks = blocks_before;
-        int lc = lc_before;
-        R = R_chunk_start;
-        for (auto& r : recs) {
-            if (r.iters_after <= h.iters) {
-                nblocks = r.nblocks; lc += r.nshifts;
-                R = r.Rafter;                                  // (fan groups leave every residual in a buffer of its own)
-                res.norms.push_back(h.norms[r.iters_after & 511]);
-                res.norm_iters.push_back(r.iters_after);
-            }
-        }
-        Xw->blocks.resize(nblocks);
-        check_used();
-        last_compression = lc;
-        res.iters = h.iters;
-        res.res_norm = h.res_norm;
-        if (opt.keep_history && run.hist_ok) {
-            const int acc = std::max(0, std::min(h.iters, iters_host) - iters_chunk_start);        // accepted iterations of this chunk
-            if (acc > 0 && !hist_V.empty()) {
-                AdiHistChunk hc;
-                hc.R0 = R_chunk_start; hc.Rs = hist_R.colsview(0, acc * k); hc.Vs = hist_V.colsview(0, acc * k);
-                for (int j = 0; j < acc; ++j) hc.mu.push_back(all_shifts[(size_t)iters_chunk_start + j].real());
-                res.hist.push_back(std::move(hc));
-            } else if (acc > 0) run.hist_ok = false;
-        }
-        if (h.smw_singular) throw Error(ERR_SINGULAR, "SMW: capacitance matrix is singular");
-        if (h.collapsed == 2) res.warnings |= 2;          // DRE_WARN_ZERO_INCREMENT: the iteration collapsed (adi.jl:134-137)
-        if (h.done || recs.empty()) finished = true;
-        if (opt.compression && last_compression >= opt.compression_interval && (!finished || cex)) {
-            // Small n: the compression works on the n x n matrix L D L' whatever the number of columns, and the increments
-            // never depend on X, so the intermediate compressions of adi.jl:72-76 are deferred to the final one
-            // (adi.jl:78-80) as long as the uncompressed factor stays small.
-            // The same holds for the direct form up to compress_direct_max_n (one GEMM over all columns) and for the factor form
-            // (panel steps ~ rank, GEMM traffic ~ columns: one late compression costs the GEMMs of two early ones and half the
-            // panels) while the factor still fits the factor-form limit c + 64 <= n after the next chunk.
-            const long rk = Xw->rank(), next = (long)std::max(opt.compression_interval * 2, run.chunk_limit + FAN_GMAX) * k;
-            const bool free_form = opt.given_residual && opt.keep_history && !opt.final_compress && ctx->recurrence_wide != 0 && run.hist_ok;
-            const bool defer = free_form || (!cex && (n <= 512 ? rk <= 16L * n
-                                       : ((n <= ctx->compress_direct_max_n && rk <= 16L * n) ||
-                                          (n >= ctx->compress_factor_min_n && rk + next + 64 <= n))));
-            if (!defer) {
-                ldlt_compress(ctx, *Xw, ctf, cex);
-                last_compression = 0;
-                run.hist_ok = false;              // (the increments are no longer the V_j)
-            }
-        }
-        if (resid && !resid->blocks.empty()) resid->blocks[0].L = R;      // (the factor may have moved to a fan group's buffer)
-    }
+    run.close_chunk(ck);
+    run.maybe_compress();
+    if (run.resid && !run.resid->blocks.empty()) run.resid->blocks[0].L = run.R;      // (the factor may have moved to a fan group's buffer)
 }
 
 AdiResult adi_finish(AdiRun& run) {
@@ -2017,14 +2085,11 @@ AdiResult adi_finish(AdiRun& run) {
     auto& Xw = run.Xw;
     int& last_compression = run.last_compression;
     auto& all_shifts = run.all_shifts;
-    // look-ahead factorisations the solve did not get to use stay in a persistent cache (Cyclic lists): whatever runs on the main stream from
-    // here on — the next Lyapunov solve finds them "known" — is ordered behind them
-    for (auto& kv : run.prefetch_ev) (void)hipStreamWaitEvent(ctx->stream, kv.second.ev, 0);
+    run.pf.wait_all();
     res.hist_ok = opt.keep_history && run.hist_ok; res.Tm = run.Tm; res.alpha_res = run.alpha_res; res.tdiag = run.tdiag;
     if (run.finalized || run.res.rhs_cols == 0 || (run.iters_host == 0 && run.res.converged)) { run.finalized = true; return res; }
     run.finalized = true;
-    auto check_used = [&]() { run.check_used(); };
-    check_used();
+    run.check_used();
     if (opt_in.shifts.kind != ShiftSpec::CYCLIC) {
         // self-generated shifts (Projection, per-solve Heuristic) never come back: their factors must not outlive the solve,
         // or device memory grows with the total number of ADI iterations of a time loop

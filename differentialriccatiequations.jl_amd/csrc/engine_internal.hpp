@@ -1,6 +1,7 @@
 // Declarations shared by the three translation units of the low-rank engine (not part of the interface in engine.hpp):
 //   ldlt.hip    LDL' objects, compress!, norms, the Lyapunov / Riccati residuals        (src/LDLt.jl, src/lyapunov/residual.jl)
-//   engine.hip  Sherman-Morrison-Woodbury pieces, shift strategies, factor cache, the ADI (src/lyapunov/adi.jl, src/shifts/*.jl, src/blocklinear/*.jl)
+//   engine.hip  Sherman-Morrison-Woodbury pieces, shift strategies, factor cache, the ADI (src/lyapunov/adi.jl, src/shifts/*.jl, src/blocklinear/*.jl);
+//               the ADI's host decisions (fan groups, shift lists, chunk ledger) are in adi_plan.hpp, free of HIP
 //   gdre.hip    Rosenbrock drivers: residual-recurrence loop, gdre_solve (dense-X step: dense_x.hip, adi_cycle.hip)   (src/riccati/lowrank_ros1.jl, lowrank_ros2.jl)
 #pragma once
 #include "engine.hpp"
@@ -40,7 +41,8 @@ template <typename T>
 std::shared_ptr<FactorEntry<T>> get_factor(Ctx* ctx, const GaleOperator& op, FactorCache* cache,
                                            std::map<std::tuple<uint64_t, double, double>, std::shared_ptr<FactorEntry<T>>>& store,
                                            std::complex<double> mu, bool want_dense = true, DeferredDense* defer = nullptr, bool check_now = true);
-Ctx* helper_ctx(Ctx* ctx, int h);
+void helpers_grow(Ctx* ctx, int nh);               // at least nh helper contexts (own stream, pool and event each)
+Ctx* helper_ctx(Ctx* ctx, int h);                  // helper context h, with the timer switch and the swizzles of its parent
 hipEvent_t aux_event(Ctx* ctx, int i);
 
 }  // namespace dre

@@ -1,6 +1,7 @@
 // Sparse side of the engine: the pencil (E', A' on one union pattern in nested-dissection order),
 // CSR SpMM, and the multifrontal LU of the shifted operator with multi-RHS solves.
 #pragma once
+#include "adi_plan.hpp"
 #include "common.hpp"
 #include "dense.hpp"
 #include "symbolic.hpp"
@@ -152,10 +153,7 @@ void mf_prepare_topinv(Ctx* ctx, const Pencil& P, const Factor<double>& F);
 void mf_solve_from(Ctx* ctx, const Pencil& P, const Factor<double>& F, const double* Win, int ldwin, int nin, double* W, int ldw, int nrhs,
                    const AdiState* st = nullptr);
 
-// partial-fraction coefficients of a fan group (engine.hip, fan_coefficients) and the fused  E' W + mixing  pass over the g solves
-#define FAN_GMAX 10
-struct FanCoef { double c[FAN_GMAX][FAN_GMAX], d[FAN_GMAX][FAN_GMAX]; };
-struct FanSlots { int s[FAN_GMAX]; };       // solve s lives in columns s[s] k .. of the panel (shift-sharded groups: slab of the owning rank)
+// the fused  E' W + mixing  pass over the g solves of a fan group (partial-fraction coefficients and panel slots: adi_plan.hpp)
 void fan_spmm_mix(Ctx* ctx, const Pencil& P, const Mat& W, const Mat& R0, Mat& V, Mat& Rc, int g, int k, const FanCoef& co, const FanSlots& sl,
                   const AdiState* st = nullptr);
 // g solves with different factors of the same pencil in shared launches: W_z = F_z^-1 [Win(:, 0:nin) | W_z(:, nin:nrhs)], W_z = columns
