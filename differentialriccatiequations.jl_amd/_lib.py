@@ -211,6 +211,11 @@ PROTOTYPES = {
     "dre_balance_lr": (C.c_int, [_vp] * 9 + [C.c_int, C.c_double] + [_pvp] * 6 + [_pi64, _pd]),
     "dre_dense_gare_solve_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _pvp, _pvp, _pi64, _pd]),
     "dre_lqg_balance": (C.c_int, [_vp] * 7 + [C.c_int, C.c_double] + [_pvp] * 9 + [_pi64, _pd]),
+    "dre_dense_stein_solve": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, _pvp, _pi64, _pd]),
+    "dre_dense_stein_residual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _pvp, _pd, _pd]),
+    "dre_dense_dare_solve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd]),
+    "dre_dense_dare_solve_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _pvp, _pvp, _pi64, _pd]),
+    "dre_dense_dare_residual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pvp, _pd, _pd]),
     "dre_sign_free": (C.c_int, [_vp, _vp]),
     "dre_host_svd_left": (C.c_int, [C.c_int, C.c_int, _pd, _pd, _pd]),
     "dre_dense_invert_batched": (C.c_int, [_vp, C.c_int, _pvp, _pi32, _pd, _pi32]),

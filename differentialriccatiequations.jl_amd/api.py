@@ -3046,6 +3046,223 @@ def gare_residual_dense(prob: GAREProblem, X, ctx=None):
     return dev.DenseMatrix(ctx, rp).numpy()
 
 
+# ------------------------------------------------------------------------------------------------
+# Discrete time: the generalized Stein equation and the DARE by doubling          (csrc/dense_doubling.hip)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class GDALEProblem:
+    """AᵀXA − EᵀXE = −C (the generalized Stein equation, the discrete-time twin of GALEProblem); C an ndarray or an LDLᵀ object, as
+    solve_gale_dense accepts it."""
+    E: Any
+    A: Any
+    C: Any
+
+
+@dataclass
+class GDAREProblem:
+    """Q + AᵀX(I + GX)⁻¹A − EᵀXE = 0, written out AᵀXA − EᵀXE − AᵀXB(R + BᵀXB)⁻¹BᵀXA + Q = 0, with G = lowrank(B, R⁻¹) and Q = lowrank(Cᵀ, S):
+    the fields and the (β, B, Rinv) / (γ, Ct, S) conventions of GAREProblem."""
+    E: Any
+    A: Any
+    G: LDLt
+    Q: LDLt
+
+
+@dataclass
+class Doubling:
+    """Dense discrete-time algorithm tag: the squared Smith iteration for a GDALEProblem and the structure-preserving doubling algorithm for
+    a GDAREProblem, on the device.  The iteration runs at order n (any n up to 46340 whose 7 n² resp. 18 n² doubles fit in device memory).
+    tol None: 10 n eps on the relative step ‖ΔH‖_F / ‖H‖_F (converged once that holds and ‖A_k‖_F < 1); max_refine: Newton (Hewer) steps of
+    the DARE while the scaled residual exceeds 100 n eps and decreases (the Stein solver takes none).  A pencil with eigenvalues on or
+    outside the unit circle (Stein), a symplectic pencil with eigenvalues on the unit circle or a plant that is not d-stabilizable (DARE)
+    raise DREError(-7)."""
+    maxiters: int = 50
+    tol: Optional[float] = None
+    max_refine: int = 2
+
+
+def _doubling_check(name, alg):
+    if not isinstance(alg, Doubling):
+        raise TypeError(f"{name} takes alg = Doubling(), not {type(alg).__name__}; nothing was run on the device")
+    if not (isinstance(alg.maxiters, (int, np.integer)) and 1 <= alg.maxiters <= 1000):
+        raise ValueError(f"{name}: Doubling.maxiters must be an integer in 1 .. 1000, got {alg.maxiters!r}; nothing was run on the device")
+    if not (isinstance(alg.max_refine, (int, np.integer)) and alg.max_refine >= 0):
+        raise ValueError(f"{name}: Doubling.max_refine must be an integer >= 0, got {alg.max_refine!r}; nothing was run on the device")
+    if alg.tol is not None and not (np.isfinite(alg.tol) and alg.tol > 0):
+        raise ValueError(f"{name}: Doubling.tol must be None or a positive number, got {alg.tol!r}; nothing was run on the device")
+
+
+def _square_pencil(name, E, A):
+    E, A = _dense_f64(E), _dense_f64(A)
+    n = E.shape[0] if E.ndim == 2 else 0
+    if E.ndim != 2 or n < 1 or E.shape != (n, n) or A.shape != (n, n):
+        raise ValueError(f"{name}: E and A must be square of the same order n >= 1, got {E.shape} and {A.shape}; nothing was run on the device")
+    return E, A, n
+
+
+def _gdale_operands(name, prob, X=None):
+    if not isinstance(prob, GDALEProblem):
+        raise TypeError(f"{name} takes a GDALEProblem, not {type(prob).__name__}; nothing was run on the device")
+    E, A, n = _square_pencil(name, prob.E, prob.A)
+    Cm = _dense_f64(prob.C.dense() if isinstance(prob.C, LDLt) else prob.C)
+    if Cm.shape != (n, n):
+        raise ValueError(f"{name}: C must be {n} x {n}, got {Cm.shape}; nothing was run on the device")
+    if X is None:
+        return E, A, Cm
+    X = _dense_f64(X)
+    if X.shape != (n, n):
+        raise ValueError(f"{name}: X must be {n} x {n}, got {X.shape}; nothing was run on the device")
+    return E, A, Cm, X
+
+
+def _gdare_check(name, E, A, B, Ct, Rinv, S):
+    """shapes of a DARE's operands (Ct is n x q) -> the dense f64 operands, Rinv and S None for the identity"""
+    E, A, n = _square_pencil(name, E, A)
+    B, Ct = _dense_f64(B), _dense_f64(Ct)
+    if B.ndim != 2 or Ct.ndim != 2 or B.shape[0] != n or Ct.shape[0] != n or B.shape[1] < 1 or Ct.shape[1] < 1:
+        raise ValueError(f"{name}: B must be {n} x m and C q x {n} with m, q >= 1, got B {B.shape} and C {Ct.T.shape}; nothing was run on the device")
+    inner = []
+    for nm, M, k in (("Rinv", Rinv, B.shape[1]), ("S", S, Ct.shape[1])):
+        if M is not None:
+            M = _dense_f64(M)
+            if M.shape != (k, k):
+                raise ValueError(f"{name}: {nm} must be {k} x {k}, got {M.shape}; nothing was run on the device")
+        inner.append(M)
+    return E, A, B, Ct, inner[0], inner[1]
+
+
+def _gdare_operands(name, prob):
+    """the checked host operands of a GDAREProblem with the scalars folded into the inner matrices (None: identity), as _gare_dense_operands"""
+    if not isinstance(prob, GDAREProblem):
+        raise TypeError(f"{name} takes a GDAREProblem, not {type(prob).__name__}; nothing was run on the device")
+    try:
+        beta, B, Rinv = prob.G
+        gamma, Ct, S = prob.Q
+    except (TypeError, ValueError):
+        raise TypeError(f"{name}: G and Q must be lowrank(B, Rinv) and lowrank(Ct, S) objects; nothing was run on the device") from None
+    Rinv, S = np.asarray(Rinv, dtype=float), np.asarray(S, dtype=float)
+    m, q = np.shape(B)[-1], np.shape(Ct)[-1]
+    Rs = None if beta == 1 and np.array_equal(Rinv, np.eye(m)) else beta * Rinv
+    Ss = None if gamma == 1 and np.array_equal(S, np.eye(q)) else gamma * S
+    return _gdare_check(name, prob.E, prob.A, B, Ct, Rs, Ss)
+
+
+def _upload_all(ctx, mats):
+    ups = [ctx.upload(M) if M is not None else None for M in mats]
+    return ups, [u.ptr if u is not None else None for u in ups]
+
+
+def _gdare_feedback(E, A, B, Ct, Rs, Ss, X):
+    """K = R⁻¹Bᵀ X (I + GX)⁻¹ A"""
+    RB = B.T if Rs is None else Rs @ B.T
+    return RB @ X @ np.linalg.solve(np.eye(E.shape[0]) + B @ (RB @ X), A)
+
+
+def solve_gdale_dense(prob: GDALEProblem, alg=None, dual=False, ctx=None, return_info=False):
+    """solve(::GDALEProblem, ::Doubling): the dense X of AᵀXA − EᵀXE = −C (dual=True: A X Aᵀ − E X Eᵀ = −C) by the squared Smith iteration on
+    E⁻¹A on the device (`dre_dense_stein_solve`): one Gauss-Jordan inversion, three GEMMs and one fused update per iteration.  E⁻¹A must have
+    its eigenvalues inside the unit circle (DREError(-7) otherwise).  return_info: (X, dict(iters, step)).  Wrong types and shapes are errors
+    before anything runs on the device."""
+    name = "solve_gdale_dense"
+    alg = Doubling() if alg is None else alg
+    _doubling_check(name, alg)
+    E, A, Cm = _gdale_operands(name, prob)
+    ctx = ctx or dev.default_context()
+    keep, ptrs = _upload_all(ctx, (E, A, Cm))
+    xp = C.c_void_p()
+    ii, dd = (C.c_int64 * 2)(), (C.c_double * 2)()
+    maxiters, tol, _ = _sign_params(alg)
+    ctx.chk(ctx.lib.dre_dense_stein_solve(ctx.ptr, *ptrs, 1 if dual else 0, maxiters, tol, C.byref(xp), ii, dd))
+    X = dev.DenseMatrix(ctx, xp).numpy()
+    del keep
+    return (X, dict(iters=int(ii[0]), step=float(dd[0]))) if return_info else X
+
+
+def gdale_residual_dense(prob: GDALEProblem, X, dual=False, ctx=None, return_info=False):
+    """C + AᵀXA − EᵀXE (dual=True: C + A X Aᵀ − E X Eᵀ), symmetrised, on the device as an ndarray; return_info adds dict(norm, scaled) with
+    the scaled norm ‖R‖_F / (‖C‖_F + ‖AᵀXA‖_F + ‖EᵀXE‖_F)."""
+    E, A, Cm, Xh = _gdale_operands("gdale_residual_dense", prob, X)
+    ctx = ctx or dev.default_context()
+    keep, ptrs = _upload_all(ctx, (E, A, Cm, Xh))
+    rp, nrm, sc = C.c_void_p(), C.c_double(), C.c_double()
+    ctx.chk(ctx.lib.dre_dense_stein_residual(ctx.ptr, *ptrs, 1 if dual else 0, C.byref(rp), C.byref(nrm), C.byref(sc)))
+    R = dev.DenseMatrix(ctx, rp).numpy()
+    del keep
+    return (R, dict(norm=nrm.value, scaled=sc.value)) if return_info else R
+
+
+def solve_gdare_dense(prob: GDAREProblem, alg=None, ctx=None, return_info=False):
+    """solve(::GDAREProblem, ::Doubling): the dense stabilizing solution X of Q + AᵀX(I + GX)⁻¹A − EᵀXE = 0 with G = β B R⁻¹ Bᵀ and
+    Q = γ Cᵀ S C on the device (`dre_dense_dare_solve`): the structure-preserving doubling algorithm at order n and up to alg.max_refine
+    Newton (Hewer) steps.  Open-loop unstable plants are fine as long as (A, B, E) is d-stabilizable and (A, C, E) d-detectable.
+    return_info: (X, dict(iters, refinements, res0, res, K)) with the scaled residuals ‖R‖_F / (‖Q‖_F + ‖AᵀX(I + GX)⁻¹A‖_F + ‖EᵀXE‖_F) after
+    the doubling and at the end, and the feedback K = R⁻¹Bᵀ X (I + GX)⁻¹ A (β folded in)."""
+    name = "solve_gdare_dense"
+    alg = Doubling() if alg is None else alg
+    _doubling_check(name, alg)
+    E, A, B, Ct, Rs, Ss = _gdare_operands(name, prob)
+    ctx = ctx or dev.default_context()
+    keep, (pE, pA, pB, pCt, pR, pS) = _upload_all(ctx, (E, A, B, Ct, Rs, Ss))
+    xp = C.c_void_p()
+    ii, dd = (C.c_int64 * 2)(), (C.c_double * 2)()
+    maxiters, tol, max_refine = _sign_params(alg)
+    ctx.chk(ctx.lib.dre_dense_dare_solve(ctx.ptr, pE, pA, pB, pR, pCt, pS, maxiters, tol, max_refine, C.byref(xp), ii, dd))
+    X = dev.DenseMatrix(ctx, xp).numpy()
+    del keep
+    if return_info:
+        return X, dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1]), K=_gdare_feedback(E, A, B, Ct, Rs, Ss, X))
+    return X
+
+
+def solve_gdare_pair(E, A, B, C_out, alg=None, Rinv=None, S=None, ctx=None, return_info=False):
+    """Both Riccati equations of discrete-time LQG design from ONE doubling (`dre_dense_dare_solve_pair`) -> (X, Y):
+        Q + AᵀX(I + GX)⁻¹A − EᵀXE = 0   (regulator)        G + A Y (I + QY)⁻¹ Aᵀ − E Y Eᵀ = 0   (filter)        G = B R⁻¹ Bᵀ, Q = Cᵀ S C
+    (Rinv m x m and S q x q: None is the identity).  X is bit for bit what solve(GDAREProblem(E, A, G, Q), Doubling()) returns; Y is the limit
+    of the G-sequence of the same doubling and needs no back-transformation.  return_info=True adds dict(iters, regulator=dict(iters,
+    refinements, res0, res), filter=the same, K, L) with K = R⁻¹Bᵀ X (I + GX)⁻¹ A and the Kalman gain L = A Y (I + QY)⁻¹ Cᵀ S.  Wrong types
+    and shapes are errors before anything runs on the device."""
+    name = "solve_gdare_pair"
+    alg = Doubling() if alg is None else alg
+    _doubling_check(name, alg)
+    Ch = _dense_f64(C_out)
+    if Ch.ndim != 2:
+        raise ValueError(f"{name}: C must be q x n, got {Ch.shape}; nothing was run on the device")
+    Eh, Ah, Bh, Ct, Rh, Sh = _gdare_check(name, E, A, B, np.ascontiguousarray(Ch.T), Rinv, S)
+    ctx = ctx or dev.default_context()
+    keep, (pE, pA, pB, pCt, pR, pS) = _upload_all(ctx, (Eh, Ah, Bh, Ct, Rh, Sh))
+    maxiters, tol, max_refine = _sign_params(alg)
+    xp, yp = C.c_void_p(), C.c_void_p()
+    ii, dd = (C.c_int64 * 4)(), (C.c_double * 4)()
+    ctx.chk(ctx.lib.dre_dense_dare_solve_pair(ctx.ptr, pE, pA, pB, pR, pCt, pS, maxiters, tol, max_refine, C.byref(xp), C.byref(yp), ii, dd))
+    X, Y = dev.DenseMatrix(ctx, xp).numpy(), dev.DenseMatrix(ctx, yp).numpy()
+    del keep
+    if not return_info:
+        return X, Y
+    SC = Ct.T if Sh is None else Sh @ Ct.T
+    L = Ah @ Y @ np.linalg.solve(np.eye(Eh.shape[0]) + Ct @ (SC @ Y), Ct @ (np.eye(Ct.shape[1]) if Sh is None else Sh))
+    info = dict(iters=int(ii[0]), regulator=dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1])),
+                filter=dict(iters=int(ii[2]), refinements=int(ii[3]), res0=float(dd[2]), res=float(dd[3])),
+                K=_gdare_feedback(Eh, Ah, Bh, Ct, Rh, Sh, X), L=L)
+    return (X, Y), info
+
+
+def gdare_residual_dense(prob: GDAREProblem, X, ctx=None, return_info=False):
+    """Q + AᵀX(I + GX)⁻¹A − EᵀXE (symmetrised) on the device as an ndarray; return_info adds dict(norm, scaled) with the scaled norm of
+    solve_gdare_dense."""
+    name = "gdare_residual_dense"
+    E, A, B, Ct, Rs, Ss = _gdare_operands(name, prob)
+    Xh = _dense_f64(X)
+    if Xh.shape != E.shape:
+        raise ValueError(f"{name}: X must be {E.shape[0]} x {E.shape[0]}, got {Xh.shape}; nothing was run on the device")
+    ctx = ctx or dev.default_context()
+    keep, (pE, pA, pB, pCt, pR, pS, pX) = _upload_all(ctx, (E, A, B, Ct, Rs, Ss, Xh))
+    rp, nrm, sc = C.c_void_p(), C.c_double(), C.c_double()
+    ctx.chk(ctx.lib.dre_dense_dare_residual(ctx.ptr, pE, pA, pB, pR, pCt, pS, pX, C.byref(rp), C.byref(nrm), C.byref(sc)))
+    R = dev.DenseMatrix(ctx, rp).numpy()
+    del keep
+    return (R, dict(norm=nrm.value, scaled=sc.value)) if return_info else R
+
+
 def solve(prob, alg, **kw):
     """CommonSolve.solve for the problems of this path."""
     if isinstance(prob, GDREProblem):
@@ -3060,4 +3277,8 @@ def solve(prob, alg, **kw):
         if isinstance(alg, MatrixSign):
             return solve_gare_dense(prob, alg, **kw)
         return solve_gare(prob, alg, **kw)
+    if isinstance(prob, GDALEProblem):
+        return solve_gdale_dense(prob, alg, **kw)
+    if isinstance(prob, GDAREProblem):
+        return solve_gdare_dense(prob, alg, **kw)
     raise TypeError(f"unsupported problem type {type(prob).__name__}")

@@ -13,6 +13,7 @@
 #include "dense_are.hpp"
 #include "dense_are_batch.hpp"
 #include "dense_batch.hpp"
+#include "dense_doubling.hpp"
 #include "dense_gj.hpp"
 #include "dense_sign.hpp"
 #include "dense_sign_lr.hpp"
@@ -88,7 +89,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 117; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 118; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -103,6 +104,8 @@ int dre_version(void) { return 117; }  // 101: dense path (dre_dense_gale_solve,
                                         //      dre_transfer_eval, dre_transfer_eval_batched)
                                         // 116: dre_adi_chain_probe (test surface of the dense-inverse ADI chain)
                                         // 117: time response of dense descriptor systems: step, impulse, simulate (dre_time_response)
+                                        // 118: discrete-time dense solvers by doubling: Stein and DARE (dre_dense_stein_solve, dre_dense_stein_residual,
+                                        //      dre_dense_dare_solve, dre_dense_dare_solve_pair, dre_dense_dare_residual)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -1602,6 +1605,62 @@ int dre_dense_gare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A
         auto* out = new dre_dense();
         out->m = std::move(R);
         if (norm) *norm = fro;
+        *Res = out;
+    });
+}
+int dre_dense_stein_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* Q, int dual, int maxiters, double tol, dre_dense** X,
+                          int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && Q && X, "dre_dense_stein_solve: null argument");
+        DenseSteinResult r = dense_stein_solve(&ctx->c, E->m, A->m, Q->m, dual != 0, maxiters, tol);
+        if (iinfo) { iinfo[0] = r.iters; iinfo[1] = 0; }
+        if (dinfo) { dinfo[0] = r.step; dinfo[1] = r.step; }
+        auto* out = new dre_dense();
+        out->m = std::move(r.X);
+        *X = out;
+    });
+}
+int dre_dense_stein_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* Q, const dre_dense* X, int dual, dre_dense** Res,
+                             double* norm, double* scaled) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && Q && X && Res, "dre_dense_stein_residual: null argument");
+        Mat R = dense_stein_residual(&ctx->c, E->m, A->m, Q->m, X->m, dual != 0, norm, scaled);
+        auto* out = new dre_dense();
+        out->m = std::move(R);
+        *Res = out;
+    });
+}
+int dre_dense_dare_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                         const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && B && Ct && X, "dre_dense_dare_solve: null argument");
+        DenseDareResult r = dense_dare_solve(&ctx->c, E->m, A->m, B->m, Rinv ? &Rinv->m : nullptr, Ct->m, S ? &S->m : nullptr, maxiters, tol, max_refine);
+        if (iinfo) { iinfo[0] = r.iters; iinfo[1] = r.refinements; }
+        if (dinfo) { dinfo[0] = r.res0; dinfo[1] = r.res; }
+        auto* out = new dre_dense();
+        out->m = std::move(r.X);
+        *X = out;
+    });
+}
+int dre_dense_dare_solve_pair(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                              const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, dre_dense** Y, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && B && Ct && X && Y, "dre_dense_dare_solve_pair: null argument");
+        DenseDarePair r = dense_dare_solve_pair(&ctx->c, E->m, A->m, B->m, Rinv ? &Rinv->m : nullptr, Ct->m, S ? &S->m : nullptr, maxiters, tol, max_refine);
+        if (iinfo) { iinfo[0] = r.X.iters; iinfo[1] = r.X.refinements; iinfo[2] = r.Y.iters; iinfo[3] = r.Y.refinements; }
+        if (dinfo) { dinfo[0] = r.X.res0; dinfo[1] = r.X.res; dinfo[2] = r.Y.res0; dinfo[3] = r.Y.res; }
+        auto Xo = std::make_unique<dre_dense>(), Yo = std::make_unique<dre_dense>();
+        Xo->m = std::move(r.X.X); Yo->m = std::move(r.Y.X);
+        *X = Xo.release(); *Y = Yo.release();
+    });
+}
+int dre_dense_dare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                            const dre_dense* S, const dre_dense* X, dre_dense** Res, double* norm, double* scaled) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(E && A && B && Ct && X && Res, "dre_dense_dare_residual: null argument");
+        Mat R = dense_dare_residual(&ctx->c, E->m, A->m, B->m, Rinv ? &Rinv->m : nullptr, Ct->m, S ? &S->m : nullptr, X->m, norm, scaled);
+        auto* out = new dre_dense();
+        out->m = std::move(R);
         *Res = out;
     });
 }

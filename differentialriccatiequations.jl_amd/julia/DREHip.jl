@@ -644,6 +644,76 @@ function residual(prob::DenseGAREProblem, X::AbstractMatrix; ctx::Context=defaul
     download(ctx, R[]), nrm[]
 end
 
+"""Discrete-time algorithm tag (dre_version >= 118): the squared Smith iteration for a `DenseGDALEProblem`, the structure-preserving doubling
+algorithm for a `DenseGDAREProblem`; tol = 0: 10 n eps on the relative step; max_refine Newton (Hewer) steps of the DARE."""
+Base.@kwdef struct Doubling; maxiters::Int = 50; tol::Float64 = 0.0; max_refine::Int = 2; end
+
+"Generalized Stein equation A'XA - E'XE = -C, all dense (`dual = true` in `solve`: A X A' - E X E' = -C)"
+struct DenseGDALEProblem; E; A; C; end
+
+"""Generalized DARE: Q + A'X(I + GX)⁻¹A - E'XE = 0 with G = β B R⁻¹ Bᵀ, Q = γ Cᵀ S C, all dense; the fields of `DenseGAREProblem`."""
+Base.@kwdef struct DenseGDAREProblem; E; A; B; Rinv = nothing; Ct; S = nothing; beta::Float64 = 1.0; gamma::Float64 = 1.0; end
+
+gare_operands(ctx::Context, prob::DenseGDAREProblem) =
+    gare_operands(ctx, DenseGAREProblem(E = prob.E, A = prob.A, B = prob.B, Rinv = prob.Rinv, Ct = prob.Ct, S = prob.S, beta = prob.beta, gamma = prob.gamma))
+
+"solve(DenseGDALEProblem, Doubling()): (X, info) by the squared Smith iteration on E⁻¹A (DREError(-7) unless its eigenvalues lie inside the unit circle)"
+function CommonSolve.solve(prob::DenseGDALEProblem, alg::Doubling; dual::Bool=false, ctx::Context=default_context())
+    ops = [upload(ctx, Matrix{Float64}(M)) for M in (prob.E, prob.A, prob.C)]
+    X = Ref{Ptr{Cvoid}}(C_NULL)
+    ii, dd = zeros(Int64, 2), zeros(2)
+    GC.@preserve ops chk(ctx, ccall((:dre_dense_stein_solve, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cdouble, Ref{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Float64}),
+                   ctx.ptr, ops[1].ptr, ops[2].ptr, ops[3].ptr, dual ? 1 : 0, alg.maxiters, alg.tol, X, ii, dd))
+    download(ctx, X[]), (iters = ii[1], step = dd[1])
+end
+
+"residual(::DenseGDALEProblem, X): (C + A'XA - E'XE, its Frobenius norm, the scaled norm)"
+function residual(prob::DenseGDALEProblem, X::AbstractMatrix; dual::Bool=false, ctx::Context=default_context())
+    ops = [upload(ctx, Matrix{Float64}(M)) for M in (prob.E, prob.A, prob.C, X)]
+    R, nrm, sc = Ref{Ptr{Cvoid}}(C_NULL), Ref{Cdouble}(0.0), Ref{Cdouble}(0.0)
+    GC.@preserve ops chk(ctx, ccall((:dre_dense_stein_residual, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}, Ref{Cdouble}, Ref{Cdouble}),
+                   ctx.ptr, ops[1].ptr, ops[2].ptr, ops[3].ptr, ops[4].ptr, dual ? 1 : 0, R, nrm, sc))
+    download(ctx, R[]), nrm[], sc[]
+end
+
+"solve(DenseGDAREProblem, Doubling()): the dense stabilizing X, (X, info)"
+function CommonSolve.solve(prob::DenseGDAREProblem, alg::Doubling; ctx::Context=default_context())
+    ops, p = gare_operands(ctx, prob)
+    X = Ref{Ptr{Cvoid}}(C_NULL)
+    ii, dd = zeros(Int64, 2), zeros(2)
+    GC.@preserve ops chk(ctx, ccall((:dre_dense_dare_solve, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Float64}),
+                   ctx.ptr, p(ops[1]), p(ops[2]), p(ops[3]), p(ops[5]), p(ops[4]), p(ops[6]), alg.maxiters, alg.tol, alg.max_refine, X, ii, dd))
+    download(ctx, X[]), (iters = ii[1], refinements = ii[2], res0 = dd[1], res = dd[2])
+end
+
+"""Both solutions of discrete-time LQG design from ONE doubling (dre_dense_dare_solve_pair): (X, Y, info) with the regulator's
+Q + A'X(I + GX)⁻¹A - E'XE = 0 and the filter's G + A Y (I + QY)⁻¹ A' - E Y E' = 0; X is bit for bit the X of `solve(prob, Doubling())`."""
+function solve_gdare_pair(prob::DenseGDAREProblem; alg::Doubling=Doubling(), ctx::Context=default_context())
+    ops, p = gare_operands(ctx, prob)
+    X, Y = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    ii, dd = zeros(Int64, 4), zeros(4)
+    GC.@preserve ops chk(ctx, ccall((:dre_dense_dare_solve_pair, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cint, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}},
+                    Ptr{Int64}, Ptr{Float64}),
+                   ctx.ptr, p(ops[1]), p(ops[2]), p(ops[3]), p(ops[5]), p(ops[4]), p(ops[6]), alg.maxiters, alg.tol, alg.max_refine, X, Y, ii, dd))
+    download(ctx, X[]), download(ctx, Y[]), (iters = ii[1], regulator = (refinements = ii[2], res0 = dd[1], res = dd[2]),
+                                             filter = (refinements = ii[4], res0 = dd[3], res = dd[4]))
+end
+
+"residual(::DenseGDAREProblem, X): (Q + A'X(I + GX)⁻¹A - E'XE, its Frobenius norm, the scaled norm)"
+function residual(prob::DenseGDAREProblem, X::AbstractMatrix; ctx::Context=default_context())
+    ops, p = gare_operands(ctx, prob)
+    Xd = upload(ctx, Matrix{Float64}(X))
+    R, nrm, sc = Ref{Ptr{Cvoid}}(C_NULL), Ref{Cdouble}(0.0), Ref{Cdouble}(0.0)
+    GC.@preserve ops Xd chk(ctx, ccall((:dre_dense_dare_residual, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Cdouble}, Ref{Cdouble}),
+                   ctx.ptr, p(ops[1]), p(ops[2]), p(ops[3]), p(ops[5]), p(ops[4]), p(ops[6]), Xd.ptr, R, nrm, sc))
+    download(ctx, R[]), nrm[], sc[]
+end
+
 """Step-size control of the dense Ros2 path, `solve(prob, Ros2(inner_alg = MatrixSign()); dt = dt0, adaptive = StepControl(...))`: a trial step is
 judged by Ros2's embedded first-order solution (weighted RMS error with `rtol`, `atol`), accepted iff err ≤ 1, the next size is
 τ·clamp(0.9·err^(−1/2), 0.2, 5) inside [dt_min, dt_max]; `tspan[2]` and the `tstops` are hit exactly.  DREError(-8) on a rejection at `dt_min`
@@ -727,6 +797,6 @@ function sym_eigh(A::AbstractMatrix; method::Symbol=:jacobi, tol::Float64=0.0, s
 end
 
 export Context, Pencil, LDLᵀ, lowrank, compress!, compress_fast!, concatenate!, residual, lyapunov_apply, ADI, Shifts, Callbacks, GALEProblem, GDREProblem, DRESolution, Ros1, Ros2,
-       Ros3, Ros4, MatrixSign, StepControl, FactoredSign, SignFactorization, solve_lr, solve_dense, DenseGAREProblem, LowRankUpdate, lr_update, ADISolver, isdone, solve, sym_eigh
+       Ros3, Ros4, MatrixSign, StepControl, FactoredSign, SignFactorization, solve_lr, solve_dense, DenseGAREProblem, Doubling, DenseGDALEProblem, DenseGDAREProblem, solve_gdare_pair, LowRankUpdate, lr_update, ADISolver, isdone, solve, sym_eigh
 
 end # module

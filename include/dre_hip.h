@@ -513,6 +513,44 @@ int dre_dense_gare_solve_pair(dre_ctx* ctx, const dre_dense* E, const dre_dense*
  * *norm = ||Res||_F.  G, Q as for dre_dense_gare_solve. */
 int dre_dense_gare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
                             const dre_dense* S, const dre_dense* X, dre_dense** Res, double* norm);
+/* Discrete-time dense solvers by doubling (dre_version >= 118; csrc/dense_doubling.hip).
+ * Generalized Stein equation  A'XA - E'XE = -Q  (dual != 0:  A X A' - E X E' = -Q)  by the squared Smith iteration on M = E^-1 A:
+ * H_{k+1} = H_k + sym(M_k' H_k M_k), M_{k+1} = M_k^2, H_0 = sym(Q), X = sym(E^-T H E^-1); one Gauss-Jordan inversion (of E) in the whole call.
+ * E, A, Q n x n, n <= 46340; *X a new n x n matrix, symmetric bit for bit.  The iteration ends when the relative step ||dH||_F / ||H||_F is at
+ * most tol (tol <= 0: 10 n eps) AND ||M_k||_F < 1.  Errors: DRE_ERR_NOT_STABLE when it produces non-finite values or does not converge in
+ * maxiters (E^-1 A has eigenvalues on or outside the unit circle); DRE_ERR_SINGULAR for a singular E; DRE_ERR_ALLOC from the up-front check of
+ * 7 n^2 doubles; DRE_ERR_INVALID for shapes and maxiters outside 1 .. 1000, before any kernel.
+ * iinfo: [0] doubling iterations [1] 0;  dinfo: [0] [1] the last relative step */
+int dre_dense_stein_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* Q, int dual, int maxiters, double tol, dre_dense** X,
+                          int64_t* iinfo, double* dinfo);
+/* Res = sym(Q + A'XA - E'XE) (dual != 0: Q + A X A' - E X E') as a new n x n matrix; *norm = ||Res||_F, *scaled = ||Res||_F / (||Q||_F + ||A'XA||_F +
+ * ||E'XE||_F); either may be NULL */
+int dre_dense_stein_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* Q, const dre_dense* X, int dual, dre_dense** Res,
+                             double* norm, double* scaled);
+/* Generalized discrete-time algebraic Riccati equation
+ *     Q + A'X (I + G X)^-1 A - E'XE = 0      (= A'XA - E'XE - A'XB (R + B'XB)^-1 B'XA + Q),      G = B Rinv B', Q = Ct S Ct',
+ * by the structure-preserving doubling algorithm on (E^-1 A, E^-1 G E^-T, Q): per iteration one Gauss-Jordan inversion of order n (of
+ * I + G_k H_k) with one Newton-Schulz correction, nine products and one fused update; X = sym(E^-T H_inf E^-1).  Arguments and the NULL-means-identity convention of Rinv and S
+ * as for dre_dense_gare_solve; any n <= 46340.  Then up to max_refine Newton (Hewer) steps  A_c' D A_c - E'DE = -R(X), X <- X + D  on the
+ * closed loop A_c = (I + G X)^-1 A with the Stein solver above, while the scaled residual
+ * ||R(X)||_F / (||Q||_F + ||A'X (I + G X)^-1 A||_F + ||E'XE||_F) exceeds 100 n eps and decreases.
+ * Errors: DRE_ERR_NOT_STABLE when the doubling produces non-finite values or does not converge in maxiters (symplectic pencil with
+ * eigenvalues on or near the unit circle: (A, B, E) not d-stabilizable or (A, C, E) not d-detectable) and when a refinement's closed loop is
+ * not d-stable; DRE_ERR_SINGULAR for a singular E, I + G_k H_k or I + G X.  Device memory of 17 n^2 doubles is checked up front (DRE_ERR_ALLOC).
+ * iinfo: [0] doubling iterations [1] refinement steps;  dinfo: [0] scaled residual after the doubling [1] final */
+int dre_dense_dare_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                         const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo);
+/* Both solutions from ONE doubling: *X as dre_dense_dare_solve returns it for the same arguments, bit for bit, and *Y = G_inf, the
+ * stabilizing solution of the filter equation  G + A Y (I + Q Y)^-1 A' - E Y E' = 0  (no back-transformation), refined by the dual Stein
+ * solve on A (I + Y Q)^-1.  Arguments, limits and errors of dre_dense_dare_solve (18 n^2 doubles); a failure that concerns one solution names
+ * it ("regulator", "filter").  iinfo (4) and dinfo (4) as for dre_dense_gare_solve_pair. */
+int dre_dense_dare_solve_pair(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                              const dre_dense* S, int maxiters, double tol, int max_refine, dre_dense** X, dre_dense** Y, int64_t* iinfo /* 4 */,
+                              double* dinfo /* 4 */);
+/* Res = sym(Q + A'X (I + G X)^-1 A - E'XE) as a new n x n matrix; *norm = ||Res||_F, *scaled the scaled norm above; either may be NULL.
+ * DRE_ERR_SINGULAR for a singular I + G X. */
+int dre_dense_dare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
+                            const dre_dense* S, const dre_dense* X, dre_dense** Res, double* norm, double* scaled);
 /* stored state i of a dense result as a new n x n matrix (sol.X[i]; index 0 is X0) */
 int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X);
 /* per Lyapunov solve j (info[4] of them): iters[j] sign iterations, refinements[j], residuals[2j], residuals[2j+1] relative residual before /
