@@ -13,7 +13,8 @@ from .api import (ADI, ADISolver, Backslash, BlockLinearProblem, BlockLinearSolv
                   freq_response, freq_response_batch, sigma_response, bt_error, transfer_function, transfer_function_batch,
                   step_response, impulse_response, simulate,
                   LQGReducedModel, solve_gare_pair, lqg_balanced_truncation, lqg_characteristic_values, lqg_error,
-                  Doubling, GDALEProblem, GDAREProblem, solve_gdale_dense, solve_gdare_dense, solve_gdare_pair, gdale_residual_dense, gdare_residual_dense)
+                  Doubling, GDALEProblem, GDAREProblem, solve_gdale_dense, solve_gdare_dense, solve_gdare_pair, gdale_residual_dense, gdare_residual_dense,
+                  GSYLEProblem, SylvesterFactorization, solve_gsyle_dense, gsyle_residual_dense, h2_norm, h2_inner, h2_error)
 from .steel_profile import SIZES, initial_value, steel_profile
 
 __all__ = [n for n in dir() if not n.startswith("_")]

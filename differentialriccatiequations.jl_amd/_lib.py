@@ -217,6 +217,12 @@ PROTOTYPES = {
     "dre_dense_dare_solve_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _pvp, _pvp, _pi64, _pd]),
     "dre_dense_dare_residual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pvp, _pd, _pd]),
     "dre_sign_free": (C.c_int, [_vp, _vp]),
+    "dre_dense_sylvester_solve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd]),
+    "dre_dense_sylvester_residual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _pvp, _pd, _pd]),
+    "dre_sylvester_create": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _pvp]),
+    "dre_sylvester_solve": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _pvp, _pi64, _pd]),
+    "dre_sylvester_iters": (C.c_int, [_vp, _pi64]),
+    "dre_sylvester_destroy": (C.c_int, [_vp, _vp]),
     "dre_host_svd_left": (C.c_int, [C.c_int, C.c_int, _pd, _pd, _pd]),
     "dre_dense_invert_batched": (C.c_int, [_vp, C.c_int, _pvp, _pi32, _pd, _pi32]),
     "dre_dense_gale_solve_batched": (C.c_int, [_vp, C.c_int, _pvp, _pvp, _pvp, C.c_int, C.c_double, C.c_int, _pvp, _pi64, _pd, _pi32]),

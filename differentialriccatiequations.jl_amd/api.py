@@ -3263,6 +3263,314 @@ def gdare_residual_dense(prob: GDAREProblem, X, ctx=None, return_info=False):
     return (R, dict(norm=nrm.value, scaled=sc.value)) if return_info else R
 
 
+# ------------------------------------------------------------------------------------------------
+# The generalized Sylvester equation by the coupled sign iteration; H2 norm, inner product and error    (csrc/dense_sylvester.hip)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class GSYLEProblem:
+    """A X F + E X B = −C with A, E n x n, B, F m x m and C n x m; E=None or F=None is the identity.  Both pencils (A, E) and (B, F) must be
+    c-stable."""
+    E: Any
+    A: Any
+    F: Any
+    B: Any
+    C: Any
+
+
+def _gsyle_pencils(name, E, A, F, B):
+    """the checked dense f64 operands (E, F None for the identity) and the orders (n, m)"""
+    A, B = _dense_f64(A), _dense_f64(B)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[0] < 1 or B.shape[0] < 1 or A.shape[0] != A.shape[1] or B.shape[0] != B.shape[1]:
+        raise ValueError(f"{name}: A and B must be square of orders n, m >= 1, got {A.shape} and {B.shape}; nothing was run on the device")
+    n, m = A.shape[0], B.shape[0]
+    out = []
+    for nm, M, k in (("E", E, n), ("F", F, m)):
+        if M is not None:
+            M = _dense_f64(M)
+            if M.shape != (k, k):
+                raise ValueError(f"{name}: {nm} must be {k} x {k} (or None for the identity), got {M.shape}; nothing was run on the device")
+        out.append(M)
+    return out[0], A, out[1], B, n, m
+
+
+def _gsyle_rect(name, what, M, n, m):
+    M = _dense_f64(M)
+    if M.shape != (n, m):
+        raise ValueError(f"{name}: {what} must be {n} x {m}, got {M.shape}; nothing was run on the device")
+    return M
+
+
+def _gsyle_operands(name, prob, X=None):
+    if not isinstance(prob, GSYLEProblem):
+        raise TypeError(f"{name} takes a GSYLEProblem, not {type(prob).__name__}; nothing was run on the device")
+    E, A, F, B, n, m = _gsyle_pencils(name, prob.E, prob.A, prob.F, prob.B)
+    mats = [E, A, F, B, _gsyle_rect(name, "C", prob.C, n, m)]
+    if X is not None:
+        mats.append(_gsyle_rect(name, "X", X, n, m))
+    return mats
+
+
+def _sign_check(name, alg):
+    if not isinstance(alg, MatrixSign):
+        raise TypeError(f"{name} takes alg = MatrixSign(), not {type(alg).__name__}; nothing was run on the device")
+    maxiters, tol, max_refine = _sign_params(alg)
+    if not 1 <= maxiters <= 1000 or max_refine < 0:
+        raise ValueError(f"{name}: MatrixSign.maxiters must be in 1 .. 1000 and max_refine >= 0; nothing was run on the device")
+    return maxiters, tol, max_refine
+
+
+def _transposed_flag(name, transposed):
+    if not isinstance(transposed, (bool, np.bool_)):
+        raise TypeError(f"{name}: transposed must be a bool, not {type(transposed).__name__}; nothing was run on the device")
+    return 1 if transposed else 0
+
+
+def _sylvester_info(ii, dd):
+    return dict(iters=int(ii[0]), refinements=int(ii[1]), res0=float(dd[0]), res=float(dd[1]), step=float(dd[2]))
+
+
+def solve_gsyle_dense(prob: GSYLEProblem, alg=None, transposed=False, ctx=None, return_info=False):
+    """solve(::GSYLEProblem, ::MatrixSign): the dense X of A X F + E X B = −C (transposed=True: AᵀX Fᵀ + EᵀX Bᵀ = −C) by the coupled sign
+    iteration on the device (`dre_dense_sylvester_solve`): the two pencils iterate in lock-step under one scaling factor and the right-hand
+    side rides along; up to alg.max_refine refinement steps replay the residual through the kept sequence.  A pencil that is not c-stable is
+    DREError(-7) and the message names it.  return_info: (X, dict(iters, refinements, res0, res, step)) with the relative residuals
+    ‖C + AXF + EXB‖_F / ‖C‖_F before and after the refinement and C's last relative step.  Wrong types and shapes are errors before anything
+    runs on the device."""
+    name = "solve_gsyle_dense"
+    alg = MatrixSign() if alg is None else alg
+    maxiters, tol, max_refine = _sign_check(name, alg)
+    flag = _transposed_flag(name, transposed)
+    mats = _gsyle_operands(name, prob)
+    ctx = ctx or dev.default_context()
+    keep, (pE, pA, pF, pB, pC) = _upload_all(ctx, mats)
+    xp = C.c_void_p()
+    ii, dd = (C.c_int64 * 2)(), (C.c_double * 3)()
+    ctx.chk(ctx.lib.dre_dense_sylvester_solve(ctx.ptr, pE, pA, pF, pB, pC, flag, maxiters, tol, max_refine, C.byref(xp), ii, dd))
+    X = dev.DenseMatrix(ctx, xp).numpy()
+    del keep
+    return (X, _sylvester_info(ii, dd)) if return_info else X
+
+
+def gsyle_residual_dense(prob: GSYLEProblem, X, transposed=False, ctx=None, return_info=False):
+    """C + A X F + E X B (transposed=True: C + AᵀX Fᵀ + EᵀX Bᵀ) on the device as an ndarray; return_info adds dict(norm, scaled) with the scaled
+    norm ‖Res‖_F / (‖C‖_F + ‖AXF‖_F + ‖EXB‖_F)."""
+    name = "gsyle_residual_dense"
+    flag = _transposed_flag(name, transposed)
+    mats = _gsyle_operands(name, prob, X)
+    ctx = ctx or dev.default_context()
+    keep, (pE, pA, pF, pB, pC, pX) = _upload_all(ctx, mats)
+    rp, nrm, sc = C.c_void_p(), C.c_double(), C.c_double()
+    ctx.chk(ctx.lib.dre_dense_sylvester_residual(ctx.ptr, pE, pA, pF, pB, pC, pX, flag, C.byref(rp), C.byref(nrm), C.byref(sc)))
+    R = dev.DenseMatrix(ctx, rp).numpy()
+    del keep
+    return (R, dict(norm=nrm.value, scaled=sc.value)) if return_info else R
+
+
+class SylvesterFactorization:
+    """A kept coupled sign iteration of the two pencils (A, E) and (B, F) on the device (`dre_sylvester_create`), beside `SignFactorization`:
+    every right-hand side of A X F + E X B = −C, in either direction, costs a replay only.  The operands are dense matrices or `DenseMatrix`
+    objects already on the device; E=None or F=None is the identity.  A context manager; `close()` frees the device memory."""
+
+    def __init__(self, E, A, F, B, maxiters=50, tol=None, ctx=None):
+        name = "SylvesterFactorization"
+        if not (isinstance(maxiters, (int, np.integer)) and 1 <= maxiters <= 1000):
+            raise ValueError(f"{name}: maxiters must be an integer in 1 .. 1000, got {maxiters!r}; nothing was run on the device")
+        if tol is not None and not (np.isfinite(tol) and tol > 0):
+            raise ValueError(f"{name}: tol must be None or a positive number, got {tol!r}; nothing was run on the device")
+        ops = dict(E=E, A=A, F=F, B=B)
+        if not any(isinstance(M, dev.DenseMatrix) for M in ops.values()):
+            ops["E"], ops["A"], ops["F"], ops["B"], _, _ = _gsyle_pencils(name, E, A, F, B)
+        elif ops["A"] is None or ops["B"] is None:
+            raise ValueError(f"{name}: A and B are required; nothing was run on the device")
+        self.ctx = ctx or dev.default_context()
+        d = {k: (M if M is None or isinstance(M, dev.DenseMatrix) else self.ctx.upload(_dense_f64(M))) for k, M in ops.items()}
+        self.n, self.m = d["A"].shape[0], d["B"].shape[0]
+        p = C.c_void_p()
+        self.ctx.chk(self.ctx.lib.dre_sylvester_create(self.ctx.ptr, d["E"].ptr if d["E"] is not None else None, d["A"].ptr,
+                                                       d["F"].ptr if d["F"] is not None else None, d["B"].ptr, int(maxiters),
+                                                       float(tol) if tol is not None else 0.0, C.byref(p)))
+        self.ptr = p
+        self._fin = weakref.finalize(self, self.ctx.lib.dre_sylvester_destroy, self.ctx.ptr, p)
+        it = C.c_int64()
+        self.ctx.lib.dre_sylvester_iters(p, C.byref(it))
+        self.iters = int(it.value)
+
+    def close(self):
+        self._fin()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def solve(self, Cm, transposed=False, download=True, max_refine=2):
+        """A X F + E X B = −C (transposed=True: AᵀX Fᵀ + EᵀX Bᵀ = −C) for an n x m C (ndarray or `DenseMatrix`) -> (X, info); download=False
+        leaves X on the device.  The untransposed X is bit for bit what solve(GSYLEProblem, MatrixSign()) returns."""
+        name = "SylvesterFactorization.solve"
+        flag = _transposed_flag(name, transposed)
+        if not (isinstance(max_refine, (int, np.integer)) and max_refine >= 0):
+            raise ValueError(f"{name}: max_refine must be an integer >= 0, got {max_refine!r}; nothing was run on the device")
+        if isinstance(Cm, dev.DenseMatrix):
+            if Cm.shape != (self.n, self.m):
+                raise ValueError(f"{name}: C must be {self.n} x {self.m}, got {Cm.shape}; nothing was run on the device")
+            Cd = Cm
+        else:
+            Cd = self.ctx.upload(_gsyle_rect(name, "C", Cm, self.n, self.m))
+        xp = C.c_void_p()
+        ii, dd = (C.c_int64 * 2)(), (C.c_double * 3)()
+        self.ctx.chk(self.ctx.lib.dre_sylvester_solve(self.ctx.ptr, self.ptr, Cd.ptr, flag, int(max_refine), C.byref(xp), ii, dd))
+        X = dev.DenseMatrix(self.ctx, xp)
+        return (X.numpy() if download else X), _sylvester_info(ii, dd)
+
+
+def _h2_system(name, what, sys_):
+    """the checked dense operands (E, A, B, C) of one system; E None is the identity"""
+    try:
+        E, A, B, Cm = sys_
+    except (TypeError, ValueError):
+        raise TypeError(f"{name}: {what} must be a tuple (E, A, B, C); nothing was run on the device") from None
+    mats = []
+    for nm, M in (("E", E), ("A", A), ("B", B), ("C", Cm)):
+        if M is None and nm == "E":
+            mats.append(None)
+            continue
+        if not isinstance(M, (np.ndarray, LowRankUpdate, ScaledPencil)) and not sp.issparse(M):
+            raise TypeError(f"{name}: {nm} of {what} must be a matrix, not {type(M).__name__}; nothing was run on the device")
+        mats.append(np.asarray(_dense_operator(M), dtype=float))
+    Eh, Ah, Bh, Ch = mats
+    n = Ah.shape[0] if Ah.ndim == 2 else 0
+    if Eh is None:
+        Eh = np.eye(n)
+    if n < 1 or Ah.shape != (n, n) or Eh.shape != (n, n) or Bh.ndim != 2 or Bh.shape[0] != n or Ch.ndim != 2 or Ch.shape[1] != n:
+        raise ValueError(f"{name}: E and A of {what} must be n x n, B n x m and C q x n; got {Eh.shape}, {Ah.shape}, {Bh.shape}, {Ch.shape}; "
+                         "nothing was run on the device")
+    return Eh, Ah, Bh, Ch
+
+
+def _h2_ports(name, s1, s2):
+    if (s1[2].shape[1], s1[3].shape[0]) != (s2[2].shape[1], s2[3].shape[0]):
+        raise ValueError(f"{name}: the two systems have (m, q) = {(s1[2].shape[1], s1[3].shape[0])} and {(s2[2].shape[1], s2[3].shape[0])}; "
+                         "nothing was run on the device")
+
+
+def _gsyle_residual_device(ctx, Ed, Ad, Fd, Bd, Cd, Xd):
+    """C + A X F + E X B of operands on the device, left there"""
+    rp = C.c_void_p()
+    ctx.chk(ctx.lib.dre_dense_sylvester_residual(ctx.ptr, Ed.ptr, Ad.ptr, Fd.ptr, Bd.ptr, Cd.ptr, Xd.ptr, 0, C.byref(rp), None, None))
+    return dev.DenseMatrix(ctx, rp)
+
+
+def _h2_trace(ctx, Cl, X, dX, Cr):
+    """tr(Cl (X + dX) Crᵀ) from two q x q blocks: the products run on the device, the blocks are added on the host"""
+    return float(sum(np.trace(ctx.gemm(False, True, 1.0, ctx.gemm(False, False, 1.0, Cl, M), Cr).numpy()) for M in (X, dX)))
+
+
+# The H2 formulas cancel, so their traces are wanted to rounding level, eps tr, while a solve stops refining at a relative residual of
+# 100 n eps (measured on SteelProfile(371): the Gramian's residual 2e-12, its trace off by 13 eps tr).  Each trace therefore gets the first-order
+# correction tr(Cl dX Crᵀ), where dX is ONE replay of the solution's residual through the kept sequence: the refinement step the solver's own
+# rule does not take, applied to the trace alone.
+def _h2_norm2(name, system, alg, ctx, side=""):
+    """‖H‖²_H2 = tr(C P Cᵀ), A P Eᵀ + E P Aᵀ = −B Bᵀ: one sign factorisation, the dual replay of B Bᵀ and of the residual; q x q blocks come back"""
+    Eh, Ah, Bh, Ch = system
+    maxiters, tol, max_refine = _sign_params(alg)
+    Ed, Ad, Bd, Cd = (ctx.upload(M) for M in (Eh, Ah, Bh, Ch))
+    try:
+        sign = SignFactorization(Ed, Ad, maxiters, tol if tol > 0 else None, ctx)
+    except DREError as e:
+        if e.code == -7 and side:
+            raise DREError(-7, f"{name}: the {side} is not c-stable ({e})") from None
+        raise
+    try:
+        R = ctx.gemm(False, True, 1.0, Bd, Bd)
+        P, _ = sign.solve_dense(R, max_refine, download=False, transposed=True)
+        Res = _gsyle_residual_device(ctx, Ed, Ad, ctx.upload(np.ascontiguousarray(Eh.T)), ctx.upload(np.ascontiguousarray(Ah.T)), R, P)
+        dP, _ = sign.solve_dense(Res, 0, download=False, transposed=True)
+    finally:
+        sign.close()
+    return _h2_trace(ctx, Cd, P, dP, Cd)
+
+
+def _h2_inner(name, s1, s2, alg, ctx, side=""):
+    """⟨H₁, H₂⟩ = tr(C₁ X C₂ᵀ), A₁ X E₂ᵀ + E₁ X A₂ᵀ = −B₁ B₂ᵀ: one Sylvester factorisation with the right pencil (A₂ᵀ, E₂ᵀ), the replay of B₁ B₂ᵀ
+    and of the residual"""
+    (E1, A1, B1, C1), (E2, A2, B2, C2) = s1, s2
+    maxiters, tol, max_refine = _sign_params(alg)
+    E1d, A1d, B1d, C1d, B2d, C2d = (ctx.upload(M) for M in (E1, A1, B1, C1, B2, C2))
+    E2t, A2t = ctx.upload(np.ascontiguousarray(E2.T)), ctx.upload(np.ascontiguousarray(A2.T))
+    try:
+        fac = SylvesterFactorization(E1d, A1d, E2t, A2t, maxiters, tol if tol > 0 else None, ctx)
+    except DREError as e:
+        if e.code == -7 and side and "right pencil" in str(e):
+            raise DREError(-7, f"{name}: the {side} is not c-stable ({e})") from None
+        raise
+    with fac:
+        R = ctx.gemm(False, True, 1.0, B1d, B2d)
+        X, _ = fac.solve(R, download=False, max_refine=max_refine)
+        dX, _ = fac.solve(_gsyle_residual_device(ctx, E1d, A1d, E2t, A2t, R, X), download=False, max_refine=0)
+    return _h2_trace(ctx, C1d, X, dX, C2d)
+
+
+def h2_norm(E, A, B, C, alg=MatrixSign(), ctx=None):
+    """‖H‖_H2 = √tr(C P Cᵀ) of E ẋ = A x + B u, y = C x (c-stable pencil (A, E); E=None: the identity), where A P Eᵀ + E P Aᵀ = −B Bᵀ: one sign
+    factorisation on the Lyapunov path (`SignFactorization.solve_dense(..., transposed=True)`), one replay of the Gramian's residual, whose trace
+    is added as a first-order correction, and the products on the device; only q x q blocks come back to the host.  DREError(-7) for a pencil that is not c-stable."""
+    name = "h2_norm"
+    _sign_check(name, alg)
+    system = _h2_system(name, "the system", (E, A, B, C))
+    return math.sqrt(max(_h2_norm2(name, system, alg, ctx or dev.default_context()), 0.0))
+
+
+def h2_inner(sys1, sys2, alg=MatrixSign(), ctx=None):
+    """The H2 inner product ⟨H₁, H₂⟩ = tr(C₁ X C₂ᵀ) of two systems (E, A, B, C) with the same numbers of inputs and outputs, where
+    A₁ X E₂ᵀ + E₁ X A₂ᵀ = −B₁ B₂ᵀ: one Sylvester solve (`SylvesterFactorization`) with the right pencil (A₂ᵀ, E₂ᵀ) on the device; only a q x q
+    block comes back.  DREError(-7) names the pencil that is not c-stable."""
+    name = "h2_inner"
+    _sign_check(name, alg)
+    s1, s2 = _h2_system(name, "sys1", sys1), _h2_system(name, "sys2", sys2)
+    _h2_ports(name, s1, s2)
+    return _h2_inner(name, s1, s2, alg, ctx or dev.default_context())
+
+
+def h2_error(E, A, B, C, rom, return_info=False, alg=MatrixSign(), ctx=None):
+    """‖H − H_r‖_H2 of the full system against a `ReducedModel` or `LQGReducedModel` (or a tuple (Er, Ar, Br, Cr)) by the closed formula
+        err² = ‖H‖² − 2 ⟨H, H_r⟩ + ‖H_r‖²
+    from `h2_norm` twice and `h2_inner` once, all on the device.  The formula cancels: its absolute accuracy is of the order
+    floor = eps (‖H‖² + ‖H_r‖²), so an error below √eps ‖H‖ cannot be resolved and err² may come out slightly negative; the function returns
+    √max(err², 0).  return_info adds dict(err2, norm2, norm2_r, inner, floor).  A reduced model that is not c-stable (an `LQGReducedModel` of
+    an unstable plant, for instance) is DREError(-7) and names the reduced side."""
+    name = "h2_error"
+    _sign_check(name, alg)
+    if isinstance(rom, (ReducedModel, LQGReducedModel)):
+        rsys = (rom.Er, rom.Ar, rom.Br, rom.Cr)
+    elif isinstance(rom, tuple) and len(rom) == 4:
+        rsys = rom
+    else:
+        raise TypeError(f"{name}: rom must be a ReducedModel, an LQGReducedModel or a tuple (Er, Ar, Br, Cr), not {type(rom).__name__}; "
+                        "nothing was run on the device")
+    full, red = _h2_system(name, "the system", (E, A, B, C)), _h2_system(name, "the reduced model", rsys)
+    _h2_ports(name, full, red)
+    ctx = ctx or dev.default_context()
+    norm2_r = _h2_norm2(name, red, alg, ctx, side="reduced model")
+    norm2 = _h2_norm2(name, full, alg, ctx)
+    inner = _h2_inner(name, full, red, alg, ctx, side="reduced model")
+    err2 = norm2 - 2.0 * inner + norm2_r
+    err = math.sqrt(max(err2, 0.0))
+    if return_info:
+        return err, dict(err2=err2, norm2=norm2, norm2_r=norm2_r, inner=inner, floor=float(np.finfo(float).eps) * (norm2 + norm2_r))
+    return err
+
+
+def _rom_h2_error(self, E, A, B, C, **kw):
+    """‖H − H_r‖_H2 of the full system (E, A, B, C) against this reduced model: `h2_error` with its keyword arguments"""
+    return h2_error(E, A, B, C, self, **kw)
+
+
+ReducedModel.h2_error = _rom_h2_error
+LQGReducedModel.h2_error = _rom_h2_error
+
+
 def solve(prob, alg, **kw):
     """CommonSolve.solve for the problems of this path."""
     if isinstance(prob, GDREProblem):
@@ -3281,4 +3589,6 @@ def solve(prob, alg, **kw):
         return solve_gdale_dense(prob, alg, **kw)
     if isinstance(prob, GDAREProblem):
         return solve_gdare_dense(prob, alg, **kw)
+    if isinstance(prob, GSYLEProblem):
+        return solve_gsyle_dense(prob, alg, **kw)
     raise TypeError(f"unsupported problem type {type(prob).__name__}")

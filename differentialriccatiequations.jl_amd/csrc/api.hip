@@ -17,6 +17,7 @@
 #include "dense_gj.hpp"
 #include "dense_sign.hpp"
 #include "dense_sign_lr.hpp"
+#include "dense_sylvester.hpp"
 #include "engine.hpp"
 #include "dense_cgj.hpp"
 #include "freq_response.hpp"
@@ -67,6 +68,7 @@ struct dre_gdre_result {
 };
 
 struct dre_sign { std::unique_ptr<SignLyap> s; };
+struct dre_sylvester { std::unique_ptr<SignSylvester> s; };
 
 static thread_local std::string g_noctx_error;
 
@@ -89,7 +91,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 118; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 119; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -106,6 +108,9 @@ int dre_version(void) { return 118; }  // 101: dense path (dre_dense_gale_solve,
                                         // 117: time response of dense descriptor systems: step, impulse, simulate (dre_time_response)
                                         // 118: discrete-time dense solvers by doubling: Stein and DARE (dre_dense_stein_solve, dre_dense_stein_residual,
                                         //      dre_dense_dare_solve, dre_dense_dare_solve_pair, dre_dense_dare_residual)
+                                        // 119: dense generalized Sylvester solver by the coupled sign iteration (dre_dense_sylvester_solve,
+                                        //      dre_dense_sylvester_residual, dre_sylvester_create, dre_sylvester_solve, dre_sylvester_iters,
+                                        //      dre_sylvester_destroy)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -2062,6 +2067,72 @@ int dre_sign_solve_lr_t(dre_ctx* ctx, dre_sign* s, const dre_dense* G, const dre
     return sign_solve_lr(ctx, true, s, G, S, rtol, max_width, max_refine, L, D, ii, dd, "dre_sign_solve_lr_t: null argument");
 }
 int dre_sign_free(dre_ctx*, dre_sign* s) { delete s; return DRE_OK; }
+
+// ---- dense generalized Sylvester solver (dense_sylvester.hip, 119) ---------------------------------------------------------------------
+static void sylvester_info(const SylvStats& st, int64_t* iinfo, double* dinfo) {
+    if (iinfo) { iinfo[0] = st.iters; iinfo[1] = st.refinements; }
+    if (dinfo) { dinfo[0] = st.res0; dinfo[1] = st.res; dinfo[2] = st.step; }
+}
+int dre_dense_sylvester_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* F, const dre_dense* B, const dre_dense* C,
+                              int transposed, int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(A && B && C && X, "dre_dense_sylvester_solve: null argument");
+        DenseSylvesterResult r = dense_sylvester_solve(&ctx->c, E ? &E->m : nullptr, A->m, F ? &F->m : nullptr, B->m, C->m, transposed != 0, maxiters, tol,
+                                                       max_refine);
+        sylvester_info(r.st, iinfo, dinfo);
+        auto* out = new dre_dense();
+        out->m = std::move(r.X);
+        *X = out;
+    });
+}
+int dre_dense_sylvester_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* F, const dre_dense* B, const dre_dense* C,
+                                 const dre_dense* X, int transposed, dre_dense** Res, double* norm, double* scaled) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(A && B && C && X && Res, "dre_dense_sylvester_residual: null argument");
+        Mat R = dense_sylvester_residual(&ctx->c, E ? &E->m : nullptr, A->m, F ? &F->m : nullptr, B->m, C->m, X->m, transposed != 0, norm, scaled);
+        auto* out = new dre_dense();
+        out->m = std::move(R);
+        *Res = out;
+    });
+}
+int dre_sylvester_create(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* F, const dre_dense* B, int maxiters, double tol,
+                         dre_sylvester** out) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(A && B && out, "dre_sylvester_create: null argument");
+        const int n = A->m.rows, m = B->m.rows;
+        DRE_REQUIRE(n >= 1 && m >= 1 && A->m.cols == n && B->m.cols == m && (!E || (E->m.rows == n && E->m.cols == n)) &&
+                        (!F || (F->m.rows == m && F->m.cols == m)),
+                    "dre_sylvester_create: E and A must be n x n, F and B m x m");
+        DRE_REQUIRE(n <= DENSE_MAX_N && m <= DENSE_MAX_N, "dre_sylvester_create: orders of at most " + std::to_string(DENSE_MAX_N) + " expected");
+        auto h = std::make_unique<dre_sylvester>();
+        Mat Ec(c, n, n), Fc(c, m, m);            // the handle outlives the caller's E and F
+        if (E) copy_mat(c, E->m, Ec); else set_identity(c, Ec);
+        if (F) copy_mat(c, F->m, Fc); else set_identity(c, Fc);
+        h->s = std::make_unique<SignSylvester>(c, Ec, Fc, maxiters, tol, 0);
+        h->s->factor(A->m, B->m);
+        *out = h.release();
+    });
+}
+int dre_sylvester_solve(dre_ctx* ctx, dre_sylvester* s, const dre_dense* C, int transposed, int max_refine, dre_dense** X, int64_t* iinfo, double* dinfo) {
+    return guarded(ctx, [&] {
+        Ctx* c = &ctx->c;
+        DRE_REQUIRE(s && C && X && max_refine >= 0, "dre_sylvester_solve: null argument or negative max_refine");
+        auto out = std::make_unique<dre_dense>();
+        out->m = Mat(c, s->s->n(), s->s->m());
+        s->s->set_max_refine(max_refine);
+        const SylvStats st = transposed ? s->s->solve_t(C->m, out->m) : s->s->solve(C->m, out->m);
+        c->sync();
+        sylvester_info(st, iinfo, dinfo);
+        *X = out.release();
+    });
+}
+int dre_sylvester_iters(const dre_sylvester* s, int64_t* n_iters) {
+    if (!s || !n_iters) return DRE_ERR_INVALID;
+    *n_iters = s->s->iters();
+    return DRE_OK;
+}
+int dre_sylvester_destroy(dre_ctx*, dre_sylvester* s) { delete s; return DRE_OK; }
 
 // device SVD and balanced truncation (110)
 int dre_svd_jacobi(dre_ctx* ctx, const dre_dense* A, double tol, dre_dense** U, dre_dense** S, dre_dense** V, int64_t* stats) {

@@ -607,6 +607,7 @@ include("DREHipBalance.jl")           # svd_jacobi, balanced_truncation: device 
 include("DREHipBatchJacobi.jl")       # sym_eigh_batch, svd_jacobi_batch, balance_lr_batch: ensembles in shared launches (dre_version >= 111)
 include("DREHipFreq.jl")              # freq_response, sigma_response, bt_error: frequency response batched by frequency (dre_version >= 112)
 include("DREHipLQG.jl")               # solve_gare_pair, lqg_balanced_truncation, lqg_error: LQG balanced truncation (dre_version >= 113)
+include("DREHipSylvester.jl")         # DenseGSYLEProblem, SylvesterFactorization, h2_norm, h2_inner, h2_error: Sylvester solver and H2 tools (dre_version >= 119; unrun)
 
 """Dense GARE: Q + A'XE + E'XA - E'XGXE = 0 with G = β B R⁻¹ Bᵀ, Q = γ Cᵀ S C (riccati/types.jl:41-52), all dense.  `solve(prob, MatrixSign())`
 returns the stabilizing X from the sign function of the Hamiltonian pencil plus Newton-Kleinman refinement (DREError(-7) when the

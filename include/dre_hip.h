@@ -551,6 +551,39 @@ int dre_dense_dare_solve_pair(dre_ctx* ctx, const dre_dense* E, const dre_dense*
  * DRE_ERR_SINGULAR for a singular I + G X. */
 int dre_dense_dare_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* B, const dre_dense* Rinv, const dre_dense* Ct,
                             const dre_dense* S, const dre_dense* X, dre_dense** Res, double* norm, double* scaled);
+/* Dense generalized Sylvester solver by the coupled sign iteration (dre_version >= 119; csrc/dense_sylvester.hip).
+ *     A X F + E X B = -C      (transposed != 0:  A'X F' + E'X B' = -C),      A, E n x n;  B, F m x m;  C, X n x m;  n, m <= 46340.
+ * E or F NULL means the identity.  Both pencils (A, E) and (B, F) must be c-stable.  Per iteration: L_k = E A_k^-1, R_k = B_k^-1 F (two
+ * Gauss-Jordan inversions), A_{k+1} = A_k/(2c) + (c/2) L_k E, B_{k+1} = B_k/(2c) + (c/2) F R_k, C_{k+1} = C_k/(2c) + (c/2) L_k C_k R_k with ONE
+ * scaling factor c_k = exp((log|det A_k| + log|det B_k| - log|det E| - log|det F|) / (n + m)) for both sides (c = 1 once both distances are
+ * below 1e-2); X = E^-1 C_inf F^-1 / 2.  The iteration ends when ||A_k + E||_F / ||E||_F and ||B_k + F||_F / ||F||_F are both at most tol
+ * (tol <= 0: 10 max(n, m) eps).  Then up to max_refine refinement steps replay the residual through the kept sequence while the relative
+ * residual ||C + A X F + E X B||_F / ||C||_F exceeds 100 max(n, m) eps.  C = 0 returns X = 0 exactly.
+ * Errors: DRE_ERR_NOT_STABLE when a side stagnates away from -E resp. -F, produces non-finite values or does not converge in maxiters (the
+ * message names the pencil: "left pencil (A, E)" or "right pencil (B, F)"); DRE_ERR_SINGULAR for a singular E, F, A_k or B_k (named);
+ * DRE_ERR_INVALID, before any kernel, for shapes and maxiters outside 1 .. 1000, and for a C with non-finite entries; DRE_ERR_ALLOC from the
+ * up-front check of (maxiters + 5)(n^2 + m^2) + 8 n m doubles.
+ * iinfo: [0] sign iterations [1] refinement steps;  dinfo: [0] relative residual before the refinement [1] final [2] C's last relative step */
+int dre_dense_sylvester_solve(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* F, const dre_dense* B, const dre_dense* C,
+                              int transposed, int maxiters, double tol, int max_refine, dre_dense** X, int64_t* iinfo /* 2 */, double* dinfo /* 3 */);
+/* Res = C + A X F + E X B (transposed != 0: C + A'X F' + E'X B') as a new n x m matrix; *norm = ||Res||_F, *scaled = ||Res||_F / (||C||_F +
+ * ||A X F||_F + ||E X B||_F); either may be NULL.  E or F NULL: the identity. */
+int dre_dense_sylvester_residual(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* F, const dre_dense* B, const dre_dense* C,
+                                 const dre_dense* X, int transposed, dre_dense** Res, double* norm, double* scaled);
+/* A kept coupled sign iteration of the two pencils (the Sylvester twin of dre_sign_create): every right-hand side, in either direction, costs
+ * only the recursion of C.  E, F NULL: the identity; the handle keeps its own copies.  Errors as dre_dense_sylvester_solve; device memory of
+ * (maxiters + 5)(n^2 + m^2) + 7 n m doubles is checked before any kernel. */
+typedef struct dre_sylvester dre_sylvester;
+int dre_sylvester_create(dre_ctx* ctx, const dre_dense* E, const dre_dense* A, const dre_dense* F, const dre_dense* B, int maxiters, double tol,
+                         dre_sylvester** out);
+/* A X F + E X B = -C (transposed != 0: A'X F' + E'X B' = -C) for an n x m C on the kept sequence, refined as in dre_dense_sylvester_solve; the
+ * untransposed *X is bit for bit what dre_dense_sylvester_solve returns for the same operands.  iinfo, dinfo as there; the kept state is not
+ * changed. */
+int dre_sylvester_solve(dre_ctx* ctx, dre_sylvester* s, const dre_dense* C, int transposed, int max_refine, dre_dense** X, int64_t* iinfo /* 2 */,
+                        double* dinfo /* 3 */);
+/* *n_iters: sign iterations of the kept sequence */
+int dre_sylvester_iters(const dre_sylvester* s, int64_t* n_iters);
+int dre_sylvester_destroy(dre_ctx* ctx, dre_sylvester* s);
 /* stored state i of a dense result as a new n x n matrix (sol.X[i]; index 0 is X0) */
 int dre_gdre_result_X_dense(dre_ctx* ctx, const dre_gdre_result* r, int i, dre_dense** X);
 /* per Lyapunov solve j (info[4] of them): iters[j] sign iterations, refinements[j], residuals[2j], residuals[2j+1] relative residual before /
