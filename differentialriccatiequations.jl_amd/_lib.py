@@ -86,6 +86,21 @@ class AdiChainProbeArgsC(C.Structure):
     ]
 
 
+class WarmProbeArgsC(C.Structure):
+    _fields_ = [
+        ("stage", C.c_int32), ("n", C.c_int32), ("q", C.c_int32), ("m", C.c_int32),
+        ("kl", C.c_int32), ("qn", C.c_int32), ("nparts", C.c_int32), ("mode", C.c_int32),
+        ("ldpad", C.c_int32), ("reserved", C.c_int32),
+        ("reltol", C.c_double), ("abstol", C.c_double), ("frac", C.c_double), ("budget_frac", C.c_double),
+        ("Q", C.c_void_p), ("Yf", C.c_void_p), ("Pf", C.c_void_p), ("Z1", C.c_void_p), ("Cw", C.c_void_p), ("Res", C.c_void_p), ("Cc", C.c_void_p), ("parts", C.c_void_p),
+        ("S", C.c_void_p), ("Wk", C.c_void_p), ("Yp", C.c_void_p), ("Pp", C.c_void_p), ("tols_in", C.c_void_p), ("basis", C.c_void_p),
+        ("Z1_out", C.c_void_p), ("Cw_out", C.c_void_p), ("slab", C.c_void_p), ("Zb", C.c_void_p), ("Zy", C.c_void_p), ("W2", C.c_void_p), ("tols", C.c_void_p),
+        ("Uc", C.c_void_p), ("T", C.c_void_p), ("Cp", C.c_void_p), ("Mout", C.c_void_p), ("LTout", C.c_void_p), ("U", C.c_void_p), ("R", C.c_void_p),
+        ("basis_out", C.c_void_p),
+        ("ticket", C.c_void_p),
+    ]
+
+
 _vp = C.c_void_p
 _pvp = C.POINTER(C.c_void_p)
 _pd = C.POINTER(C.c_double)
@@ -128,6 +143,7 @@ PROTOTYPES = {
     "dre_sym_eig": (C.c_int, [_vp, _vp, C.c_double, _pvp, _pvp]),
     "dre_sym_eig_probe": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, _pi32, C.c_int, _pi64, _pd] + [_pvp] * 7),
     "dre_adi_chain_probe": (C.c_int, [_vp, C.POINTER(AdiChainProbeArgsC)]),
+    "dre_warm_probe": (C.c_int, [_vp, C.POINTER(WarmProbeArgsC)]),
     "dre_sym_eig_jacobi": (C.c_int, [_vp, _vp, C.c_double, _pvp, _pvp, _pi64]),
     "dre_shift_factor": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_double, _pvp]),
     "dre_shift_solve": (C.c_int, [_vp, _vp, _vp, _pvp, _pvp]),

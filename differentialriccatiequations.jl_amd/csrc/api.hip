@@ -91,7 +91,7 @@ static int guarded(dre_ctx* ctx, F&& f) {
 
 extern "C" {
 
-int dre_version(void) { return 119; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
+int dre_version(void) { return 120; }  // 101: dense path (dre_dense_gale_solve, dre_dense_gdre_solve); 102: dre_dense_invert, dense_gj_panel, n > 4096;
                                         // 103: dense GARE (dre_dense_gare_solve, dre_dense_gare_residual); 104: factored sign solver (dre_sign_*); 105: batched dense path (dre_dense_*_batched);
                                         // 106: batched dense GARE (dre_dense_gare_solve_batched); 107: adaptive dense Ros2 (dre_dense_gdre_solve_adaptive,
                                         // dre_gdre_result_step_stats, DRE_ERR_STEP); 108: dre_gemm_probe (test surface of the GEMM family), gemm_swizzle = 2;
@@ -111,6 +111,7 @@ int dre_version(void) { return 119; }  // 101: dense path (dre_dense_gale_solve,
                                         // 119: dense generalized Sylvester solver by the coupled sign iteration (dre_dense_sylvester_solve,
                                         //      dre_dense_sylvester_residual, dre_sylvester_create, dre_sylvester_solve, dre_sylvester_iters,
                                         //      dre_sylvester_destroy)
+                                        // 120: dre_warm_probe (test surface of the warm-started compression, warm.hip)
 
 int dre_ctx_create(int device, dre_ctx** out) {
     if (!out) return DRE_ERR_INVALID;
@@ -744,6 +745,157 @@ int dre_sym_eig_probe(dre_ctx* ctx, const dre_dense* S, double tolfac, int want_
         dre_dense* res[7] = {od, oe, ot, oV, ow, oZ, oB};
         for (int k = 0; k < 7; ++k) if (outs[k]) *outs[k] = res[k];
         for (auto& m : made) m.release();
+    });
+}
+// ---- dre_warm_probe: the kernels of the warm-started compression (warm.hip) on caller-supplied operands (test and diagnostic surface) -------
+// Every launch goes through warm_project, warm_z, warm_zapply, warm_small, warm_eig, warm_finish or warm_chain_jacobi, with the buffer shapes of
+// their callers (dense_x.hip, compress_warm; ldlt.hip, warm_compress_eig).
+int dre_warm_probe(dre_ctx* ctx, const dre_warm_probe_args* args) {
+    return guarded(ctx, [&] {
+        DRE_REQUIRE(args, "dre_warm_probe: null argument");
+        const dre_warm_probe_args& p = *args;
+        const int st = p.stage, n = p.n, q = p.q, m = p.m, kl = p.kl, qn = p.qn;
+        DRE_REQUIRE(st >= DRE_WARM_PROBE_PROJECT && st <= DRE_WARM_PROBE_CHAIN, "dre_warm_probe: unknown stage");
+        DRE_REQUIRE(p.ldpad >= 0 && p.ldpad <= 64, "dre_warm_probe: ldpad must lie in 0 .. 64");
+        const bool rows_n = st != DRE_WARM_PROBE_SMALL && st != DRE_WARM_PROBE_EIG;
+        if (rows_n) DRE_REQUIRE(n >= 1 && n <= 65536, "dre_warm_probe: n must lie in 1 .. 65536");
+        if (st == DRE_WARM_PROBE_PROJECT || st == DRE_WARM_PROBE_Z || st == DRE_WARM_PROBE_ZAPPLY || st == DRE_WARM_PROBE_SMALL || st == DRE_WARM_PROBE_CHAIN)
+            DRE_REQUIRE(q >= 1 && q <= 64, "dre_warm_probe: q must lie in 1 .. 64");
+        if (st == DRE_WARM_PROBE_Z || st == DRE_WARM_PROBE_CHAIN) DRE_REQUIRE(n <= 1024, "dre_warm_probe: n above 1024 (warm_z keeps all of Z in LDS)");
+        if (st == DRE_WARM_PROBE_PROJECT) DRE_REQUIRE(p.Q && p.Yf && p.Pf, "dre_warm_probe: Q, Yf or Pf missing");
+        if (st == DRE_WARM_PROBE_Z) DRE_REQUIRE(p.Z1 && p.Cw && p.Res, "dre_warm_probe: Z1, Cw or Res missing");
+        if (st == DRE_WARM_PROBE_ZAPPLY) DRE_REQUIRE(p.Z1 && p.Cw, "dre_warm_probe: Z1 or Cw missing");
+        if (st == DRE_WARM_PROBE_SMALL || st == DRE_WARM_PROBE_CHAIN) {
+            const int mm = st == DRE_WARM_PROBE_CHAIN ? q + 16 : m;
+            DRE_REQUIRE(mm == q || mm == q + 16, "dre_warm_probe: m must be q or q + 16");
+            DRE_REQUIRE(mm <= 80, "dre_warm_probe: m above 80");
+            DRE_REQUIRE(qn >= 1 && qn <= mm && (st != DRE_WARM_PROBE_CHAIN || qn <= 64), "dre_warm_probe: qn must lie in 1 .. m (chain: at most 64)");
+            DRE_REQUIRE(kl >= 1 && kl <= qn, "dre_warm_probe: kl must lie in 1 .. qn");
+            DRE_REQUIRE(p.nparts >= 0 && p.nparts <= (1 << 24) && (p.nparts == 0 || p.parts), "dre_warm_probe: nparts without parts");
+            DRE_REQUIRE(p.budget_frac >= 0.0 && p.budget_frac <= 1.0, "dre_warm_probe: budget_frac must lie in 0 .. 1");
+        }
+        if (st == DRE_WARM_PROBE_SMALL) {
+            DRE_REQUIRE(p.mode == 0 || p.mode == 1, "dre_warm_probe: mode must be 0 or 1");
+            DRE_REQUIRE(p.Cc, "dre_warm_probe: Cc missing");
+        }
+        if (st == DRE_WARM_PROBE_EIG) {
+            DRE_REQUIRE(m >= 1 && m <= 80, "dre_warm_probe: m must lie in 1 .. 80");
+            DRE_REQUIRE(p.S, "dre_warm_probe: S missing");
+        }
+        if (st == DRE_WARM_PROBE_FINISH) {
+            DRE_REQUIRE(q >= 1 && q <= 80, "dre_warm_probe: q must lie in 1 .. 80");
+            DRE_REQUIRE(kl >= 1 && kl <= 80, "dre_warm_probe: kl must lie in 1 .. 80");
+            DRE_REQUIRE(p.Q && p.Wk && p.Yp && p.Pp && p.tols_in, "dre_warm_probe: B, Wk, Yp, Pp or tols_in missing");
+        }
+        if (st == DRE_WARM_PROBE_CHAIN) DRE_REQUIRE(p.Res && p.basis, "dre_warm_probe: Res or basis missing");
+        // (the arguments are judged without a context, so that the refusals can be tested on a machine without a device)
+        DRE_REQUIRE(ctx, "dre_warm_probe: arguments accepted, context missing");
+        Ctx* c = &ctx->c;
+        const int ldn = n + p.ldpad;
+        // a matrix of `rows` rows prefilled with NaN (all bits set): the view has the rows the entry points expect, the allocation ld of them
+        auto nan_mat = [&](int rows, int ld, int cols) {
+            Mat full(c, ld, cols);
+            DRE_HIP(hipMemsetAsync(full.p, 0xFF, (size_t)ld * cols * sizeof(double), c->stream));
+            return full.view(0, 0, rows, cols);
+        };
+        auto put = [&](const double* h, const Mat& v, int c0, int rows, int cols) {
+            DRE_HIP(hipMemcpy2DAsync(v.p + (size_t)c0 * v.ld, (size_t)v.ld * sizeof(double), h, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double), (size_t)cols,
+                                     hipMemcpyHostToDevice, c->stream));
+        };
+        auto get = [&](double* h, const Mat& v, int c0, int cols) {          // whole columns of the allocation, padding rows included
+            if (h) DRE_HIP(hipMemcpyAsync(h, v.p + (size_t)c0 * v.ld, (size_t)v.ld * cols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        };
+        auto nan_arr = [&](size_t cnt) {
+            DevArr<double> d(c, std::max<size_t>(cnt, 1));
+            DRE_HIP(hipMemsetAsync(d.p, 0xFF, d.n * sizeof(double), c->stream));
+            return d;
+        };
+        auto up = [&](double* d, const double* h, size_t cnt) { if (cnt) DRE_HIP(hipMemcpyAsync(d, h, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream)); };
+        auto down = [&](double* h, const double* d, size_t cnt) { if (h && cnt) DRE_HIP(hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream)); };
+        if (!c->warm_tickets) {
+            c->warm_tickets = std::make_shared<Buf>(c, 4 * sizeof(int));
+            DRE_HIP(hipMemsetAsync(c->warm_tickets->p, 0, 4 * sizeof(int), c->stream));
+        }
+        int* const tickets = (int*)c->warm_tickets->p;
+        auto finish = [&] {
+            int ht[4] = {-1, -1, -1, -1};
+            DRE_HIP(hipMemcpyAsync(ht, tickets, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            c->sync();
+            if (p.ticket) { p.ticket[0] = ht[0]; p.ticket[1] = ht[1]; }
+        };
+        const int nstrip = rows_n ? ceil_div(n, 16) : 0, nslab = rows_n ? warm_project_slabs(n) : 0;
+        if (st == DRE_WARM_PROBE_PROJECT || st == DRE_WARM_PROBE_Z || st == DRE_WARM_PROBE_ZAPPLY) {
+            // the buffers of the callers: the basis buffer [Om | Q | Z], the right-hand block [Y_p, Y_f, W, Z, W_2], the slab with C behind the shares
+            Mat QO = nan_mat(n, ldn, 32 + q + 16), YB = nan_mat(n, ldn, 64 + q), Z1 = nan_mat(n, ldn, 16);
+            DevArr<double> slab = nan_arr((size_t)nslab * 256 + nstrip + 256);
+            double* const Cw = slab.p + (size_t)nslab * 256 + nstrip;
+            if (st == DRE_WARM_PROBE_PROJECT) {
+                Mat Qv = QO.colsview(32, q), Yf = YB.colsview(16, 16), Pf(c, q, 16);
+                put(p.Q, QO, 32, n, q); put(p.Yf, YB, 16, n, 16); up(Pf.p, p.Pf, (size_t)q * 16);
+                warm_project(c, n, q, Qv, Yf, Pf, Z1, slab.p, tickets, Cw);
+                get(p.Z1_out, Z1, 0, 16); down(p.Cw_out, Cw, 256); down(p.slab, slab.p, (size_t)nslab * 256);
+            } else {
+                put(p.Z1, Z1, 0, n, 16); up(Cw, p.Cw, 256);
+                Mat Zb = QO.colsview(32 + q, 16), Zy = YB.colsview(32 + q, 16), W2 = YB.colsview(48 + q, 16);
+                if (st == DRE_WARM_PROBE_Z) {
+                    Mat Res = nan_mat(n, ldn, n);
+                    put(p.Res, Res, 0, n, n);
+                    warm_z(c, n, Z1, Cw, Res, Zb, Zy, W2);
+                    get(p.W2, YB, 48 + q, 16);
+                } else {
+                    warm_zapply(c, n, Z1, Cw, Zb, Zy);
+                }
+                get(p.Zb, QO, 32 + q, 16); get(p.Zy, YB, 32 + q, 16);
+            }
+            finish();
+            return;
+        }
+        if (st == DRE_WARM_PROBE_SMALL) {
+            Mat Cc(c, m, 64 + q), Uc = nan_mat(m, m, qn), T = nan_mat(kl, kl, kl), Cp = nan_mat(m, m, 16), Mo = nan_mat(m, m, m), LT = nan_mat(m, m, m);
+            up(Cc.p, p.Cc, (size_t)m * (64 + q));
+            DevArr<double> parts(c, std::max(p.nparts, 1)), tols = nan_arr(12);
+            up(parts.p, p.parts, (size_t)p.nparts);
+            warm_small(c, q, m, kl, qn, Cc, p.nparts ? parts.p : nullptr, p.nparts, p.reltol, p.abstol, p.frac, p.budget_frac, tols.p, Uc, T, Cp, tickets + 1,
+                       p.mode == 1 ? &Mo : nullptr, p.mode == 1 ? &LT : nullptr);
+            down(p.tols, tols.p, 12); get(p.Uc, Uc, 0, qn); get(p.T, T, 0, kl); get(p.Cp, Cp, 0, 16); get(p.Mout, Mo, 0, m); get(p.LTout, LT, 0, m);
+            finish();
+            return;
+        }
+        if (st == DRE_WARM_PROBE_EIG) {
+            Mat S(c, m, m), U = nan_mat(m, m, m);
+            up(S.p, p.S, (size_t)m * m);
+            warm_eig(c, m, S, U);
+            get(p.U, U, 0, m);
+            finish();
+            return;
+        }
+        if (st == DRE_WARM_PROBE_FINISH) {
+            const int rc = 16 * ceil_div(kl, 16);
+            Mat B = nan_mat(n, ldn, q), Wk(c, q, kl), Yp = nan_mat(n, ldn, 16), Pp(c, q, 16), R = nan_mat(n, ldn, rc);
+            put(p.Q, B, 0, n, q); up(Wk.p, p.Wk, (size_t)q * kl); put(p.Yp, Yp, 0, n, 16); up(Pp.p, p.Pp, (size_t)q * 16);
+            DevArr<double> slab = nan_arr((size_t)nstrip), tols(c, 12);
+            up(tols.p, p.tols_in, 12);
+            warm_finish(c, n, q, kl, B, Wk, Yp, Pp, R, slab.p, tickets + 1, tols.p);
+            get(p.R, R, 0, rc); down(p.tols, tols.p, 12); down(p.slab, slab.p, (size_t)nstrip);
+            finish();
+            return;
+        }
+        // CHAIN: the Jacobi form of the dense-X time loop's compression
+        WarmChain w;
+        const int mb = q + 16;
+        w.n = n; w.qb = q; w.kl = kl; w.qn = qn;
+        w.Res = nan_mat(n, ldn, n); w.QOc = nan_mat(n, ldn, 32 + 64 + 16); w.QOn = nan_mat(n, ldn, 32 + 64 + 16);
+        put(p.Res, w.Res, 0, n, n); put(p.basis, w.QOc, 0, n, 32 + q);
+        w.YB = nan_mat(n, ldn, 64 + q); w.Z1 = nan_mat(n, ldn, 16); w.Cc = nan_mat(mb, mb, 64 + q); w.Uc = nan_mat(mb, mb, qn); w.Cp = nan_mat(mb, mb, 16);
+        w.Pf = nan_mat(q, q, 16); w.Tm = nan_mat(kl, kl, kl);
+        DevArr<double> slab = nan_arr((size_t)nstrip * 256 + nstrip + 256), parts(c, std::max(p.nparts, 1)), tols = nan_arr(12);
+        up(parts.p, p.parts, (size_t)p.nparts);
+        w.slab = slab.p; w.tickets = tickets; w.tols = tols.p;
+        w.parts = p.nparts ? parts.p : nullptr; w.nparts = p.nparts; w.reltol = p.reltol; w.abstol = p.abstol; w.frac = p.frac; w.bf = p.budget_frac;
+        warm_chain_jacobi(c, w);
+        get(p.R, w.QOn, 32, qn); get(p.basis_out, w.QOc, 0, 32 + q + 16); get(p.T, w.Tm, 0, kl); get(p.Uc, w.Uc, 0, qn); get(p.Cp, w.Cp, 0, 16);
+        down(p.tols, tols.p, 12);
+        finish();
     });
 }
 // ---- dre_adi_chain_probe: the dense-inverse ADI chain on caller-supplied operands (test and diagnostic surface) ----------------------------

@@ -291,5 +291,19 @@ void warm_ctl(Ctx* ctx, double* tols, int* ticket, int J);
 void warm_eig(Ctx* ctx, int m, const Mat& S, Mat& U);
 int warm_project_slabs(int n);                                 // workgroups of warm_project (slab: 256 doubles each)
 void warm_zapply(Ctx* ctx, int n, const Mat& Z1, const double* Cw, Mat& Zb, Mat& Zy);
+// The launch sequence of one warm-started compression of a DENSE residual (n <= 1024), owned by warm.hip: the dense-X time loop (dense_x.hip,
+// compress_warm) and dre_warm_probe both go through it.  The caller allocates and keeps everything until the stream has passed the launches.
+struct WarmChain {
+    int n = 0, qb = 0, kl = 0, qn = 0;        // order, columns of the basis, the chain's width, columns of the next basis
+    Mat Res;                                   // n x n
+    Mat QOc, QOn;                              // basis buffers, n x (32 + 64 + 16) or wider: [Om_p, Om_f | Q | Z]; the next basis goes to QOn's columns 32 .. 32 + qn
+    const double* parts = nullptr; int nparts = 0; double reltol = 0.0, abstol = -1.0, frac = 1.0, bf = 0.4;
+    double* tols = nullptr;                    // 12 doubles
+    int* tickets = nullptr;                    // [0]: warm_project, [1]: warm_small and warm_finish
+    double* slab = nullptr;                    // nstrip x 256 shares of Z_1'Z_1 | nstrip shares of the probe | Cw (256),  nstrip = ceil(n / 16)
+    Mat YB, Pf, Z1, Cc, Uc, Cp, Tm;            // n x (64 + qb), qb x 16, n x 16, mb x (64 + qb), mb x qn, mb x 16, kl x kl;  mb = qb + 16
+};
+void warm_chain_front(Ctx* ctx, WarmChain& w);       // [Y_p, Y_f, W], P_f, Z_1 and C, Z and W_2, B'[Y_p, Y_f, W, Z, W_2]: five launches
+void warm_chain_jacobi(Ctx* ctx, WarmChain& w);      // the front, then warm_small (mode 0) and warm_finish
 
 }  // namespace dre

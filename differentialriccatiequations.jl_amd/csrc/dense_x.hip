@@ -428,7 +428,8 @@ bool DenseStep::warm_try() const {
            sx.q_cols + 32 <= n && !(ctx->dense_x_max_k > 0 && sx.q_cols > ctx->dense_x_max_k);
 }
 
-// B = [Q, Z]: the previous step's eigenbasis + 16 fresh directions; see warm.hip for the six launches
+// B = [Q, Z]: the previous step's eigenbasis + 16 fresh directions; the launches are warm.hip's (warm_chain_jacobi: eight; the wide-basis
+// variant shares the first five, warm_chain_front)
 Compressed DenseStep::compress_warm() {
     Compressed cz;
     const int qb = sx.q_cols, mb = qb + 16;
@@ -436,24 +437,19 @@ Compressed DenseStep::compress_warm() {
     const int qn = std::min(std::min(mb, WARM_QCAP), kl + (ctx->dense_warm == 2 ? 16 : 0));      // columns of the next basis (the leading eigen-directions; dense_warm = 2: 16 spare ones)
     Mat& QOc = sx.QO[sx.qcur];
     Mat& QOn = sx.QO[1 - sx.qcur];
-    Mat YB(ctx, n, 64 + qb), Z1(ctx, n, 16), Cc(ctx, mb, 64 + qb), Uc(ctx, mb, qn), Cp(ctx, mb, 16);
+    WarmChain w;
+    w.n = n; w.qb = qb; w.kl = kl; w.qn = qn;
+    w.YB = Mat(ctx, n, 64 + qb); w.Z1 = Mat(ctx, n, 16); w.Cc = Mat(ctx, mb, 64 + qb); w.Uc = Mat(ctx, mb, qn); w.Cp = Mat(ctx, mb, 16);
     DevArr<double> slab(ctx, (size_t)nt * 256 + nt + 256);
-    double* const Cw = slab.p + (size_t)nt * 256 + nt;
+    w.Pf = Mat(ctx, qb, 16);
+    w.Res = Res; w.QOc = QOc; w.QOn = QOn; w.slab = slab.p; w.tickets = sx.tickets.p; w.tols = tols.p;
+    w.parts = part.p; w.nparts = nt * nt; w.reltol = reltol; w.abstol = adi.abstol; w.frac = adi.residual_abs_frac;
+    w.bf = sx.est_ratio < 0.0 ? 0.4 : std::min(0.6, std::max(0.05, 1.0 - 2.6 * sx.est_ratio));
     side.start();      // (the side stream's dozen launches are enqueued by the parked thread while this one enqueues the compression)
-    gemm_thin(ctx, false, n, 32 + qb, n, 1.0, Res.p, Res.ld, QOc.p, QOc.ld, 0.0, YB.p, YB.ld, nullptr, "warm_project");     // [Y_p, Y_f, W] = Res [Om_p, Om_f, Q]
-    Mat Qb = QOc.colsview(32, qb), Bb = QOc.colsview(32, mb), Yp = YB.colsview(0, 16), Yf = YB.colsview(16, 16);
-    Mat Pf(ctx, qb, 16);
-    gemm_thin(ctx, true, qb, 16, n, 1.0, Qb.p, Qb.ld, Yf.p, Yf.ld, 0.0, Pf.p, Pf.ld, nullptr, "warm_project");                    // P_f = Q'Y_f
-    warm_project(ctx, n, qb, Qb, Yf, Pf, Z1, slab.p, sx.tickets.p, Cw);
-    Mat Zb = QOc.colsview(32 + qb, 16), Zy = YB.colsview(32 + qb, 16), W2 = YB.colsview(48 + qb, 16);
-    warm_z(ctx, n, Z1, Cw, Res, Zb, Zy, W2);
-    gemm_thin(ctx, true, mb, 64 + qb, n, 1.0, Bb.p, Bb.ld, YB.p, YB.ld, 0.0, Cc.p, Cc.ld, nullptr, "warm_project");           // B' [Y_p, Y_f, W, Z, W_2]
-    const double bf = sx.est_ratio < 0.0 ? 0.4 : std::min(0.6, std::max(0.05, 1.0 - 2.6 * sx.est_ratio));
     if (mb <= 48 || ctx->dense_warm != 3) {
-        cz.Tm = Mat(ctx, kl, kl);
-        warm_small(ctx, qb, mb, kl, qn, Cc, part.p, nt * nt, reltol, adi.abstol, adi.residual_abs_frac, bf, tols.p, Uc, cz.Tm, Cp, sx.tickets.p + 1);
+        w.Tm = cz.Tm = Mat(ctx, kl, kl);
+        warm_chain_jacobi(ctx, w);                      // the eight launches of the Jacobi form (warm.hip)
         Mat Rfull = QOn.colsview(32, qn);
-        warm_finish(ctx, n, mb, qn, Bb, Uc, Yp, Cp, Rfull, slab.p + (size_t)nt * 256, sx.tickets.p + 1, tols.p);
         cz.R = Rfull.colsview(0, kl);
         cz.k = kl;
         cz.wq_next = qn;
@@ -461,9 +457,10 @@ Compressed DenseStep::compress_warm() {
         // wide basis (the first warm steps behind a cold one: its Krylov basis is not an eigenbasis, and a Jacobi iteration on 80 x 80 from
         // scratch costs a millisecond): the small kernel stops behind the whitening and hands M over; its band reduction (the cold path's
         // kernels on an 80-row matrix, with their read-back) gives a basis of J_b columns, narrow enough for the Jacobi form from the next step on
+        warm_chain_front(ctx, w);
         Mat Mw(ctx, mb, mb), LT(ctx, mb, mb);
         cz.Tm = Mat(ctx, kl, kl);
-        warm_small(ctx, qb, mb, kl, qn, Cc, part.p, nt * nt, reltol, adi.abstol, adi.residual_abs_frac, bf, tols.p, Uc, cz.Tm, Cp, sx.tickets.p + 1, &Mw, &LT);
+        warm_small(ctx, qb, mb, kl, qn, w.Cc, w.parts, w.nparts, w.reltol, w.abstol, w.frac, w.bf, tols.p, w.Uc, cz.Tm, w.Cp, sx.tickets.p + 1, &Mw, &LT);
         side.join();
         SymBand wsb = sym_band_reduce(ctx, Mw, adi.compress_tolfac, -1.0, tols.p + 3);
         cz.k = wsb.J;
@@ -473,13 +470,13 @@ Compressed DenseStep::compress_warm() {
         gemm_thin(ctx, false, mb, cz.k, mb, 1.0, LT.p, LT.ld, Bq.p, Bq.ld, 0.0, Ub.p, Ub.ld, nullptr, "warm_project");
         cz.Tm = wsb.D;
         warm_ctl(ctx, tols.p, sx.tickets.p + 1, cz.k);
-        Mat Rfull = QOn.colsview(32, cz.k);
-        warm_finish(ctx, n, mb, cz.k, Bb, Ub, Yp, Cp, Rfull, slab.p + (size_t)nt * 256, sx.tickets.p + 1, tols.p);
+        Mat Bb = QOc.colsview(32, mb), Yp = w.YB.colsview(0, 16), Rfull = QOn.colsview(32, cz.k);
+        warm_finish(ctx, n, mb, cz.k, Bb, Ub, Yp, w.Cp, Rfull, slab.p + (size_t)nt * 256, sx.tickets.p + 1, tols.p);
         cz.R = Rfull;
         cz.wq_next = cz.k;
         keepV.push_back(Mw); keepV.push_back(LT); keepV.push_back(Bq); keepV.push_back(Ub);
     }
-    keepV.push_back(YB); keepV.push_back(Pf); keepV.push_back(Z1); keepV.push_back(Cc); keepV.push_back(Uc); keepV.push_back(Cp);
+    keepV.push_back(w.YB); keepV.push_back(w.Pf); keepV.push_back(w.Z1); keepV.push_back(w.Cc); keepV.push_back(w.Uc); keepV.push_back(w.Cp);
     keepRpk.push_back(slab.buf);
     cz.warm_tols = tols.p;
     cz.wnext = 1 - sx.qcur;

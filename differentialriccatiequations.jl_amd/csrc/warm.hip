@@ -268,8 +268,9 @@ void warm_zapply(Ctx* ctx, int n, const Mat& Z1, const double* Cw, Mat& Zb, Mat&
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // k_warm_small: the small generalized eigenproblem in one workgroup.
-// tols layout (8 doubles): [0] abstol of the Lyapunov solve (adi.jl:61-62), [1] truncation tolerance of the residual compression, [2] ||rhs||_F,
-// [3] unused, [4] J (rank kept), [5] reject flag, [6] estimate of ||(I - P_B) Res||_F^2, [7] dropped^2 + off^2
+// tols layout (12 doubles): [0] abstol of the Lyapunov solve (adi.jl:61-62), [1] truncation tolerance of the residual compression, [2] ||rhs||_F,
+// [3] mode 0: sweeps + 1e-4 rounds with a rotation + 1e-7 active coordinates (diagnostics), mode 1: the band reduction's tolerance, [4] J (rank kept), [5] reject flag,
+// [6] estimate of ||(I - P_B) Res||_F^2, [7] dropped^2 + off^2 (mode 1: the truncation's budget), [8..10] mode 0: timings (diagnostics), [11] unused
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct WarmSmallArgs {
     int q, m, kl, qn;                  // basis columns, m = q + 16 (q when there are no fresh directions), chain width, columns of the next basis
@@ -881,6 +882,30 @@ void warm_finish(Ctx* ctx, int n, int q, int kl, const Mat& Q, const Mat& Wk, co
     TimedScope ts(ctx, "warm_finish", 8.0 * ((double)n * q + (double)n * kl + 16.0 * n), 2.0 * n * (double)q * (kl + 16));
     hipLaunchKernelGGL(k_warm_finish, dim3(ceil_div(n, 16)), dim3(256), 0, ctx->stream, a);
     DRE_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The launch sequence in front of the ADI chain, for the dense-X time loop and for dre_warm_probe alike
+// ---------------------------------------------------------------------------------------------------------------------------------
+void warm_chain_front(Ctx* ctx, WarmChain& w) {
+    const int n = w.n, qb = w.qb, mb = qb + 16, nt = ceil_div(n, 16);
+    const Mat &Res = w.Res, &QOc = w.QOc;
+    Mat &YB = w.YB, &Pf = w.Pf, &Z1 = w.Z1, &Cc = w.Cc;
+    double* const Cw = w.slab + (size_t)nt * 256 + nt;
+    gemm_thin(ctx, false, n, 32 + qb, n, 1.0, Res.p, Res.ld, QOc.p, QOc.ld, 0.0, YB.p, YB.ld, nullptr, "warm_project");     // [Y_p, Y_f, W] = Res [Om_p, Om_f, Q]
+    Mat Qb = QOc.colsview(32, qb), Bb = QOc.colsview(32, mb), Yf = YB.colsview(16, 16);
+    gemm_thin(ctx, true, qb, 16, n, 1.0, Qb.p, Qb.ld, Yf.p, Yf.ld, 0.0, Pf.p, Pf.ld, nullptr, "warm_project");                    // P_f = Q'Y_f
+    warm_project(ctx, n, qb, Qb, Yf, Pf, Z1, w.slab, w.tickets, Cw);
+    Mat Zb = QOc.colsview(32 + qb, 16), Zy = YB.colsview(32 + qb, 16), W2 = YB.colsview(48 + qb, 16);
+    warm_z(ctx, n, Z1, Cw, Res, Zb, Zy, W2);
+    gemm_thin(ctx, true, mb, 64 + qb, n, 1.0, Bb.p, Bb.ld, YB.p, YB.ld, 0.0, Cc.p, Cc.ld, nullptr, "warm_project");           // B' [Y_p, Y_f, W, Z, W_2]
+}
+void warm_chain_jacobi(Ctx* ctx, WarmChain& w) {
+    const int n = w.n, qb = w.qb, mb = qb + 16, nt = ceil_div(n, 16);
+    warm_chain_front(ctx, w);
+    warm_small(ctx, qb, mb, w.kl, w.qn, w.Cc, w.parts, w.nparts, w.reltol, w.abstol, w.frac, w.bf, w.tols, w.Uc, w.Tm, w.Cp, w.tickets + 1);
+    Mat Bb = w.QOc.colsview(32, mb), Yp = w.YB.colsview(0, 16), Rfull = w.QOn.colsview(32, w.qn);
+    warm_finish(ctx, n, mb, w.qn, Bb, w.Uc, Yp, w.Cp, Rfull, w.slab + (size_t)nt * 256, w.tickets + 1, w.tols);
 }
 
 }  // namespace dre

@@ -216,6 +216,41 @@ typedef struct dre_adi_chain_probe_args {
     int32_t* state_i; double* state_d;
 } dre_adi_chain_probe_args;
 int dre_adi_chain_probe(dre_ctx* ctx, const dre_adi_chain_probe_args* args);
+/* Test and diagnostic surface of the warm-started compression (dre_version >= 120; csrc/warm.hip, DESIGN.md "warm probe"): ONE call of an entry
+ * point of that file on caller-supplied operands, in buffers shaped like those of the library's own callers (the basis buffer [Om | Q | Z], the
+ * right-hand block [Y_p, Y_f, W, Z, W_2], the slab of nslab 256 + nstrip + 256 doubles with C behind the shares, the context's block of four
+ * arrival counters, zeroed once per context).  No kernel of its own.  Every array is HOST memory, column-major, without padding; every output may
+ * be NULL; every output is prefilled with NaN on the device, so what a kernel never wrote comes back as NaN.  Matrices of n rows live in
+ * allocations of n + ldpad rows (the library's callers: ldpad = 0) and their OUTPUTS come back with all n + ldpad rows.
+ * stage 0 PROJECT (warm_project):  Q (n x q), Yf (n x 16), Pf (q x 16)  ->  Z1_out ((n + ldpad) x 16), Cw_out (16 x 16), slab (nslab x 256 shares of
+ *   Z_1'Z_1, share (i, j) of workgroup b at 256 b + i + 16 j;  nslab = ceil(n / rows), rows = 16 up to 256 strips of 16 rows, else 16 ceil(strips / 256)).
+ * stage 1 Z (warm_z, n <= 1024):  Z1 (n x 16), Cw, Res (n x n)  ->  Zb, Zy, W2 ((n + ldpad) x 16 each).   stage 2 ZAPPLY (warm_zapply): Z1, Cw -> Zb, Zy.
+ *   q only places the views inside the two buffers.
+ * stage 3 SMALL (warm_small; mode 0: the Jacobi form, mode 1: stops behind the whitening):  Cc (m x (64 + q)) = [P_p | . | B'W | B'Z | B'W_2], parts
+ *   (nparts, or NULL with 0), reltol, abstol, frac, budget_frac, kl, qn  ->  tols (12), Uc (m x qn), T (kl x kl), Cp (m x 16), mode 1: Mout, LTout (m x m).
+ * stage 4 EIG (warm_eig):  S (m x m)  ->  U (m x m).
+ * stage 5 FINISH (warm_finish):  Q = B (n x q, q <= 80), Wk (q x kl), Yp (n x 16), Pp (q x 16), tols_in (12: [1], [5], [7] are read)  ->  R ((n + ldpad) x
+ *   16 ceil(kl / 16)), tols (12), slab (ceil(n / 16) shares of the probe).
+ * stage 6 CHAIN (the launch sequence of the dense-X time loop's compression, Jacobi form, n <= 1024):  Res (n x n), basis (n x (32 + q): [Om_p, Om_f, Q]),
+ *   parts / nparts, reltol, abstol, frac, budget_frac, kl, qn (at most 64)  ->  R ((n + ldpad) x qn: the next basis, its first kl columns the chain's R),
+ *   basis_out ((n + ldpad) x (32 + q + 16): with Z in the last 16 columns), T, tols, Uc ((q + 16) x qn), Cp ((q + 16) x 16).
+ * ticket (2): the arrival counters of warm_project and of warm_small / warm_finish after the call.
+ * DRE_ERR_INVALID before any launch: an unknown stage, n < 1, q outside 1 .. 64 (FINISH: 1 .. 80), m not q or q + 16, m > 80, qn outside 1 .. m, kl
+ * outside 1 .. qn (FINISH: 1 .. 80), n > 1024 for Z and CHAIN, mode outside {0, 1}, nparts without parts, a missing input.  The context stays usable. */
+enum { DRE_WARM_PROBE_PROJECT = 0, DRE_WARM_PROBE_Z = 1, DRE_WARM_PROBE_ZAPPLY = 2, DRE_WARM_PROBE_SMALL = 3, DRE_WARM_PROBE_EIG = 4, DRE_WARM_PROBE_FINISH = 5,
+       DRE_WARM_PROBE_CHAIN = 6 };
+typedef struct dre_warm_probe_args {
+    int32_t stage, n, q, m;
+    int32_t kl, qn, nparts, mode;
+    int32_t ldpad, reserved;
+    double reltol, abstol, frac, budget_frac;
+    const double* Q; const double* Yf; const double* Pf; const double* Z1; const double* Cw; const double* Res; const double* Cc; const double* parts;
+    const double* S; const double* Wk; const double* Yp; const double* Pp; const double* tols_in; const double* basis;
+    double* Z1_out; double* Cw_out; double* slab; double* Zb; double* Zy; double* W2; double* tols; double* Uc; double* T; double* Cp; double* Mout;
+    double* LTout; double* U; double* R; double* basis_out;
+    int32_t* ticket;
+} dre_warm_probe_args;
+int dre_warm_probe(dre_ctx* ctx, const dre_warm_probe_args* args);
 /* eigen(Symmetric(S)) by two-sided cyclic block Jacobi on the whole device (blocks of 16, round-robin ordering, both products of the update on
  * v_mfma_f64_16x16x4_f64): all q eigenpairs, values ascending, S untouched (full symmetric storage; indefinite, rank-deficient and clustered
  * spectra are fine).  Converged when off(A) <= tol ||A||_F; tol <= 0: q eps.  stats (may be NULL): [0] block sweeps, [1] rounds.

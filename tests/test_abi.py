@@ -17,7 +17,7 @@ def test_every_declared_symbol_is_exported_and_bound():
     import dre_amd as D
     lib = D._lib.load()
     names = _declared()
-    assert len(names) >= 129 and "dre_adi_chain_probe" in names
+    assert len(names) >= 130 and "dre_adi_chain_probe" in names and "dre_warm_probe" in names
     for n in names:
         assert hasattr(lib, n), f"{n} declared in dre_hip.h but not exported"
         assert n in D._lib.PROTOTYPES, f"{n} has no ctypes prototype"
@@ -71,13 +71,13 @@ def test_adi_options_struct_layout_matches_the_header(tmp_path):
 
 
 def test_gemm_probe_struct_layouts_match_the_header(tmp_path):
-    """`dre_gemm_view`, `dre_gemm_product`, `dre_gemm_probe_options` and `dre_adi_chain_probe_args` cross the boundary BY LAYOUT (ctypes `GemmViewC`,
+    """`dre_gemm_view`, `dre_gemm_product`, `dre_gemm_probe_options`, `dre_adi_chain_probe_args` and `dre_warm_probe_args` cross the boundary BY LAYOUT (ctypes `GemmViewC`,
     `GemmProductC`, `GemmProbeOptionsC`, `AdiChainProbeArgsC`): sizes and the offset of every field are compared with what the C compiler makes of include/dre_hip.h."""
     import ctypes as C
     import subprocess
     import dre_amd as D
     pairs = (("dre_gemm_view", D._lib.GemmViewC), ("dre_gemm_product", D._lib.GemmProductC), ("dre_gemm_probe_options", D._lib.GemmProbeOptionsC),
-             ("dre_adi_chain_probe_args", D._lib.AdiChainProbeArgsC))
+             ("dre_adi_chain_probe_args", D._lib.AdiChainProbeArgsC), ("dre_warm_probe_args", D._lib.WarmProbeArgsC))
     body = "".join(f'printf("%zu ", sizeof({c}));' + "".join(f'printf("%zu ", offsetof({c}, {f[0]}));' for f in T._fields_) for c, T in pairs)
     src = tmp_path / "probe_layout.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dre_hip.h"\nint main(void) { ' + body + ' return 0; }\n')
