@@ -1,5 +1,5 @@
 // In-place Gauss-Jordan inversion with row pivoting (dense_gj.hip), and the small host-side helpers that the dense sign-function family
-// (dense_sign.hip, dense_sign_lr.hip, dense_are.hip, dre_dense_invert of api.hip) shares.  See DESIGN.md, "Dense path".
+// (dense_sign.hip, dense_sign_lr.hip, dense_are.hip, dre_dense_invert of api_dense.hip) shares.  See DESIGN.md, "Dense path".
 #pragma once
 #include <algorithm>
 #include <limits>

@@ -1,4 +1,4 @@
-// Bounds check of dre_gemm_probe's operand views (api.hip).  Plain host C++ without any HIP type, so that a stand-alone program can test it on
+// Bounds check of dre_gemm_probe's operand views (api_probe.hip).  Plain host C++ without any HIP type, so that a stand-alone program can test it on
 // a machine without a GPU (tests/test_gemm_tilemap_host.py): this check is what keeps a wrong probe call from reading or writing outside a buffer.
 #pragma once
 #include <cstdint>

@@ -167,8 +167,10 @@ def test_probe_adds_no_kernel_and_launches_only_through_the_chain():
     import os
     import re
     from conftest import ROOT
-    api = open(os.path.join(ROOT, "differentialriccatiequations.jl_amd", "csrc", "api.hip")).read()
-    body = api[api.index("int dre_adi_chain_probe("):api.index("int dre_sym_eig_jacobi(")]
+    api = open(os.path.join(ROOT, "differentialriccatiequations.jl_amd", "csrc", "api_probe.hip")).read()
+    start = api.index("int dre_adi_chain_probe(")
+    end = api.find("// ---- dre_", start)          # the next probe's banner, or the end of the file
+    body = api[start:end if end >= 0 else len(api)]
     assert "hipLaunchKernelGGL" not in body and "<<<" not in body and "__global__" not in body
     called = set(re.findall(r"\b(adi_[a-z_]+|gemm[a-z_]*|copy_mat|fill_mat|residual_norm[a-z_]*|dense_adi_step)\s*\(", body))
     assert called == {"adi_fast_build", "adi_fast_pack_r", "adi_fast_iter", "adi_group_pack", "adi_group_iter", "adi_fast_pick", "adi_fast_nstrip",

@@ -161,8 +161,10 @@ def test_probe_prototype_matches_the_header_and_the_version():
             assert a is C.c_int, p
     # the source refuses before it launches: the checks stand in front of the copy of S and the call of sym_eig, the finite check of
     # sym_eig in front of the QL stage
-    api = open(os.path.join(ROOT, "differentialriccatiequations.jl_amd", "csrc", "api.hip")).read()
-    body = api[api.index("int dre_sym_eig_probe("):api.index("int dre_sym_eig_jacobi(")]
+    api = open(os.path.join(ROOT, "differentialriccatiequations.jl_amd", "csrc", "api_probe.hip")).read()
+    start = api.index("int dre_sym_eig_probe(")
+    end = api.find("// ---- dre_", start)          # the next probe's banner, or the end of the file
+    body = api[start:end if end >= 0 else len(api)]
     assert body.index("square matrix expected") < body.index("order above 8192") < body.index("copy_mat") < body.index("sym_eig(c, A")
     assert body.index("sym_eig(c, A") < body.index("outside [0, jdim)") < body.index("sym_eig_backtransform")
     assert "c->sym_eig_method = 0" in body and "~Method0" in body

@@ -229,8 +229,10 @@ def test_widest_problem_is_accepted_and_the_next_q_refused():
 
 def test_probe_adds_no_kernel_and_launches_only_through_the_entry_points():
     from conftest import ROOT
-    api = open(os.path.join(ROOT, "differentialriccatiequations.jl_amd", "csrc", "api.hip")).read()
-    body = api[api.index("int dre_warm_probe("):api.index("// ---- dre_adi_chain_probe")]
+    api = open(os.path.join(ROOT, "differentialriccatiequations.jl_amd", "csrc", "api_probe.hip")).read()
+    start = api.index("int dre_warm_probe(")
+    end = api.find("// ---- dre_", start)          # the next probe's banner, or the end of the file
+    body = api[start:end if end >= 0 else len(api)]
     assert "hipLaunchKernelGGL" not in body and "<<<" not in body and "__global__" not in body
     called = set(re.findall(r"\b(warm_[a-z_]+|gemm[a-z_]*|copy_mat|fill_[a-z]+)\s*\(", body))
     assert called == {"warm_project", "warm_z", "warm_zapply", "warm_small", "warm_eig", "warm_finish", "warm_chain_jacobi", "warm_project_slabs"}
